@@ -13,6 +13,11 @@ owns its own 10^5-cell shard of an N x 10^5-cell surface; the per-rank spectra a
 summed with one RCCL all-reduce (torch.distributed 'nccl' = RCCL over xGMI).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config config2] [--df-mode 1..5]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K passes and prints the result line.  --dump-outputs DIR also writes what
+the last timed pass computed as DIR/<name>.npy (dump_outputs).  --full adds the other measurements to the same line:
+the per-species timing of the main workload, the north_star workload (config 4) and the CPU legs (cpu_baseline).
 
 Ranks: under a launcher (torch.distributed.run sets WORLD_SIZE / RANK / LOCAL_RANK) the world comes from the
 environment and --gpus must agree with it; a plain `python bench.py --gpus N` with N > 1 starts the N rank
@@ -121,6 +126,25 @@ def make_surface(cfg, rank, world, dim, baryon, whole=False):
             return s, (lo, hi)
         return {k: np.ascontiguousarray(v[lo:hi]) for k, v in s.items()}, None
     return synth.as_read(synth.surface(cfg["cells"], seed=7 + rank, dimension=dim, baryon=baryon, full3d=(dim == 3))), None
+
+
+DUMP_MAX_BYTES = 64 * 10 ** 6      # --dump-outputs: every file of one run together
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: write {name: array} as path/<name>.npy in float64, DUMP_MAX_BYTES at the most in all.  An
+    array larger than its share of that is written as a fixed sample: <name>.npy then holds the values at the flat
+    indices listed (as float64, ascending) in <name>_index.npy, drawn without replacement by a generator seeded with 0
+    -- the same entries for every run and every build, so two dumps compare entry for entry."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_MAX_BYTES // len(arrays) - 256             # 256: two .npy headers
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=share // 16, replace=False))
+            np.save(os.path.join(path, name + "_index.npy"), idx.astype(np.float64))
+            a = a.ravel()[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def _host_cpu():
@@ -270,10 +294,12 @@ def executed_roofline(args, mode, ms_spectra, ms_total, neta, units_local, n_loc
     return r
 
 
-def run_workload(args, cfg_name, mode, steps, warmup, rank, world, local_rank, dev, dist, classes=True):
+def run_workload(args, cfg_name, mode, steps, warmup, rank, world, local_rank, dev, dist, classes=True, dump=None):
     """Build the engine for one workload on this rank's shard, run `warmup` untimed and `steps` timed
     passes (barrier + synchronize on both sides, max over ranks) and return the measurement.  classes: the
-    engine's integrand classes (is3d_set_species_classes; the default) or one integral per species."""
+    engine's integrand classes (is3d_set_species_classes; the default) or one integral per species.  dump: a
+    directory for what the last timed pass computed (rank 0 writes it after the clock has stopped, dump_outputs):
+    the spectra [species][pT][phi][y], summed over the ranks, or operation 0's three binned distributions."""
     import torch
     from is3d2_amd import build_engine, make_spec
     from is3d2_amd import dist as D
@@ -327,12 +353,16 @@ def run_workload(args, cfg_name, mode, steps, warmup, rank, world, local_rank, d
     if operation == 0 and world > 1 and spec["bins"].get("threads", 0):
         raise SystemExit("operation 0 with reference thread emulation runs on one rank")
 
+    last = {}       # operation 0: what the latest pass returned (the spectra of operation 1 land in `out`)
+
     def step():
         if operation == 0:
             t, r, ph = eng.calculate_dN_dX()      # synchronous: device passes + small host binning epilogue
+            last.update(binned=None, dN_taudtaudy=t, dN_2pirdrdy=r, dN_dphidy=ph)
             if world > 1:
                 binned = torch.from_numpy(np.concatenate([t.ravel(), r.ravel(), ph.ravel()])).to(dev)
                 dist.all_reduce(binned)
+                last["binned"] = binned
             return eng.stats()
         if qrange is not None:
             if args.backend == "nccl":
@@ -369,6 +399,15 @@ def run_workload(args, cfg_name, mode, steps, warmup, rank, world, local_rank, d
         dist.all_reduce(units_all)
     elapsed = tmax.item()
     total_units = units_all.item() * steps
+    if dump and rank == 0:
+        if operation == 0:
+            arrays = {k: last[k] for k in ("dN_taudtaudy", "dN_2pirdrdy", "dN_dphidy")}
+            if last["binned"] is not None:      # N > 1: the sums over the ranks, cut back into the three arrays
+                parts = np.split(last["binned"].cpu().numpy(), np.cumsum([a.size for a in arrays.values()])[:-1])
+                arrays = {k: p.reshape(a.shape) for (k, a), p in zip(arrays.items(), parts)}
+        else:
+            arrays = {"spectra": out.cpu().numpy().reshape(nsp, npT, nphi, ny)}
+        dump_outputs(dump, arrays)
     eng.close()
     del out
 
@@ -424,18 +463,27 @@ def main():
     ap.add_argument("--chosen", default="", help="override the chosen-species list (pikp, smash, urqmd)")
     ap.add_argument("--operation", type=int, default=1, choices=[0, 1],
                     help="1 continuous spectra (default, the BASELINE metric); 0 spacetime distributions dN/dX")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed passes write what the last one computed as DIR/<name>.npy (float64; an array "
+                         "too large for the 64 MB limit as a fixed seeded sample with its <name>_index.npy)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the per-species timing of the main "
+                         "workload, the north_star workload and the CPU legs (each with its own opt-out below)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU legs")
     ap.add_argument("--no-per-species", action="store_true",
-                    help="skip the second timing of the main workload with one integral per species (classes off)")
+                    help="with --full: skip the second timing of the main workload with one integral per species "
+                         "(classes off)")
     ap.add_argument("--cpu-seconds", type=float, default=25.0)
     ap.add_argument("--tune", action="append", metavar="KEY=VALUE",
                     help="engine tuning knob (is3d_set_tuning), e.g. max_splits=128; repeatable")
     ap.add_argument("--north-star-steps", type=int, default=3,
-                    help="timed passes of the north_star workload (config4: 10^6 3+1D cells, SMASH, RTA-CE, "
-                         "sharded over the ranks) reported beside the main line; 0 skips it")
+                    help="with --full: timed passes of the north_star workload (config4: 10^6 3+1D cells, SMASH, "
+                         "RTA-CE, sharded over the ranks) reported beside the main line; 0 skips it")
     ap.add_argument("--north-star-cpu-seconds", type=float, default=20.0,
                     help="CPU-leg sample length of the north_star workload (rank 0, N = 1); 0 skips that leg")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
 
     world, spawn = resolve_world(args.gpus, os.environ)
     if spawn:
@@ -458,9 +506,10 @@ def main():
 
     from is3d2_amd import _lib
     log("build_id %s" % _lib.build_id())
-    m = run_workload(args, args.config, args.df_mode, args.steps, args.warmup, rank, world, local_rank, dev, dist)
+    m = run_workload(args, args.config, args.df_mode, args.steps, args.warmup, rank, world, local_rank, dev, dist,
+                     dump=args.dump_outputs)
     per_species = None
-    if not args.no_per_species and m["config"]["species_integrated"] < m["config"]["species"]:
+    if args.full and not args.no_per_species and m["config"]["species_integrated"] < m["config"]["species"]:
         # the same workload with one integral per species (integrand classes off): the same spectra to rounding
         # (< 1e-9, tests/test_gpu_classes.py), the kernel's per-species rate
         o = run_workload(args, args.config, args.df_mode, args.steps, 1, rank, world, local_rank, dev, dist,
@@ -471,7 +520,7 @@ def main():
                        "note": "same workload and clock rules with integrand classes off (is3d_set_species_classes(e, 0)): "
                                "every species integrated separately; equal to rounding (< 1e-9), tests/test_gpu_classes.py"}
     ns = None
-    if args.north_star_steps > 0 and args.config != "config4" and args.operation == 1:
+    if args.full and args.north_star_steps > 0 and args.config != "config4" and args.operation == 1:
         n = run_workload(args, "config4", 0, args.north_star_steps, 1, rank, world, local_rank, dev, dist)
         ns = {"metric": "freezeout-cell-species-mom-points/sec", "value": n["value"],
               "unit": "cell-species-mom-points/s", "steps": n["steps"], "warmup": n["warmup"],
@@ -507,7 +556,7 @@ def main():
             res["per_species_integration"] = per_species
         if ns is not None:
             res["north_star"] = ns
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(m["spec"], m["surf"], m["units_per_cell"], m["n_local"], args.cpu_seconds,
                                                args.operation)
         print(json.dumps(res), flush=True)

@@ -7,7 +7,7 @@
 TAG=${1:-sweep}; C5=${2:-5000000}
 OUT=gpurun_out/${TAG}_sweep.jsonl
 mkdir -p gpurun_out
-run() { timeout -k 10 300 python bench.py --no-cpu-baseline --north-star-steps 0 "$@" >> "$OUT" || exit $?; }
+run() { timeout -k 10 300 python bench.py --full --no-cpu-baseline --north-star-steps 0 "$@" >> "$OUT" || exit $?; }
 for m in 2 3 4 5; do run --steps 3 --warmup 1 --config config2 --df-mode $m; done
 for m in 1 2 3 4 5; do run --steps 2 --warmup 1 --config config3 --df-mode $m --no-per-species; done
 for m in 1 3; do run --steps 2 --warmup 1 --config config2 --operation 0 --df-mode $m --no-per-species; done
