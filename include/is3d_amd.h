@@ -24,6 +24,9 @@
  *   is3d_surface_averages             ds_max-weighted averages (Plasma)        (readindata.cpp:316-366, iS3D.cpp:184-219)
  *   is3d_total_yield                  calculate_total_yield (operation 2       (ParticleSampler.cpp:447-636,
  *                                     oversampling) + particle densities        DeltafData.cpp:555-690)
+ *   is3d_set_vorticity                thermal vorticity columns of a mode-5 surface (readindata.cpp:298-306)
+ *   is3d_calculate_polarization       calculate_spin_polzn, mode = 5            (Polarization.cpp:25-263,
+ *                                                                                EmissionFunction.cpp:1305-1310)
  *
  * Conventions: caller-owned host buffers in and out; the engine owns its HBM
  * buffers.  Errors are return codes (never exit()); is3d_last_error() gives the
@@ -258,6 +261,30 @@ int is3d_total_yield(is3d_engine *e, const double *plasma, double y_cut, double 
 
 int is3d_get_jonah_table(const is3d_engine *e, double *lambda2, double *z, double *bulk_over_P,
                          double *bulk_over_P_max);
+
+/* mode = 5, spin polarization from thermal vorticity (EmissionFunctionArray::calculate_spin_polzn,
+ * Polarization.cpp:25-263, run after the chosen operation at EmissionFunction.cpp:1305-1310).  The six
+ * thermal-vorticity components wbar^{tx ty tn xy xn yn} of every cell are the last six columns of a mode-5
+ * input/surface.dat (no unit conversion, readindata.cpp:298-306); host pointers, copied.  Set them after the
+ * surface: n_cells must equal the surface's, and setting a surface again clears them.
+ * S_out[c][ipart][ipT][iphi][iy], c = 0..4: the raw cell sums S_t, S_x, S_y, S_n, Snorm of the reference (the files
+ * hold S_c / Snorm), each in the spectra layout; 2+1D: one y = 0 slot, summed over the eta table with weights
+ * eta_weight x (eta_2 - eta_1) as in the reference.  T_avg = Plasma::temperature: one temperature for the whole
+ * surface, no chemical potential, no degeneracy, no (2 pi hbarc)^-3, every cell counted (no u.dsigma test).
+ * Needs params (dimension), species, momentum grid, surface and vorticity -- no delta-f tables, Gauss-Laguerre
+ * table or PDG set.  Honours is3d_set_cell_window, is3d_set_species_classes (classes by (mass, sign)) and the
+ * "max_splits" / "split_bytes" / "slab_bytes" knobs; sums in a fixed order (bit-reproducible).
+ * Two deliberate departures from the reference: the vorticity is indexed by the global cell (Polarization.cpp:131-136
+ * uses the index inside its 10 000-cell chunk: identical up to 10 000 cells), and the layout above is the one the
+ * row labels of the reference's files name (its writer, EmissionFunction.cpp:591, reads another index than its loop
+ * filled).  Errors: IS3D_ERR_STATE for a missing setup step, IS3D_ERR_ARG for T_avg <= 0 or a vorticity length
+ * other than the surface's.  is3d_launch_polarization + is3d_finish is the resident form (dev_out: device buffer of
+ * is3d_polarization_size doubles); is3d_get_stats then holds the cells and device times of the call. */
+typedef struct { const double *wtx, *wty, *wtn, *wxy, *wxn, *wyn; } is3d_vorticity;
+int is3d_set_vorticity(is3d_engine *e, long n_cells, const is3d_vorticity *w);
+long is3d_polarization_size(const is3d_engine *e);      /* 5 * is3d_output_size */
+int is3d_calculate_polarization(is3d_engine *e, double T_avg, double *S_out);
+int is3d_launch_polarization(is3d_engine *e, double T_avg, double *dev_out, void *stream);
 
 #ifdef __cplusplus
 }

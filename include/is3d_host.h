@@ -9,6 +9,9 @@
  *   is3d_host_total_yield          IS3D::run_particlization(1) for operation = 2: the oversampling
  *                                  estimate Ntotal / Nevents (EmissionFunction.cpp:1235-1249)
  *   is3d_host_read_surface         FO_data_reader::read_freezeout_surface modes 1/5/6/7 (readindata.cpp:149-731)
+ *   is3d_host_read_vorticity       the thermal-vorticity columns of a mode-5 surface    (readindata.cpp:298-306)
+ *   is3d_host_polarization         calculate_spin_polzn + write_polzn_vector_toFile     (Polarization.cpp:25-263,
+ *                                                                                        EmissionFunction.cpp:561-609)
  *   is3d_host_read_pdg             PDG_Data::read_resonances                            (readindata.cpp:1217-1252)
  *   is3d_host_param                ParameterReader::getVal                              (ParameterReader.cpp:142-155)
  */
@@ -37,6 +40,17 @@ int is3d_host_total_yield(const char *workdir, int device, int num_devices, doub
  * avg5 the Plasma averages T, E, P, muB, nB after the 15-digit round trip. */
 long is3d_host_read_surface(const char *workdir, int mode, int dimension, int include_baryon, double *fields,
                             double *avg5);
+/* The six thermal-vorticity columns of a mode-5 <workdir>/input/surface.dat (wbar^{tx ty tn xy xn yn}, no unit
+ * conversion, readindata.cpp:298-306): returns the number of cells (or < 0); w6 (optional) receives [6][n]. */
+long is3d_host_read_vorticity(const char *workdir, int dimension, int include_baryon, double *w6);
+/* mode = 5 only: EmissionFunctionArray::calculate_spin_polzn (Polarization.cpp:25-263) of the run directory on
+ * HIP devices devices[0..num_devices), at T = the Plasma average temperature, without running the operation:
+ * writes results/St.dat, Sx.dat, Sy.dat, Sn.dat (rows y, phi, pT, S_c / Snorm) and returns the raw sums
+ * S_out[5][species][pT][phi][y] (S_t S_x S_y S_n Snorm; optional, capacity doubles).
+ * is3d_host_run_particlization[_devices] of a mode = 5 directory runs the same after the chosen operation
+ * (EmissionFunction.cpp:1305-1310) and writes the same four files. */
+int is3d_host_polarization(const char *workdir, const int *devices, int num_devices, double *S_out, long out_capacity,
+                           char *err, int errlen);
 /* Returns the number of particles (or < 0); arrays optional (capacity entries). */
 int is3d_host_read_pdg(const char *workdir, int hrg_eos, int capacity, long *mcid, double *mass, int *gspin,
                        int *baryon, int *sign);

@@ -5,4 +5,5 @@ package is the Python host binding used by tests and bench.py; the C++ host laye
 (iS3D driver, readers, writers) lives in is3d2_amd/csrc/host.
 """
 from . import data, hrg, synth  # noqa: F401
+from ._lib import VORTICITY_FIELDS  # noqa: F401
 from .engine import Engine, IS3DError, build_engine, make_spec, output_shape, surface_averages  # noqa: F401

@@ -22,7 +22,10 @@ EXPORTS = ["is3d_abi_version", "is3d_build_id", "is3d_create", "is3d_create_devi
            "is3d_surface_averages", "is3d_get_jonah_table", "is3d_set_momentum_weights", "is3d_set_spacetime_bins",
            "is3d_calculate_dN_dX", "is3d_get_cell_yields", "is3d_total_yield", "is3d_set_chain_range",
            "is3d_launch_begin", "is3d_chain_passes", "is3d_chain_pass", "is3d_chain_end", "is3d_launch_end",
-           "is3d_chain_boundary_size", "is3d_chain_boundary_get", "is3d_chain_boundary_put"]
+           "is3d_chain_boundary_size", "is3d_chain_boundary_get", "is3d_chain_boundary_put",
+           "is3d_set_vorticity", "is3d_polarization_size", "is3d_calculate_polarization", "is3d_launch_polarization"]
+
+VORTICITY_FIELDS = ["wtx", "wty", "wtn", "wxy", "wxn", "wyn"]
 
 
 class Params(C.Structure):
@@ -40,6 +43,10 @@ class SpacetimeBins(C.Structure):
 
 class Surface(C.Structure):
     _fields_ = [(k, C.POINTER(C.c_double)) for k in SURFACE_FIELDS]
+
+
+class Vorticity(C.Structure):
+    _fields_ = [(k, C.POINTER(C.c_double)) for k in VORTICITY_FIELDS]
 
 
 class Stats(C.Structure):
@@ -109,6 +116,11 @@ def load():
     lib.is3d_chain_boundary_size.argtypes = [C.c_void_p]
     lib.is3d_chain_boundary_get.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     lib.is3d_chain_boundary_put.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    lib.is3d_set_vorticity.argtypes = [C.c_void_p, C.c_long, P(Vorticity)]
+    lib.is3d_polarization_size.restype = C.c_long
+    lib.is3d_polarization_size.argtypes = [C.c_void_p]
+    lib.is3d_calculate_polarization.argtypes = [C.c_void_p, d, pd]
+    lib.is3d_launch_polarization.argtypes = [C.c_void_p, d, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 

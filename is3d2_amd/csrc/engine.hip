@@ -68,6 +68,7 @@
 #include "spline_host.h"
 #include "kernels.h"
 #include "group.h"
+#include "polzn.h"
 
 using namespace is3d;
 using namespace is3d::kern;
@@ -941,6 +942,12 @@ struct is3d_engine {
   unsigned long long* d_cnt = nullptr;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   LaunchCtx lc;               // the launch in flight (staged launches)
+  // spin polarization (mode 5, polzn.hip): thermal vorticity [6][ncell] of the surface set last (a new surface
+  // clears it) and the kernels' constants, rebuilt after a species / classes / grid / params change
+  double* d_vort = nullptr; long vort_cap = 0; bool have_vort = false;
+  bool have_surf = false;    // a surface was set (an empty one set from device memory has no d_surf)
+  is3d::polzn::Tables pz;
+  bool pz_dirty = true;
   is3d_stats st{};
   bool launched = false;
 
@@ -1001,6 +1008,8 @@ extern "C" void is3d_destroy(is3d_engine* e) {
   if (e->join) (void)hipEventDestroy(e->join);
   dfree(e->d_ycell); dfree(e->d_part); dfree(e->d_keys); dfree(e->d_perm); dfree(e->d_offs);
   dfree(e->d_err); dfree(e->d_cnt);
+  dfree(e->d_vort);
+  is3d::polzn::tables_free(e->pz);
   for (auto& v : e->ev) if (v) (void)hipEventDestroy(v);
   delete e;
 }
@@ -1069,6 +1078,7 @@ extern "C" int is3d_set_params(is3d_engine* e, const is3d_params* p) {
   e->p = *p;
   e->have_params = true;
   e->tables_dirty = true;
+  e->pz_dirty = true;
   return IS3D_OK;
 }
 
@@ -1085,6 +1095,7 @@ extern "C" int is3d_set_species(is3d_engine* e, int n, const double* mass, const
   std::stable_sort(e->order.begin(), e->order.end(), [&](int a, int b) { return e->mass[a] < e->mass[b]; });
   e->have_species = true;
   e->tables_dirty = true;
+  e->pz_dirty = true;
   return IS3D_OK;
 }
 
@@ -1095,6 +1106,7 @@ extern "C" int is3d_set_species_classes(is3d_engine* e, int on) {
   if (!e) return IS3D_ERR_ARG;
   e->classes = on != 0;
   e->tables_dirty = true;
+  e->pz_dirty = true;
   return IS3D_OK;
 }
 
@@ -1127,6 +1139,7 @@ extern "C" int is3d_set_momentum_grid(is3d_engine* e, int npT, const double* pT,
   e->eta_w.assign(eta_weight ? eta_weight : pT, eta_weight ? eta_weight + std::max(neta, 0) : pT);
   e->have_grid = true;
   e->tables_dirty = true;
+  e->pz_dirty = true;
   return IS3D_OK;
 }
 
@@ -1591,6 +1604,8 @@ extern "C" int is3d_set_surface(is3d_engine* e, long n, const is3d_surface* s) {
     e->surf_cap = n;
   }
   e->ncell = n;
+  e->have_surf = true;
+  e->have_vort = false;
   e->win_lo = e->win_hi = -1;
   e->chain_q0 = e->chain_q1 = -1;
   if (n == 0) return IS3D_OK;
@@ -1610,6 +1625,8 @@ extern "C" int is3d_set_surface_device(is3d_engine* e, long n, const double* dev
   e->surf_cap = 0;
   e->d_surf = const_cast<double*>(dev_fields);
   e->ncell = n;
+  e->have_surf = true;
+  e->have_vort = false;
   e->win_lo = e->win_hi = -1;
   e->chain_q0 = e->chain_q1 = -1;
   return IS3D_OK;
@@ -1628,6 +1645,8 @@ extern "C" int is3d_internal_copy_surface(is3d_engine* e, long n, const double* 
     e->surf_cap = n;
   }
   e->ncell = n;
+  e->have_surf = true;
+  e->have_vort = false;
   e->win_lo = e->win_hi = -1;
   e->chain_q0 = e->chain_q1 = -1;
   for (int f = 0; f < NSURF && n > 0; f++)
@@ -2504,6 +2523,87 @@ extern "C" int is3d_get_cell_yields(const is3d_engine* e, double* dN_dy_cell) {
     const int so = e->order[s];
     for (long c = 0; c < n; c++) dN_dy_cell[(size_t)so * n + c] = pref * e->degen[so] * y[(size_t)e->scls[s] * n + c];
   }
+  return IS3D_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// spin polarization from thermal vorticity (mode 5; Polarization.cpp:25-263, kernels in polzn.hip)
+// ------------------------------------------------------------------------------------------
+extern "C" int is3d_set_vorticity(is3d_engine* e, long n, const is3d_vorticity* w) {
+  if (e && e->grp) return is3d::group_set_vorticity(e->grp, n, w);
+  if (!e) return IS3D_ERR_ARG;
+  if (!e->have_surf) return e->fail(IS3D_ERR_STATE, "is3d_set_vorticity: set the surface first");
+  if (!w || n != e->ncell) return e->fail(IS3D_ERR_ARG, "is3d_set_vorticity: the vorticity must have one entry per surface cell");
+  const double* f[6] = {w->wtx, w->wty, w->wtn, w->wxy, w->wxn, w->wyn};
+  for (int k = 0; k < 6; k++)
+    if (!f[k] && n > 0) return e->fail(IS3D_ERR_ARG, "is3d_set_vorticity: vorticity component missing");
+  HIPCHK(e, hipSetDevice(e->device));
+  if (!ensure(e->d_vort, e->vort_cap, 6L * n)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(vorticity) failed");
+  for (int k = 0; k < 6 && n > 0; k++)
+    HIPCHK(e, hipMemcpy(e->d_vort + (size_t)k * n, f[k], n * sizeof(double), hipMemcpyHostToDevice));
+  e->have_vort = true;
+  return IS3D_OK;
+}
+
+extern "C" long is3d_polarization_size(const is3d_engine* e) {
+  const long n = is3d_output_size(e);
+  return n < 0 ? n : 5 * n;
+}
+
+extern "C" int is3d_launch_polarization(is3d_engine* e, double T_avg, double* dev_out, void* stream) {
+  if (e && e->grp) return is3d::group_launch_polarization(e->grp, T_avg, dev_out, stream);
+  if (!e) return IS3D_ERR_ARG;
+  if (!e->have_params || !e->have_species || !e->have_grid)
+    return e->fail(IS3D_ERR_STATE, "polarization: params, species and momentum grid must be set");
+  if (!e->have_surf) return e->fail(IS3D_ERR_STATE, "polarization: no surface set");
+  if (!e->have_vort) return e->fail(IS3D_ERR_STATE, "polarization: no thermal vorticity set for this surface (is3d_set_vorticity)");
+  if (!(T_avg > 0.0)) return e->fail(IS3D_ERR_ARG, "polarization: T_avg must be positive");
+  if (!dev_out) return e->fail(IS3D_ERR_ARG, "null output buffer");
+  HIPCHK(e, hipSetDevice(e->device));
+  if (e->pz_dirty) {
+    const std::string msg = is3d::polzn::tables_build(e->pz, e->p.dimension, e->classes, e->mass, e->sign, e->pT, e->phi,
+                                                      e->y, e->eta, e->eta_w);
+    if (!msg.empty()) return e->fail(IS3D_ERR_ARG, "polarization: " + msg);
+    e->pz_dirty = false;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const long n = e->ncell;
+  const long wlo = e->win_hi >= 0 ? e->win_lo : 0, whi = e->win_hi >= 0 ? e->win_hi : n, nw = whi - wlo;
+  e->st = is3d_stats{};
+  e->st.cells = nw;
+  HIPCHK(e, hipMemsetAsync(e->d_err, 0, sizeof(int), st));
+  HIPCHK(e, hipMemsetAsync(e->d_cnt, 0, 8 * sizeof(unsigned long long), st));
+  HIPCHK(e, hipEventRecord(e->ev[0], st));
+  HIPCHK(e, hipEventRecord(e->ev[1], st));     // no prepass: k_polzn reads the surface itself
+  if (nw == 0) {
+    HIPCHK(e, hipMemsetAsync(dev_out, 0, e->pz.out_size() * sizeof(double), st));
+    HIPCHK(e, hipEventRecord(e->ev[2], st));
+  } else {
+    const is3d::polzn::Plan P = is3d::polzn::make_plan(e->pz, nw, e->max_splits, e->split_bytes, e->slab_bytes);
+    if (!P.ok) return e->fail(IS3D_ERR_ARG, "polarization: the phi / y / eta tables do not fit a workgroup's LDS tile");
+    if (!ensure(e->d_slab, e->slab_cap, P.nsplit * P.sstride)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(slabs) failed");
+    e->last_nchunk = 0;
+    e->last_nsplit = P.nsplit;
+    e->last_nslab = P.nsplit;
+    HIPCHK(e, is3d::polzn::enqueue(e->pz, P, e->d_surf, e->d_vort, n, wlo, whi, T_avg, e->d_slab, dev_out, st, e->ev[2]));
+  }
+  HIPCHK(e, hipEventRecord(e->ev[3], st));
+  e->launched = true;
+  return IS3D_OK;
+}
+
+extern "C" int is3d_calculate_polarization(is3d_engine* e, double T_avg, double* S_out) {
+  if (e && e->grp) return is3d::group_calculate_polarization(e->grp, T_avg, S_out);
+  if (!e || !S_out) return e ? e->fail(IS3D_ERR_ARG, "null output") : IS3D_ERR_ARG;
+  const long outsize = is3d_polarization_size(e);
+  if (outsize < 0) return e->fail(IS3D_ERR_STATE, "polarization: params, species and momentum grid must be set");
+  HIPCHK(e, hipSetDevice(e->device));
+  if (!ensure(e->d_out, e->out_cap, outsize)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(output) failed");
+  int rc = is3d_launch_polarization(e, T_avg, e->d_out, nullptr);
+  if (rc) return rc;
+  rc = is3d_finish(e);
+  if (rc) return rc;
+  HIPCHK(e, hipMemcpy(S_out, e->d_out, outsize * sizeof(double), hipMemcpyDeviceToHost));
   return IS3D_OK;
 }
 

@@ -48,6 +48,11 @@ long group_output_size(const Group* g);
 int group_evaluate_df_coefficients(Group* g, double T, double muB, double E, double P, double bulkPi, double* out15);
 int group_total_yield(Group* g, const double* plasma, double y_cut, double* n_total, double* densities);
 int group_get_jonah_table(const Group* g, double* l2, double* z, double* bp, double* bpmax);
+// spin polarization (mode 5): every shard gets the vorticity of its window, runs polzn.hip's kernels on it, and the
+// five arrays are summed like the spectra (group_launch's reduction)
+int group_set_vorticity(Group* g, long n, const is3d_vorticity* w);
+int group_launch_polarization(Group* g, double T_avg, double* dev_out, void* stream);
+int group_calculate_polarization(Group* g, double T_avg, double* S_out);
 }  // namespace is3d
 
 // engine.hip internals the group uses on its shard engines (not part of the public ABI)

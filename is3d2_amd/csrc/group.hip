@@ -390,11 +390,13 @@ static int launch_split_chains(Group* g, S stream_of) {
   return IS3D_OK;
 }
 
-int group_launch(Group* g, double* dev_out, void* stream) {
+// One launch of every shard plus the reduction of their outputs.  polzn: the shards run the spin polarization at
+// T_avg (five spectra-sized arrays) instead of the spectra.
+static int launch_shards(Group* g, double* dev_out, void* stream, bool polzn, double T_avg) {
   if (!dev_out) return g->fail(IS3D_ERR_ARG, "null output buffer");
   if (stale_split(g)) return g->fail(IS3D_ERR_STATE, kStaleSplit);
   const int K = (int)g->sh.size();
-  const long out_n = group_output_size(g);
+  const long out_n = (polzn ? 5 : 1) * group_output_size(g);
   if (out_n <= 0) return g->fail(IS3D_ERR_STATE, "species / grids / params not set");
   if ((int)g->buf.size() != K || g->buf_n < out_n) {
     for (int k = 1; k < (int)g->buf.size(); k++) if (g->buf[k]) { (void)hipSetDevice(g->dev[k]); (void)hipFree(g->buf[k]); }
@@ -416,8 +418,13 @@ int group_launch(Group* g, double* dev_out, void* stream) {
   if (hipEventRecord(g->ev0, g->cur0) != hipSuccess) return g->fail(IS3D_ERR_DEVICE, "hipEventRecord failed");
   auto stream_of = [&](int k) { return k ? g->st[k] : g->cur0; };
   const char* dc = std::getenv("IS3D_CHAIN_DIST");
-  g->dist_chain = g->full && K > 1 && !(dc && !std::strcmp(dc, "0"));
-  if (!g->dist_chain) {
+  g->dist_chain = !polzn && g->full && K > 1 && !(dc && !std::strcmp(dc, "0"));
+  if (polzn) {
+    for (int k = 0; k < K; k++) {
+      const int rc = is3d_launch_polarization(g->sh[k], T_avg, g->buf[k], k ? (void*)g->st[k] : stream);
+      if (rc) return g->shard_fail(k, rc);
+    }
+  } else if (!g->dist_chain) {
     for (int k = 0; k < K; k++) {
       const int rc = is3d_launch(g->sh[k], g->buf[k], k ? (void*)g->st[k] : stream);
       if (rc) return g->shard_fail(k, rc);
@@ -462,6 +469,27 @@ int group_launch(Group* g, double* dev_out, void* stream) {
   if (hipEventRecord(g->ev1, g->cur0) != hipSuccess) return g->fail(IS3D_ERR_DEVICE, "hipEventRecord failed");
   g->launched = true;
   return IS3D_OK;
+}
+
+int group_launch(Group* g, double* dev_out, void* stream) { return launch_shards(g, dev_out, stream, false, 0.0); }
+
+int group_launch_polarization(Group* g, double T_avg, double* dev_out, void* stream) {
+  return launch_shards(g, dev_out, stream, true, T_avg);
+}
+
+// every shard's window of the vorticity: the whole arrays where every shard holds the whole surface (PTMA
+// warm-start chains; its cell window then selects the cells), else cells [lo, hi) of the shard
+int group_set_vorticity(Group* g, long n, const is3d_vorticity* w) {
+  if (g->lo.size() != g->sh.size()) return g->fail(IS3D_ERR_STATE, "is3d_set_vorticity: set the surface first");
+  if (!w || n != g->ncell) return g->fail(IS3D_ERR_ARG, "is3d_set_vorticity: the vorticity must have one entry per surface cell");
+  if (n > 0 && (!w->wtx || !w->wty || !w->wtn || !w->wxy || !w->wxn || !w->wyn))
+    return g->fail(IS3D_ERR_ARG, "is3d_set_vorticity: vorticity component missing");
+  return each_parallel(g, [&](int k) -> int {
+    const long o = g->full ? 0 : g->lo[k], m = g->full ? n : g->hi[k] - g->lo[k];
+    auto at = [&](const double* f) { return f ? f + o : nullptr; };
+    const is3d_vorticity v{at(w->wtx), at(w->wty), at(w->wtn), at(w->wxy), at(w->wxn), at(w->wyn)};
+    return is3d_set_vorticity(g->sh[k], m, &v);
+  });
 }
 
 int group_finish(Group* g) {
@@ -517,6 +545,27 @@ int group_calculate_spectra(Group* g, double* dN_out) {
   (void)hipSetDevice(g->dev[0]);
   if (hipMemcpy(dN_out, g->d_out, n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
     return g->fail(IS3D_ERR_DEVICE, "spectra download failed");
+  return IS3D_OK;
+}
+
+int group_calculate_polarization(Group* g, double T_avg, double* S_out) {
+  if (!S_out) return g->fail(IS3D_ERR_ARG, "null output");
+  const long n = 5 * group_output_size(g);
+  if (n <= 0) return g->fail(IS3D_ERR_STATE, "species / grids / params not set");
+  (void)hipSetDevice(g->dev[0]);
+  if (g->out_n < n) {
+    if (g->d_out) (void)hipFree(g->d_out);
+    g->d_out = nullptr;
+    g->out_n = 0;
+    if (hipMalloc(&g->d_out, n * sizeof(double)) != hipSuccess) return g->fail(IS3D_ERR_DEVICE, "hipMalloc(output) failed");
+    g->out_n = n;
+  }
+  int rc = group_launch_polarization(g, T_avg, g->d_out, nullptr);
+  if (!rc) rc = group_finish(g);
+  if (rc) return rc;
+  (void)hipSetDevice(g->dev[0]);
+  if (hipMemcpy(S_out, g->d_out, n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+    return g->fail(IS3D_ERR_DEVICE, "polarization download failed");
   return IS3D_OK;
 }
 

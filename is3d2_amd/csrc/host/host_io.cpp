@@ -116,6 +116,7 @@ void Surface::resize(long n) {
   for (auto* v : {&tau, &x, &y, &eta, &dat, &dax, &day, &dan, &ux, &uy, &un, &E, &T, &P, &pixx, &pixy, &pixn, &piyy,
                   &piyn, &bulkPi, &muB, &nB, &Vx, &Vy, &Vn})
     v->assign(n, 0.0);
+  for (auto& v : w) v.clear();
 }
 
 static double round15(double v) {
@@ -169,6 +170,7 @@ std::string read_surface(const std::string& dir, int mode, int dimension, int in
   double d;
   auto rd = [&]() { double v = 0.0; f >> v; return v; };
   if (mode == 1 || mode == 5) {
+    if (mode == 5) for (auto& v : s.w) v.assign(n, 0.0);
     for (long i = 0; i < n; i++) {
       s.tau[i] = rd(); s.x[i] = rd(); s.y[i] = rd(); s.eta[i] = rd();
       s.dat[i] = rd(); s.dax[i] = rd(); s.day[i] = rd(); s.dan[i] = rd();
@@ -188,7 +190,7 @@ std::string read_surface(const std::string& dir, int mode, int dimension, int in
         nB = rd(); s.nB[i] = nB;
         s.Vx[i] = rd(); s.Vy[i] = rd(); s.Vn[i] = rd();
       }
-      if (mode == 5) for (int k = 0; k < 6; k++) rd();   // thermal vorticity (polarization, out of scope)
+      if (mode == 5) for (int k = 0; k < 6; k++) s.w[k][i] = rd();   // thermal vorticity, dimensionless (:298-306)
       if (dimension == 2) s.eta[i] = 0;
       const double tau = s.tau[i];
       const double ut = std::sqrt(1. + s.ux[i] * s.ux[i] + s.uy[i] * s.uy[i] + tau * tau * s.un[i] * s.un[i]);
@@ -390,6 +392,35 @@ static void mkdirs(const std::string& path) {
     if (path[i] == '/' && cur.size() > 1) mkdir(cur.c_str(), 0755);
   }
   mkdir(path.c_str(), 0755);
+}
+
+std::string write_polzn_files(const std::string& dir, const PolznView& v) {
+  const std::string out = join(dir, "results");
+  mkdirs(out);
+  const long npT = v.npT, nphi = v.nphi, ny = v.ny;
+  const long per = (long)v.npart * npT * nphi * ny;
+  const double* norm = v.S + 4 * per;
+  const char* names[4] = {"St.dat", "Sx.dat", "Sy.dat", "Sn.dat"};
+  for (int c = 0; c < 4; c++) {
+    const std::string path = out + "/" + names[c];
+    FILE* f = std::fopen(path.c_str(), "w");
+    if (!f) return "cannot write " + path;
+    const double* S = v.S + c * per;
+    for (long ipart = 0; ipart < v.npart; ipart++)
+      for (long iy = 0; iy < ny; iy++) {
+        const double y = v.dimension == 3 ? v.y->get(1, iy + 1) : 0.0;
+        for (long iphip = 0; iphip < nphi; iphip++) {
+          const double phip = v.phi->get(1, iphip + 1);
+          for (long ipT = 0; ipT < npT; ipT++) {
+            const long i = iy + ny * (iphip + nphi * (ipT + npT * ipart));
+            std::fprintf(f, "%.8e\t%.8e\t%.8e\t%.8e\n", y, phip, v.pT->get(1, ipT + 1), S[i] / norm[i]);
+          }
+          std::fprintf(f, "\n");
+        }
+      }
+    std::fclose(f);
+  }
+  return "";
 }
 
 std::string write_spectra_files(const std::string& dir, const SpectraView& v) {

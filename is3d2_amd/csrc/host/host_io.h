@@ -38,6 +38,9 @@ bool load_table(const std::string& path, Table& t);
 struct Surface {
   std::vector<double> tau, x, y, eta, dat, dax, day, dan, ux, uy, un, E, T, P, pixx, pixy, pixn, piyy, piyn, bulkPi,
       muB, nB, Vx, Vy, Vn;
+  // mode 5 only: thermal vorticity wbar^{tx ty tn xy xn yn}, no unit conversion (readindata.cpp:298-306); else empty
+  std::vector<double> w[6];
+  bool has_vorticity() const { return size() > 0 && (long)w[0].size() == size(); }
   long size() const { return (long)tau.size(); }
   void resize(long n);
 };
@@ -80,6 +83,18 @@ struct SpectraView {
   const std::vector<long>* mcid;
 };
 std::string write_spectra_files(const std::string& dir, const SpectraView& v);
+
+// write_polzn_vector_toFile (EmissionFunction.cpp:561-609): <dir>/results/St.dat, Sx.dat, Sy.dat, Sn.dat with rows
+// "y \t phi \t pT \t S_c / Snorm" (scientific, 8 digits), species -> y -> phi -> pT, a blank line after each pT run.
+// Departure from the reference: each row holds the value its labels name (the reference reads index
+// iy + ny (iphi + nphi (ipT + npT ipart)) from arrays filled at ipart + npart (ipT + npT (iphi + nphi iy)), and in
+// 2+1D loops y_tab_length rows over one filled y slot); 2+1D writes one y = 0 block.
+struct PolznView {
+  const double* S;                  // [5][species][pT][phi][y]: S_t S_x S_y S_n Snorm
+  int npart, npT, nphi, ny, dimension;
+  const Table *pT, *phi, *y;
+};
+std::string write_polzn_files(const std::string& dir, const PolznView& v);
 
 // operation = 0 writers (SpacetimeDistribution.cpp:138-145, 407-440): dN_taudtaudy_<mcid>.dat,
 // dN_2pirdrdy_<mcid>.dat, dN_dphidy_<mcid>.dat under <dir>/results/continuous/, opened in append mode,

@@ -95,7 +95,12 @@ static is3d_spacetime_bins spacetime_bins(const ParameterReader& p) {
 // all-reduce over distinct GPUs), replacing the reference's OpenMP fan-out and thread reduction
 // (MomentumSpectra.cpp:98-107, 383-411).
 void EmissionFunctionArray::run_sharded(const RunOptions& opt, int operation) {
-  const is3d_params prm = engine_params(p_, operation, dimension_);
+  // operation < 0: the polarization alone, on an engine of its own, so that the caller can write the operation's
+  // files before it runs (a polarization error then costs none of them)
+  const bool polzn_only = operation < 0;
+  if (polzn_only && !((int)p_.get("mode") == 5 && surf_.has_vorticity()))
+    throw EngineError(IS3D_ERR_STATE, "polarization needs a mode = 5 surface (thermal vorticity columns)");
+  const is3d_params prm = engine_params(p_, polzn_only ? 1 : operation, dimension_);
   const is3d_spacetime_bins bins = spacetime_bins(p_);
   const int ndev = opt.devices.empty() ? std::max(1, opt.num_devices) : (int)opt.devices.size();
   std::vector<int> devs(ndev);
@@ -111,11 +116,13 @@ void EmissionFunctionArray::run_sharded(const RunOptions& opt, int operation) {
   try {
     set_or_throw(e, is3d_set_params(e, &prm));
     set_or_throw(e, is3d_set_species(e, np, mass_.data(), sign_.data(), degen_.data(), baryon_.data()));
-    set_or_throw(e, is3d_set_pdg(e, (int)pdg_mass_.size(), pdg_mass_.data(), pdg_sign_.data(), pdg_degen_.data(), pdg_baryon_.data()));
     set_or_throw(e, is3d_set_momentum_grid(e, (int)pTv.size(), pTv.data(), (int)phiv.size(), phiv.data(), (int)yv.size(),
                                            yv.data(), (int)etav.size(), etav.data(), etaw.data()));
-    set_or_throw(e, is3d_set_gauss_laguerre(e, galpha_, gpts_, gr_.data(), gw_.data()));
-    set_or_throw(e, is3d_set_df_tables(e, df_.nT, df_.nmuB, df_.T.data(), df_.muB.data(), df_.tab.data(), plasma_.T));
+    if (!polzn_only) {
+      set_or_throw(e, is3d_set_pdg(e, (int)pdg_mass_.size(), pdg_mass_.data(), pdg_sign_.data(), pdg_degen_.data(), pdg_baryon_.data()));
+      set_or_throw(e, is3d_set_gauss_laguerre(e, galpha_, gpts_, gr_.data(), gw_.data()));
+      set_or_throw(e, is3d_set_df_tables(e, df_.nT, df_.nmuB, df_.T.data(), df_.muB.data(), df_.tab.data(), plasma_.T));
+    }
     auto fp = [&](const std::vector<double>& v) { return v.empty() ? nullptr : v.data(); };
     is3d_surface s{fp(surf_.tau), fp(surf_.x), fp(surf_.y), fp(surf_.eta), fp(surf_.dat), fp(surf_.dax), fp(surf_.day),
                    fp(surf_.dan), fp(surf_.ux), fp(surf_.uy), fp(surf_.un), fp(surf_.E), fp(surf_.T), fp(surf_.P),
@@ -128,7 +135,7 @@ void EmissionFunctionArray::run_sharded(const RunOptions& opt, int operation) {
     } else if (operation == 2) {
       const double plasma[5] = {plasma_.T, plasma_.E, plasma_.P, plasma_.muB, plasma_.nB};
       set_or_throw(e, is3d_total_yield(e, plasma, p_.get("y_cut", 0.5), &ntotal_, nullptr));
-    } else {
+    } else if (operation == 0) {
       set_or_throw(e, is3d_set_momentum_weights(e, pTw.data(), phiw.data()));
       set_or_throw(e, is3d_set_spacetime_bins(e, &bins));
       bins_ = bins;
@@ -136,6 +143,13 @@ void EmissionFunctionArray::run_sharded(const RunOptions& opt, int operation) {
       dNr_.assign((size_t)np * bins.r_bins, 0.0);
       dNphi_.assign((size_t)np * bins.phip_bins, 0.0);
       set_or_throw(e, is3d_calculate_dN_dX(e, dNtau_.data(), dNr_.data(), dNphi_.data()));
+    }
+    if (polzn_only) {   // EmissionFunction.cpp:1305-1310: T = QGP->temperature
+      const is3d_vorticity w{surf_.w[0].data(), surf_.w[1].data(), surf_.w[2].data(), surf_.w[3].data(),
+                             surf_.w[4].data(), surf_.w[5].data()};
+      set_or_throw(e, is3d_set_vorticity(e, n, &w));
+      S_.assign(is3d_polarization_size(e), 0.0);
+      set_or_throw(e, is3d_calculate_polarization(e, plasma_.T, S_.data()));
     }
   } catch (...) {
     is3d_destroy(e);
@@ -152,6 +166,15 @@ void EmissionFunctionArray::calculate_dN_dX(const RunOptions& opt) { run_sharded
 double EmissionFunctionArray::estimate_total_yield(const RunOptions& opt) {
   run_sharded(opt, 2);
   return ntotal_;
+}
+
+void EmissionFunctionArray::calculate_polarization(const RunOptions& opt) { run_sharded(opt, -1); }
+
+void EmissionFunctionArray::write_polzn_files(const std::string& dir) const {
+  const int ny = (dimension_ == 3) ? (int)y_.rows() : 1;
+  PolznView v{S_.data(), (int)mass_.size(), (int)pT_.rows(), (int)phi_.rows(), ny, dimension_, &pT_, &phi_, &y_};
+  const std::string err = host::write_polzn_files(dir, v);
+  if (!err.empty()) throw std::runtime_error(err);
 }
 
 void EmissionFunctionArray::write_spacetime_files(const std::string& dir) const {
@@ -214,9 +237,11 @@ void IS3D::run_particlization(int fo_from_file, const RunOptions& opt) {
   check(err.empty(), err);
   Table chosen, pT, phi, y, eta;
   check(load_table(path_in(dir_, "PDG/chosen_particles.dat"), chosen), "cannot read PDG/chosen_particles.dat");
-  DfTablesData df;
-  err = read_df_tables(dir_, hrg, df);
-  check(err.empty(), err);
+  DfTablesData df;          // the polarization alone uses neither the df tables nor the Gauss-Laguerre roots
+  if (!opt.polarization_only) {
+    err = read_df_tables(dir_, hrg, df);
+    check(err.empty(), err);
+  }
   check(load_table(path_in(dir_, "tables/momentum/pT_table.dat"), pT), "cannot read tables/momentum/pT_table.dat");
   check(load_table(path_in(dir_, "tables/momentum/phi_table.dat"), phi), "cannot read tables/momentum/phi_table.dat");
   check(load_table(path_in(dir_, "tables/momentum/y_table.dat"), y), "cannot read tables/momentum/y_table.dat");
@@ -224,9 +249,19 @@ void IS3D::run_particlization(int fo_from_file, const RunOptions& opt) {
         "cannot read tables/spacetime_rapidity/eta_table.dat");
   int galpha = 0, gpts = 0;
   std::vector<double> gr, gw;
-  err = read_gauss_laguerre(path_in(dir_, "tables/gauss/gla_roots_weights.txt"), galpha, gpts, gr, gw);
-  check(err.empty(), err);
+  if (!opt.polarization_only) {
+    err = read_gauss_laguerre(path_in(dir_, "tables/gauss/gla_roots_weights.txt"), galpha, gpts, gr, gw);
+    check(err.empty(), err);
+  }
   EmissionFunctionArray efa(prm, chosen, pT, phi, y, eta, parts, *surf, df, avg, gr, gw, galpha, gpts);
+  S_.clear();
+  if (opt.polarization_only) {
+    efa.calculate_polarization(opt);
+    if (opt.write_files) efa.write_polzn_files(dir_);
+    S_ = efa.polarization();
+    dN_.clear();
+    return;
+  }
   if (operation == 2) {        // EmissionFunction.cpp:1235-1249: the oversampling estimate
     nevents_ = 1;
     if ((int)prm.get("oversample", 0.0)) {
@@ -238,9 +273,7 @@ void IS3D::run_particlization(int fo_from_file, const RunOptions& opt) {
       std::printf("\nSampling 1 particlization event...\n\n");
     }
     dN_.clear();
-    return;
-  }
-  if (operation == 1) {
+  } else if (operation == 1) {
     efa.calculate_spectra(opt);
     if (opt.write_files) efa.write_files(dir_);
     if (!opt.quiet) std::printf("\nSpectra calculation took %g seconds\n\n", efa.seconds());
@@ -257,6 +290,13 @@ void IS3D::run_particlization(int fo_from_file, const RunOptions& opt) {
       dN_.insert(dN_.end(), efa.dN_2pirdrdy().begin() + (long)k * b.r_bins, efa.dN_2pirdrdy().begin() + (long)(k + 1) * b.r_bins);
       dN_.insert(dN_.end(), efa.dN_dphidy().begin() + (long)k * b.phip_bins, efa.dN_dphidy().begin() + (long)(k + 1) * b.phip_bins);
     }
+  }
+  // mode = 5 (EmissionFunction.cpp:1305-1310): after the chosen operation, whichever it is, and after its files
+  if (mode == 5 && surf->has_vorticity()) {
+    if (!opt.quiet) std::printf("\nComputing spin polarization...\n");
+    efa.calculate_polarization(opt);
+    if (opt.write_files) efa.write_polzn_files(dir_);
+    S_ = efa.polarization();
   }
 }
 
@@ -325,6 +365,41 @@ extern "C" int is3d_host_total_yield(const char* workdir, int device, int num_de
     put_err(err, errlen, ex.what());
     return IS3D_ERR_ARG;
   }
+}
+
+extern "C" int is3d_host_polarization(const char* workdir, const int* devices, int num_devices, double* S_out,
+                                      long out_capacity, char* err, int errlen) {
+  if (!devices || num_devices <= 0) { put_err(err, errlen, "empty device list"); return IS3D_ERR_ARG; }
+  try {
+    IS3D run(workdir ? workdir : ".");
+    RunOptions opt;
+    opt.devices.assign(devices, devices + num_devices);
+    opt.quiet = true;
+    opt.polarization_only = true;
+    run.run_particlization(1, opt);
+    const auto& S = run.polarization();
+    if (S_out) {
+      if ((long)S.size() > out_capacity) { put_err(err, errlen, "output buffer too small"); return IS3D_ERR_ARG; }
+      std::copy(S.begin(), S.end(), S_out);
+    }
+    return IS3D_OK;
+  } catch (const EngineError& ex) {
+    put_err(err, errlen, ex.what());
+    return ex.code;
+  } catch (const std::exception& ex) {
+    put_err(err, errlen, ex.what());
+    return IS3D_ERR_ARG;
+  }
+}
+
+extern "C" long is3d_host_read_vorticity(const char* workdir, int dimension, int include_baryon, double* w6) {
+  Surface s;
+  Averages a{};
+  if (!read_surface(workdir ? workdir : ".", 5, dimension, include_baryon, s, a, false).empty()) return -1;
+  const long n = s.size();
+  if (w6)
+    for (int k = 0; k < 6; k++) std::copy(s.w[k].begin(), s.w[k].end(), w6 + (size_t)k * n);
+  return n;
 }
 
 extern "C" long is3d_host_read_surface(const char* workdir, int mode, int dimension, int include_baryon, double* fields,

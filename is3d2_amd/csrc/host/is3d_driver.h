@@ -34,6 +34,7 @@ struct RunOptions {
   std::vector<int> devices;  // if not empty: shard k runs on devices[k] (an index may repeat)
   bool write_files = true;
   bool quiet = false;
+  bool polarization_only = false;   // mode = 5: run only calculate_spin_polzn and its writer, not the operation
 };
 
 // EmissionFunctionArray(paraRdr, chosen, pT, phi, y, eta, particles, Nparticles, surface, FO_length, df tables)
@@ -57,6 +58,15 @@ class EmissionFunctionArray {
   const std::vector<long>& mcid() const { return mcid_; }
   // operation = 2 oversampling estimate (ParticleSampler.cpp:447-636): the reference's Ntotal
   double estimate_total_yield(const RunOptions& opt);
+  // mode = 5 (EmissionFunction.cpp:1305-1310): calculate_spin_polzn at T = the Plasma average temperature, on an
+  // engine of its own that holds only params, species, grid, surface and vorticity.  IS3D::run_particlization calls
+  // it after the chosen operation (0, 1 or 2) and after that operation's files are written.
+  // polarization() = the raw sums [5][species][pT][phi][y] (S_t S_x S_y S_n Snorm), write_polzn_files the four
+  // results/S*.dat (S_c / Snorm)
+  void calculate_polarization(const RunOptions& opt);
+  bool has_polarization() const { return !S_.empty(); }
+  const std::vector<double>& polarization() const { return S_; }
+  void write_polzn_files(const std::string& dir) const;
   double seconds() const { return seconds_; }
 
  private:
@@ -73,10 +83,12 @@ class EmissionFunctionArray {
   std::vector<long> mcid_;
   std::vector<double> dN_;
   std::vector<double> dNtau_, dNr_, dNphi_;
+  std::vector<double> S_;
   is3d_spacetime_bins bins_{};
   double seconds_ = 0.0;
   double ntotal_ = 0.0;
-  void run_sharded(const RunOptions& opt, int operation);   // operation 2: the yield estimate
+  // operation 2: the yield estimate; -1: the polarization alone (an engine without PDG, Gauss-Laguerre and df tables)
+  void run_sharded(const RunOptions& opt, int operation);
 };
 
 class IS3D {
@@ -94,6 +106,8 @@ class IS3D {
   // spectra (operation 1) or, per species, [dN_taudtaudy | dN_2pirdrdy | dN_dphidy] bins (operation 0)
   void run_particlization(int fo_from_file, const RunOptions& opt = RunOptions());
   const std::vector<double>& spectra() const { return dN_; }
+  // mode = 5: the raw polarization sums [5][species][pT][phi][y] of the run (empty otherwise)
+  const std::vector<double>& polarization() const { return S_; }
   // operation = 2: Ntotal and Nevents = min(ceil(min_num_hadrons / Ntotal), max_num_samples) if
   // oversample, else 1 (EmissionFunction.cpp:1237-1249); the sampling itself is not on this path
   double total_yield() const { return ntotal_; }
@@ -105,6 +119,7 @@ class IS3D {
   long nevents_ = 0;
   Surface mem_;
   std::vector<double> dN_;
+  std::vector<double> S_;
 };
 
 }  // namespace host

@@ -117,6 +117,7 @@ class Engine:
         a = [_arr(x) for x in (pT, phi, y, eta, eta_w)]
         self._chk(self.lib.is3d_set_momentum_grid(self._e, len(a[0]), _dp(a[0]), len(a[1]), _dp(a[1]),
                                                   len(a[2]), _dp(a[2]), len(a[3]), _dp(a[3]), _dp(a[4])))
+        self.npT, self.nphi = len(a[0]), len(a[1])
 
     def set_momentum_weights(self, pT_w, phi_w):
         a, b = _arr(pT_w), _arr(phi_w)
@@ -182,6 +183,35 @@ class Engine:
         out = np.zeros((self.npart, self.ncell))
         self._chk(self.lib.is3d_get_cell_yields(self._e, _dp(out)))
         return out
+
+    # --- mode 5: spin polarization from thermal vorticity (Polarization.cpp:25-263) ------------------------
+    def set_vorticity(self, w):
+        """Thermal vorticity of the surface set last: an array (6, n) in the order wtx wty wtn wxy wxn wyn (the
+        last six columns of a mode-5 surface.dat) or a dict with those keys.  A new surface clears it."""
+        if isinstance(w, dict):
+            cols = [_arr(w[k]) for k in _lib.VORTICITY_FIELDS]
+        else:
+            w = _arr(w)
+            if w.ndim != 2 or w.shape[0] != 6:
+                raise ValueError("vorticity must have shape (6, n)")
+            cols = [_arr(w[k]) for k in range(6)]
+        v = _lib.Vorticity(*[_dp(c) for c in cols])
+        self._chk(self.lib.is3d_set_vorticity(self._e, len(cols[0]), C.byref(v)))
+
+    def calculate_polarization(self, T_avg):
+        """Raw cell sums (S_t, S_x, S_y, S_n, Snorm)[species][pT][phi][y] at T_avg = Plasma::temperature; the
+        reference's results/S*.dat hold S_c / Snorm.  Returns an array (5, npart, npT, nphi, ny)."""
+        n = self.lib.is3d_polarization_size(self._e)
+        if n < 0:
+            raise IS3DError(_lib.IS3D_ERR_STATE, "params / species / momentum grid not set")
+        out = np.zeros(n, dtype=np.float64)
+        self._chk(self.lib.is3d_calculate_polarization(self._e, float(T_avg), _dp(out)))
+        return out.reshape(5, self.npart, self.npT, self.nphi, -1)
+
+    def launch_polarization(self, T_avg, dev_out_ptr, stream_ptr=None):
+        """Resident form: writes 5 x output_size doubles into the device buffer; finish() synchronises."""
+        self._chk(self.lib.is3d_launch_polarization(self._e, float(T_avg), C.c_void_p(dev_out_ptr),
+                                                    C.c_void_p(stream_ptr or 0)))
 
     def launch(self, dev_out_ptr, stream_ptr=None):
         self._chk(self.lib.is3d_launch(self._e, C.c_void_p(dev_out_ptr), C.c_void_p(stream_ptr or 0)))
@@ -304,6 +334,8 @@ def build_engine(spec, surf, T_avg=None, device=0, devices=None, species_classes
     e.set_df_tables(*spec["df"], T_avg)
     if surf is not None:
         e.set_surface(surf)
+        if all(surf.get(k) is not None for k in _lib.VORTICITY_FIELDS):   # mode 5: thermal vorticity
+            e.set_vorticity({k: surf[k] for k in _lib.VORTICITY_FIELDS})
     return e
 
 

@@ -24,6 +24,9 @@ def load():
         lib.is3d_host_read_pdg.argtypes = [C.c_char_p, C.c_int, C.c_int, PL, PD, PI, PI, PI]
         lib.is3d_host_param.argtypes = [C.c_char_p, C.c_char_p, PD]
         lib.is3d_host_total_yield.argtypes = [C.c_char_p, C.c_int, C.c_int, PD, PL, C.c_char_p, C.c_int]
+        lib.is3d_host_read_vorticity.restype = C.c_long
+        lib.is3d_host_read_vorticity.argtypes = [C.c_char_p, C.c_int, C.c_int, PD]
+        lib.is3d_host_polarization.argtypes = [C.c_char_p, PI, C.c_int, PD, C.c_long, C.c_char_p, C.c_int]
         _lib = lib
     return _lib
 
@@ -38,6 +41,17 @@ def read_surface(workdir, mode, dimension, include_baryon):
     lib.is3d_host_read_surface(workdir.encode(), mode, dimension, include_baryon,
                                f.ctypes.data_as(C.POINTER(C.c_double)), avg.ctypes.data_as(C.POINTER(C.c_double)))
     return f.reshape(25, n), avg
+
+
+def read_vorticity(workdir, dimension, include_baryon):
+    """The six thermal-vorticity columns (wtx wty wtn wxy wxn wyn) of a mode-5 input/surface.dat, shape (6, n)."""
+    lib = load()
+    n = lib.is3d_host_read_vorticity(workdir.encode(), dimension, include_baryon, None)
+    if n < 0:
+        raise RuntimeError("surface read failed")
+    w = np.zeros(6 * n)
+    lib.is3d_host_read_vorticity(workdir.encode(), dimension, include_baryon, w.ctypes.data_as(C.POINTER(C.c_double)))
+    return w.reshape(6, n)
 
 
 def read_pdg(workdir, hrg_eos):
@@ -86,6 +100,20 @@ def run_particlization_devices(workdir, out_size, devices):
     dv = np.ascontiguousarray(devices, dtype=np.int32)
     rc = lib.is3d_host_run_particlization_devices(workdir.encode(), dv.ctypes.data_as(C.POINTER(C.c_int)), len(dv),
                                                   out.ctypes.data_as(C.POINTER(C.c_double)), out_size, err, 512)
+    if rc:
+        raise HostError(rc, err.value.decode())
+    return out
+
+
+def polarization(workdir, out_size, devices=(0,)):
+    """mode = 5 run directory: calculate_spin_polzn alone (Polarization.cpp:25-263).  Writes results/S{t,x,y,n}.dat
+    and returns the raw sums (S_t, S_x, S_y, S_n, Snorm), flat [5][species][pT][phi][y]; out_size = 5 x spectra size."""
+    lib = load()
+    out = np.zeros(out_size)
+    err = C.create_string_buffer(512)
+    dv = np.ascontiguousarray(devices, dtype=np.int32)
+    rc = lib.is3d_host_polarization(workdir.encode(), dv.ctypes.data_as(C.POINTER(C.c_int)), len(dv),
+                                    out.ctypes.data_as(C.POINTER(C.c_double)), out_size, err, 512)
     if rc:
         raise HostError(rc, err.value.decode())
     return out

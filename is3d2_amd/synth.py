@@ -74,10 +74,16 @@ def surface(n, seed=7, dimension=2, baryon=False, full3d=False):
     return {k: np.ascontiguousarray(s[k], dtype=np.float64) for k in FIELDS}
 
 
+def vorticity(n, seed):
+    """Thermal vorticity wbar^{tx ty tn xy xn yn} of n cells, shape (6, n): exactly the draw
+    write_mode1(..., vorticity_seed=seed) writes (dimensionless, no unit conversion on the way back)."""
+    return np.random.default_rng(seed).normal(0.0, 0.05, (6, n))
+
+
 def write_mode1(path, surf, include_baryon=False, vorticity_seed=None):
     """input/surface.dat in the CPU-VH format (readindata.cpp:179-202): E, T, P, pi, Pi and muB
     stored in fm units (divided by hbarc), %.17g.  vorticity_seed: mode 5 -- six thermal-vorticity
-    columns wbar^{tx ty tn xy xn yn} after the rest (readindata.cpp:298-306; read, not used by the spectra)."""
+    columns wbar^{tx ty tn xy xn yn} after the rest (readindata.cpp:298-306; the spin polarization's input)."""
     cols = ["tau", "x", "y", "eta", "dat", "dax", "day", "dan", "ux", "uy", "un", "E", "T", "P",
             "pixx", "pixy", "pixn", "piyy", "piyn", "bulkPi"]
     if include_baryon:
@@ -87,7 +93,7 @@ def write_mode1(path, surf, include_baryon=False, vorticity_seed=None):
         v = np.asarray(surf[k], dtype=np.float64)
         arr.append(v / HBARC if k in _HBARC_FIELDS else v)
     if vorticity_seed is not None:
-        w = np.random.default_rng(vorticity_seed).normal(0.0, 0.05, (6, len(surf["tau"])))
+        w = vorticity(len(surf["tau"]), vorticity_seed)
         arr.extend(list(w))
     a = np.stack(arr, axis=1)
     with open(path, "w") as f:
