@@ -150,8 +150,9 @@ int is3d_set_species(is3d_engine *e, int n, const double *mass, const double *si
  * renormalisation (MomentumSpectra.cpp:800-808) -- while the degeneracy multiplies the result
  * (MomentumSpectra.cpp:365).  With classes on, chosen species with identical keys are integrated once and the
  * reduction writes every member (prefactor x its degeneracy x the shared cell sum): the spectra are
- * bit-identical to integrating each species separately (on = 0) when both take the same launch plan (at the
- * BASELINE sizes), otherwise equal to rounding (the class count can change the cell-split grouping).
+ * equal to rounding (< 1e-9 relative, tests/test_gpu_classes.py) to integrating each species separately (on = 0):
+ * the two launches group different lanes into their wavefronts and can pick other cell splits, and they are
+ * bit-identical only when the per-wavefront Boltzmann-tail decisions coincide as well.
  * is3d_species_integrated returns the number of species the kernels integrate (SMASH 444 -> 193), or minus an
  * IS3D_ERR_* code when the tables cannot be finalised (is3d_last_error says why). */
 int is3d_set_species_classes(is3d_engine *e, int on);

@@ -77,56 +77,20 @@ IS3D_HD double exp_poly(const ExpCoef& E, double x) {
   return ldexp(p, (int)(unsigned)__builtin_bit_cast(unsigned long long, t));
 }
 
-// As exp_poly with a one-FMA reduction r = x - k ln2 (k ln2 exact inside the FMA; the error
-// |k| |ln2 - ln2_double| <= |k| 2.3e-17 is a third of the rounding error |x| 2^-53 >= |k| 7.7e-17
-// that any double argument x already carries, so the result's accuracy relative to the exact
-// exp of the exact argument is unchanged).  Used per point on the modified-momentum path.
-IS3D_HD double exp_poly1(const ExpCoef& E, double x) {
-  const double t = fma(x, E.l2e, E.shift);
-  const double k = t - E.shift;
-  const double r = fma(-k, E.ln2, x);
-  double p = E.c[0];
-  for (int i = 1; i < 10; i++) p = fma(p, r, E.c[i]);
-  p = fma(p, r, 1.0);
-  p = fma(p, r, 1.0);
-  return ldexp(p, (int)(unsigned)__builtin_bit_cast(unsigned long long, t));
-}
-
 IS3D_HD double exp_dom690(double x) { return exp_poly(exp_coef(), x); }
 
 // Table-driven exp for the per-point exponentials of the modified-momentum path, taking
-// xN = x N/ln2 (the caller folds N/ln2 into its coefficients; N = kExpTabN = 256 by default, 64 as
-// the alternative build): K = rint(xN) from the low word of xN + 1.5 2^52, rs = xN - K (exact),
+// xN = x N/ln2 (the caller folds N/ln2 into its coefficients; N = kExpTabN = 256): K = rint(xN) from the
+// low word of xN + 1.5 2^52, rs = xN - K (exact),
 // e^x = 2^(K / N) 2^((K mod N)/N) e^(c rs) with c = ln2/N, e^(c rs) - 1 = rs (a1 + rs (a2 + ...))
-// (Taylor through degree 4 for N = 256, 5 for N = 64: |c rs| <= ln2/(2N) leaves < 4e-17 truncation),
+// (Taylor through degree 4: |c rs| <= ln2/(2N) = ln2/512 leaves 3.8e-17 truncation),
 // and T = 2^((K mod N)/N) correctly rounded from an N-entry table the kernels keep in LDS:
-// 8 FP64 + 3 INT32 ops (N = 256) instead of exp_poly1's 15 FP64, ~1 ulp.  The error of xN itself
+// 8 FP64 + 3 INT32 ops instead of exp_poly's 15 FP64, ~1 ulp.  The error of xN itself
 // (~|x| 2e-16 absolute in x) is the same order as the rounding of the exponent argument that the
 // reference's own exp(E/T - chem) carries.  Valid for |xN| < 2^50; underflow / overflow via ldexp.
-// 2^(j/64), j = 0..63 (tools/gen_exp2_table.py)
-static constexpr double kExp2Tab64[64] = {
-    1.0, 1.0108892860517005, 1.0218971486541166, 1.0330248790212284,
-    1.0442737824274138, 1.0556451783605572, 1.0671404006768237, 1.0787607977571199,
-    1.0905077326652577, 1.102382583307841, 1.1143867425958924, 1.1265216186082418,
-    1.1387886347566916, 1.1511892299529827, 1.1637248587775775, 1.1763969916502812,
-    1.189207115002721, 1.202156731452703, 1.215247359980469, 1.22848053610687,
-    1.241857812073484, 1.255380757024691, 1.2690509571917332, 1.2828700160787783,
-    1.2968395546510096, 1.3109612115247644, 1.3252366431597413, 1.339667524053303,
-    1.3542555469368927, 1.3690024229745905, 1.383909881963832, 1.3989796725383112,
-    1.4142135623730951, 1.42961333839197, 1.4451808069770467, 1.460917794180647,
-    1.4768261459394993, 1.4929077282912648, 1.5091644275934228, 1.5255981507445384,
-    1.5422108254079407, 1.559004400237837, 1.5759808451078865, 1.593142151342267,
-    1.6104903319492543, 1.6280274218573478, 1.645755478153965, 1.6636765803267364,
-    1.681792830507429, 1.7001063537185235, 1.718619298122478, 1.7373338352737062,
-    1.7562521603732995, 1.7753764925265212, 1.7947090750031072, 1.8142521755003989,
-    1.8340080864093424, 1.8539791250833855, 1.8741676341103, 1.8945759815869656,
-    1.9152065613971474, 1.9360617934922943, 1.9571441241754002, 1.978456026387951,
-};
-// a_k = (ln2/64)^k / k!, k = 1..5
-static constexpr double kExpTabA[5] = {0.010830424696249145, 5.86490495505617e-05, 2.1173137155464776e-07, 5.732851688640402e-10, 1.2417843701716925e-12};
-static constexpr double kInvLn2x64 = 92.33248261689366;   // 64 / ln2
-// 2^(j/256), j = 0..255 (tools/gen_exp2_table.py 256)
-static constexpr double kExp2Tab256[256] = {
+static constexpr int kExpTabBits = 8, kExpTabN = 1 << kExpTabBits, kExpTabDeg = 4;
+// 2^(j/256), j = 0..255, correctly rounded
+static constexpr double kExp2Tab[kExpTabN] = {
     1.0, 1.0027112750502025, 1.0054299011128027, 1.0081558981184175,
     1.0108892860517005, 1.0136300849514894, 1.016378314910953, 1.019133996077738,
     1.0218971486541166, 1.0246677928971357, 1.0274459491187637, 1.030231637686041,
@@ -193,65 +157,15 @@ static constexpr double kExp2Tab256[256] = {
     1.978456026387951, 1.9838201648502194, 1.9891988469672663, 1.9945921121709402,
 };
 // a_k = (ln2/256)^k / k!, k = 1..4
-static constexpr double kExpTabA256[4] = {0.0027076061740622863, 3.6655655969101062e-06, 3.3083026805413713e-09, 2.239395190875157e-12};
-static constexpr double kInvLn2x256 = 369.3299304675746;   // 256 / ln2
+static constexpr double kExpTabCoefs[kExpTabDeg] = {0.0027076061740622863, 3.6655655969101062e-06, 3.3083026805413713e-09, 2.239395190875157e-12};
+static constexpr double kInvLn2xN = 369.3299304675746;   // 256 / ln2
 
-// IS3D_EXP_TAB_BITS = 8 (default): 256-entry table, |c rs| <= ln2/512, degree-4 Taylor (truncation
-// 3.8e-17): one FMA fewer per exp than the 64-entry table's degree 5; 6: the 64-entry table
-#ifndef IS3D_EXP_TAB_BITS
-#define IS3D_EXP_TAB_BITS 8
-#endif
-#if IS3D_EXP_TAB_BITS == 8
-static constexpr int kExpTabN = 256, kExpTabDeg = 4;
-#define kExp2Tab kExp2Tab256
-#define kExpTabCoefs kExpTabA256
-static constexpr double kInvLn2xN = kInvLn2x256;
-#else
-static constexpr int kExpTabN = 64, kExpTabDeg = 5;
-#define kExp2Tab kExp2Tab64
-#define kExpTabCoefs kExpTabA
-static constexpr double kInvLn2xN = kInvLn2x64;
-#endif
-
-// degree of the modified lanes' 2^(r/N) polynomial with the 256-entry table: 3 (minimax, 3.5e-14 relative) or 4 (Taylor, ~1 ulp)
-#ifndef IS3D_MOD_EXP_DEG
-#define IS3D_MOD_EXP_DEG 3
-#endif
-// the modified lanes' exp table: IS3D_MOD_TAB_BITS = 8 shares exp_tab's 256 entries (degree-3 polynomial); 11 gives them
-// their own 2^(j/2048) table (16 KB of LDS in the modified launches, which in turn drop their unused {b', Phi} rows:
-// IS3D_MOD_TABLES) and a degree-2 polynomial -- one FMA fewer per point, 2.1e-13 instead of 3.5e-14 relative
-#ifndef IS3D_MOD_TAB_BITS
-#define IS3D_MOD_TAB_BITS 8
-#endif
-// the modified launch builds only the per-tile tables its lanes read: no {b', Phi} rows and no separable y-term
-// slots (those serve the F_FB launch, which builds its own)
-#ifndef IS3D_MOD_TABLES
-#define IS3D_MOD_TABLES 1
-#endif
-#if IS3D_MOD_TAB_BITS == 11
-#if !IS3D_MOD_TABLES
-#error "IS3D_MOD_TAB_BITS = 11 needs IS3D_MOD_TABLES (the modified launches then read no exp_tab table)"
-#endif
-#include "exp2_tab2048.h"
-static constexpr int kModTabN = 2048, kModExpDeg = 2;
-#define kModExp2Tab kExp2Tab2048
-static constexpr double kModInvLn2xN = kInvLn2x2048;
-#define kModExpA kExpTabA2048
-#elif IS3D_MOD_TAB_BITS == IS3D_EXP_TAB_BITS
-static constexpr int kModTabN = kExpTabN;
-#define kModExp2Tab kExp2Tab
+// the modified lanes share exp_tab's 256-entry table, with a degree-3 polynomial for 2^(r/N): near-minimax (Chebyshev)
+// coefficients of (2^(r/256) - 1) / r on |r| <= 1/2, 1 + r p(r) within 3.5e-14 relative (the degree-4 Taylor form: ~1 ulp)
+static constexpr int kModTabN = kExpTabN, kModExpDeg = 3;
+static constexpr const double (&kModExp2Tab)[kModTabN] = kExp2Tab;
 static constexpr double kModInvLn2xN = kInvLn2xN;
-#if IS3D_EXP_TAB_BITS == 8 && IS3D_MOD_EXP_DEG == 3
-static constexpr int kModExpDeg = 3;
-// near-minimax (Chebyshev) coefficients of (2^(r/256) - 1) / r on |r| <= 1/2: 1 + r p(r) within 3.5e-14
-static constexpr double kModExpA[3] = {0.0027076061740622863, 3.6655660167967235e-06, 3.308302907918888e-09};
-#else
-static constexpr int kModExpDeg = kExpTabDeg;
-#define kModExpA kExpTabCoefs
-#endif
-#else
-#error "IS3D_MOD_TAB_BITS: 11, or equal to IS3D_EXP_TAB_BITS"
-#endif
+static constexpr double kModExpA[kModExpDeg] = {0.0027076061740622863, 3.6655660167967235e-06, 3.308302907918888e-09};
 
 struct ExpTabCoef { double shift, a[kExpTabDeg]; };
 
@@ -272,22 +186,7 @@ IS3D_HD double exp_tab(const ExpTabCoef& E, const double* tab, double xN, int ks
 #pragma unroll
   for (int i = kExpTabDeg - 2; i >= 0; i--) q = fma(q, rs, E.a[i]);
   const double T = tab[ki & (kExpTabN - 1)];
-  return ldexp(fma(T, rs * q, T), (ki >> IS3D_EXP_TAB_BITS) - kshift);
-}
-
-// e^(a v ln2 / kExpTabN) for a product a v (|a v| < 2^51) with the range reduction folded into the
-// product: t = fma(a, v, shift) rounds a v to the integer K exactly (one rounding), shift - t = -K
-// exactly, and rs = fma(a, v, -K) is the remainder with a single rounding -- three ops where
-// xN = a v, xN + shift, t - shift, xN - K took four (modified path, mod_en_x)
-IS3D_HD double exp_tab_fma(const ExpTabCoef& E, const double* tab, double a, double v) {
-  const double t = fma(a, v, E.shift);
-  const double rs = fma(a, v, E.shift - t);
-  const int ki = (int)(unsigned)__builtin_bit_cast(unsigned long long, t);
-  double q = E.a[kExpTabDeg - 1];
-#pragma unroll
-  for (int i = kExpTabDeg - 2; i >= 0; i--) q = fma(q, rs, E.a[i]);
-  const double T = tab[ki & (kExpTabN - 1)];
-  return ldexp(fma(T, rs * q, T), ki >> IS3D_EXP_TAB_BITS);
+  return ldexp(fma(T, rs * q, T), (ki >> kExpTabBits) - kshift);
 }
 
 // sinh and cosh of d for the y-terms: |d| < 0.5 by their Taylor series through d^17 / d^16 (truncation
@@ -1185,12 +1084,9 @@ static constexpr double kExpFast = -300.0;
 // (the rounding of the reciprocal it replaces: rcp1, ~2e-15); a Grad lane whose smallest exponent exceeds it
 // takes (1 - u) (1 + (1 - u) S) = (1 + S) - u (1 + 2 S) per point, no reciprocal (sep_quad_tb_near_t)
 static constexpr double kNearX = 18.0;
-// IS3D_SEP_INVA: sep_setup's default for inv_a (tail / near lanes take 1/a from one table exp of -xs instead of a and
-// its reciprocal).  MI355X (profiles/round6_r6e_ab_inva.log): config 2 operation 0 Grad k_dndx 319.6 -> 313.0 ms, but
-// the F_TS Grad k_spectra 151.0 -> 155.7 ms (same VGPRs, more SGPR spills) -- so off by default, on in k_dndx
-#ifndef IS3D_SEP_INVA
-#define IS3D_SEP_INVA 0
-#endif
+// sep_setup's inv_a: tail / near lanes take 1/a from one table exp of -xs instead of a and its reciprocal.  MI355X
+// (profiles/round6_r6e_ab_inva.log): config 2 operation 0 Grad k_dndx 319.6 -> 313.0 ms, but the F_TS Grad k_spectra
+// 151.0 -> 155.7 ms (same VGPRs, more SGPR spills) -- so off by default, and k_dndx passes it
 
 // 1/d for finite normal d: v_rcp_f64 (measured max rel. error 4.5e-8 on gfx950) + one
 // Newton step (~2e-15); IEEE division on the host.  Callers guarantee d is finite.
@@ -1239,7 +1135,7 @@ IS3D_HD bool sep_slow_cell(const double* R, double pT_max, double b_max) {
 
 IS3D_HD void sep_setup(int flavor, const double* R, const double* Y, double mT, double mT2, double m2, double mTb,
                        double pT, double sign, double baryon, const double* etab, SepLane& L, int allow_tail = 0,
-                       int allow_near = 0, bool inv_a = IS3D_SEP_INVA) {
+                       int allow_near = 0, bool inv_a = false) {
   L.sign = sign;
   L.x = fma(mT, Y[Y_AT], -baryon * R[R_CHEM]);
   const double zb = pT * R[R_ZB];                 // >= max_j |pT B_j / T|
@@ -1275,7 +1171,7 @@ IS3D_HD void sep_setup(int flavor, const double* R, const double* Y, double mT, 
 #endif
   const int k = (L.fast && xs > 150.0) ? (int)((xs - 150.0) * 1.4426950408889634) : 0;
   // tail and near lanes (xs > kNearX, so fast) use only 1/a = e^-xs 2^k: one table exp of -xs instead of a = e^xs 2^-k
-  // and its reciprocal (IS3D_SEP_INVA; a is left 0, none of their loops reads it)
+  // and its reciprocal (inv_a; a is left 0, none of their loops reads it)
   const bool inva = inv_a && (L.tail || L.near);
   double ra = 0.0;
   if (inva) {
@@ -1700,7 +1596,7 @@ IS3D_HD void sep_quad_tb_near_t(const SepLane& L, double mT, const dbl2* b, cons
 //   RTA-CE  acc += pb (1 + L + S / E),   L = L0 + Lc pc + Ls ps, E = E0 + Ec pc + Es ps, one 1/E per four
 // (pb = w p.dsigma f_eq = fma(D0, b', escw PD); against the fast fours' ~12 (Grad) / ~20 (RTA-CE) ops).
 // The F_TB launch's Grad tail lanes in this form read 6 LDS-array cycles per point instead of 8 but were
-// 2.2% slower there (IS3D_TAIL_PD, r2d); the per-lane launches (baryon on, RTA-CE with many classes) use it.
+// 2.2% slower there (r2d A/B); the per-lane launches (baryon on, RTA-CE with many classes) use it.
 template <int FL, bool REG, bool OUT>
 IS3D_HD void sep_quad_pd_tail_t(const SepLane& L, const dbl2* c, const dbl2* b, const double* pd, double* acc) {
   constexpr bool needE = FL == SEP_CE;
@@ -1820,29 +1716,17 @@ IS3D_HD double sqrt_nr(double v) {
 // table lanes (!clamp) e^chem is folded out of the exponential into sign and the p.dsigma
 // coefficients (en = e^chem e^-E/T: en / (1 + sign en) = e^chem e / (1 + (sign e^chem) e)), so a point
 // evaluates e^(-sig E_mod) alone.
-// Plus form (IS3D_MOD_PLUS, table lanes): f = 1 / (e^x + sign e^chem) e^chem with x = E_mod / T_mod evaluated as
+// Plus form (table lanes): f = 1 / (e^x + sign e^chem) e^chem with x = E_mod / T_mod evaluated as
 //   f = 2^-k / (E + s),  E = e^x 2^-k,  s = sign e^chem 2^-k,  2^-k e^chem folded into the p.dsigma coefficients,
 // where k = floor(x_min / ln2) over the lane's phi points (from mod_setup's lower bound) keeps E in [~1, 2^250]:
 // four denominators multiply without overflow and the scale costs nothing per point (2^-k enters the range
 // reduction's shift constant, shiftk = 1.5 2^52 - N k).  The numerator is 1, so a point saves the en x q_j product
 // of the en form (f = en / (1 + s en)); it is also the reference's own form, 1 / (exp(E/T - chem) + sign)
 // (MomentumSpectra.cpp:980).  Lanes whose phi range exceeds 250 binades take the clamped en form.
-#ifndef IS3D_MOD_PLUS
-#define IS3D_MOD_PLUS 1
-#endif
-// Boltzmann-tail lanes (IS3D_MOD_TAIL): where |s| < 2^-55 <= 2^-55 E at every point, E + s == E exactly, so
+// Boltzmann-tail lanes: where |s| < 2^-55 <= 2^-55 E at every point, E + s == E exactly, so
 // f = 2^-k / E = e^-(x - k ln2) 2^-k: the point evaluates that exponential directly (the shift constant
 // 1.5 2^52 + N k) and skips the denominators and the shared reciprocal (mod_quad_tab_tail_t).  Decided once
 // per wavefront (mod_setup allow_tail): a wave whose lanes straddle the bound runs the normal fours only
-#ifndef IS3D_MOD_TAIL
-#define IS3D_MOD_TAIL 1
-#endif
-#ifndef IS3D_MOD_WIDE_TAIL
-#define IS3D_MOD_WIDE_TAIL 1
-#endif
-#ifndef IS3D_MOD_EXACT
-#define IS3D_MOD_EXACT 1
-#endif
 struct ModExpCoef { double a[kModExpDeg]; };
 
 struct ModLane {
@@ -1853,7 +1737,7 @@ struct ModLane {
   ModExpCoef et;               // pinned once per lane setup, reused by every phi point
   const double* etab;          // 2^(j/kModTabN) table (LDS on the device)
   int skip, clamp;   // clamp: some point's exp argument may leave the table lanes' domain (exp_clamped instead)
-  int tail;          // IS3D_MOD_TAIL: Boltzmann-tail table lane (shiftk = 1.5 2^52 + N k, mod_quad_tab_tail_t)
+  int tail;          // Boltzmann-tail table lane (shiftk = 1.5 2^52 + N k, mod_quad_tab_tail_t)
 };
 
 // Qv = |pc Vc + ps Vs|^2 for one (cell, phi), exp-table units (sig^2)
@@ -1871,28 +1755,13 @@ static constexpr double kLn2overN = 1.0 / kModInvLn2xN;
 // overflows too (E/T - chem > 715), so folding e^chem out loses nothing, and four 1 + sign e^chem e
 // factors multiply without overflow in the quad reciprocal
 static constexpr double kModTabX = 1.0e6, kModTabChem = 30.0;
-#ifndef IS3D_MODQ_ACC
-#define IS3D_MODQ_ACC 1
-#endif
-#ifndef IS3D_MOD_SQ_BOUNDS
-#define IS3D_MOD_SQ_BOUNDS 1
-#endif
 
 // e^x for xN = x kModTabN/ln2 with the modified lanes' table and polynomial (mod_setup's e^chem)
 IS3D_HD double mod_exp(const double* etab, double xN) {
-  if (IS3D_MOD_TAB_BITS == IS3D_EXP_TAB_BITS) return exp_tab(exp_tab_coef(), etab, xN);   // the shared table
-  const double sh = 6755399441055744.0;
-  const double t = xN + sh;
-  const double rs = xN - (t - sh);
-  const int ki = (int)(unsigned)__builtin_bit_cast(unsigned long long, t);
-  double p = kModExpA[kModExpDeg - 1];
-#pragma unroll
-  for (int i = kModExpDeg - 2; i >= 0; i--) p = fma(p, rs, kModExpA[i]);
-  const double T = etab[ki & (kModTabN - 1)];
-  return ldexp(fma(T, rs * p, T), ki >> IS3D_MOD_TAB_BITS);
+  return exp_tab(exp_tab_coef(), etab, xN);   // the shared table
 }
 
-// mod_setup's skip test alone (same operations, IS3D_MOD_SQ_BOUNDS form), for an early branch past the setup
+// mod_setup's skip test alone (same operations), for an early branch past the setup
 IS3D_HD bool mod_skips(const double* R, const double* Y, double mT, double m2, double pT, double baryon, bool ymu = true) {
   const double ux = Y[Y_MUX], uy = Y[Y_MUY], uz = Y[Y_MUZ];
   const double u2 = ymu ? Y[Y_MU2] : fma(ux, ux, fma(uy, uy, uz * uz));
@@ -1904,7 +1773,7 @@ IS3D_HD bool mod_skips(const double* R, const double* Y, double mT, double m2, d
 }
 
 // KJX > 0 (k_spectra's table lanes; -1: nx points, the host emulator): MW / MT are the lane's {PDm, Qv} and T2 rows of KJX points.  A lane whose bounds
-// span more than 250 binades (wide) takes its exact smallest / largest X over those points instead (IS3D_MOD_EXACT): the
+// span more than 250 binades (wide) takes its exact smallest / largest X over those points instead: the
 // bounds |mT U| -+ pT |V|max are loose where pT |V| is large, and a lane found wide by them went to the clamped en form
 // (1.6x the normal fours' instructions) although its points spanned a median 134 binades (config 2 PTM, host census)
 template <int KJX = 0>
@@ -1927,20 +1796,12 @@ IS3D_HD void mod_setup(const double* R, const double* Y, double mT, double m2, d
   // the lane takes the clamped exp
   const double mu = mT * (ymu ? Y[Y_MU] : sqrt(u2));
   const double lo = mu - pT * R[R_VB], hi = mu + pT * R[R_VB];
-#if IS3D_MOD_SQ_BOUNDS
   // the same two tests on squares (no sqrt): skip when sig E_min (1 - 1e-12) exceeds
   // thr = (kExpMax + 1 + chem) N/ln2 -- always when thr < 0, as E_min >= 0
   const double thr = (kExpMax + 1.0 + L.chemm) * kModInvLn2xN, xm = kModTabX * kModInvLn2xN;
   L.skip = (thr < 0.0 || (lo > 0.0 && (m2s + lo * lo) * (1.0 - 2e-12) > thr * thr)) ? 1 : 0;
   L.clamp = ((m2s + hi * hi) < xm * xm && fabs(L.chemm) < kModTabChem) ? 0 : 1;
-#else
-  const double emin = (lo > 0.0) ? sqrt(m2s + lo * lo) * (1.0 - 1e-12) : 0.0;
-  L.skip = (emin * kLn2overN - L.chemm > kExpMax + 1.0) ? 1 : 0;
-  const double emax = sqrt(m2s + hi * hi) * kLn2overN;
-  L.clamp = (emax < kModTabX && fabs(L.chemm) < kModTabChem) ? 0 : 1;
-#endif
   int k = 0, wide = 0;
-#if IS3D_MOD_PLUS
   if (!L.clamp) {
     // k = floor(x_min / ln2) from the lane's smallest sig E_mod (a lower bound of it: rounding down only
     // raises E by a factor < 2); the normal fours need the largest point within 250 binades of 2^k (wide: not)
@@ -1957,7 +1818,7 @@ IS3D_HD void mod_setup(const double* R, const double* Y, double mT, double m2, d
     };
     scale();
     if constexpr (KJX != 0) {   // KJX = -1: nx points (the host emulator)
-      if (IS3D_MOD_EXACT && MW) {
+      if (MW) {
         // the exact range of the lane's points (the loops' own X expression); a wave-uniform branch on the device
 #if defined(__HIP_DEVICE_COMPILE__)
         int aw = __any(wide);
@@ -1980,15 +1841,13 @@ IS3D_HD void mod_setup(const double* R, const double* Y, double mT, double m2, d
       }
     }
   }
-#endif
   // only callers that evaluate tail lanes with mod_quad_tab_tail_t pass allow_tail.  The tail form has no
   // denominators (no product of four), so a wide lane is a tail lane too when its sign term is negligible
-  // (IS3D_MOD_WIDE_TAIL; before, every wide lane took the clamped en form: 5% of config 2's PTM wavefronts, at 1.6x the
+  // (before, every wide lane took the clamped en form: 5% of config 2's PTM wavefronts, at 1.6x the
   // normal fours' instructions)
-  L.tail = (IS3D_MOD_PLUS && IS3D_MOD_TAIL && allow_tail && !L.clamp && (IS3D_MOD_WIDE_TAIL || !wide) &&
-            L.chemm * 1.4426950408889634 < k - 55) ? 1 : 0;
+  L.tail = (allow_tail && !L.clamp && L.chemm * 1.4426950408889634 < k - 55) ? 1 : 0;
 #if defined(__HIP_DEVICE_COMPILE__)
-  if (IS3D_MOD_TAIL && allow_tail) {   // one decision per wavefront, passed through a VGPR (see sep_setup)
+  if (allow_tail) {   // one decision per wavefront, passed through a VGPR (see sep_setup)
     int t = __all(L.tail);
     asm volatile("" : "+v"(t));
     L.tail = t;
@@ -2007,8 +1866,7 @@ IS3D_HD void mod_setup(const double* R, const double* Y, double mT, double m2, d
 }
 
 // The Fermi/Bose factor of one point as num / q: clamped lanes num = en = e^(chem - E_mod/T_mod),
-// q = 1 + sign en; table lanes in the plus form num = 1, q = E + s (see ModLane), in the en form (IS3D_MOD_PLUS 0)
-// num = en = e^(-E_mod/T_mod), q = 1 + s en.  X = (sig E_mod)^2: one Newton step of the v_rsq_f64 estimate y
+// q = 1 + sign en; table lanes in the plus form num = 1, q = E + s (see ModLane).  X = (sig E_mod)^2: one Newton step of the v_rsq_f64 estimate y
 // folded into the exp argument, sig E_mod = g v with g = X y, v = 1.5 - 0.5 g y, and the range reduction folded
 // into the product (t = fma(g, v, shift) rounds g v to the integer K exactly, rs = fma(g, v, shift - t))
 // rsq estimate of the table lanes' X = (sig E_mod)^2 (v_rsq_f64, 16 cycles per wave on MI355X, tools/microbench.hip; v_rsq_f32
@@ -2029,9 +1887,9 @@ IS3D_HD void mod_nq_x(const ModLane& L, double X, double& num, double& q) {
     return;
   }
   const double y = mod_rsq(X);
-  const double g = IS3D_MOD_PLUS ? X * y : -(X * y);
+  const double g = X * y;
   const double v = fma(-0.5, X * y * y, 1.5);
-  const double sh = IS3D_MOD_PLUS ? L.shiftk : kconst(6755399441055744.0);
+  const double sh = L.shiftk;
   const double t = fma(g, v, sh);
   const double rs = fma(g, v, sh - t);
   const int ki = (int)(unsigned)__builtin_bit_cast(unsigned long long, t);
@@ -2039,9 +1897,8 @@ IS3D_HD void mod_nq_x(const ModLane& L, double X, double& num, double& q) {
 #pragma unroll
   for (int i = kModExpDeg - 2; i >= 0; i--) p = fma(p, rs, L.et.a[i]);
   const double T = L.etab[ki & (kModTabN - 1)];
-  const double e = ldexp(fma(T, rs * p, T), ki >> IS3D_MOD_TAB_BITS);
-  if (IS3D_MOD_PLUS) { num = 1.0; q = e + L.sign; }
-  else { num = e; q = fma(L.sign, e, 1.0); }
+  const double e = ldexp(fma(T, rs * p, T), ki >> kExpTabBits);
+  num = 1.0; q = e + L.sign;
 }
 
 // the same from the lane's linear form (qv = modqv of the cell at this phi)
@@ -2117,32 +1974,20 @@ IS3D_HD double modt2(const double* R, const double* Y, dbl2 cs) {
 // mod_nq_x for four points in stages: the four range reductions, then the four table reads issued
 // together, then the four polynomials (independent of the reads), then the products -- so one LDS
 // latency is waited for per four points instead of per one or two (same operations, same results)
-#ifndef IS3D_MOD_STAGED
-#define IS3D_MOD_STAGED 1
-#endif
-#ifndef IS3D_MOD_IEXP
-#define IS3D_MOD_IEXP 0
-#endif
-// m 2^k for a normal m and a k that keeps the result normal: k added to the exponent field of the high word
-IS3D_HD double exp_field_add(double m, int k) {
-  const unsigned long long b = __builtin_bit_cast(unsigned long long, m);
-  const unsigned hi = (unsigned)(b >> 32) + ((unsigned)k << 20), lo = (unsigned)b;
-  return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
 template <bool CLAMP, bool TAIL = false>
 IS3D_HD void mod_nq4(const ModLane& L, const double* X, double* num, double* q) {
-  if (!TAIL && (CLAMP || !IS3D_MOD_STAGED)) {
+  if (!TAIL && CLAMP) {
 #pragma unroll
     for (int i = 0; i < 4; i++) mod_nq_x<CLAMP>(L, X[i], num[i], q[i]);
     return;
   }
   double t[4], rs[4], T[4], p[4];
   int ki[4];
-  const double sh = IS3D_MOD_PLUS ? L.shiftk : kconst(6755399441055744.0);
+  const double sh = L.shiftk;
 #pragma unroll
   for (int i = 0; i < 4; i++) {
     const double y = mod_rsq(X[i]);
-    const double g = (IS3D_MOD_PLUS && !TAIL) ? X[i] * y : -(X[i] * y);
+    const double g = !TAIL ? X[i] * y : -(X[i] * y);
     const double v = fma(-0.5, X[i] * y * y, 1.5);
     t[i] = fma(g, v, sh);
     rs[i] = fma(g, v, sh - t[i]);
@@ -2160,14 +2005,9 @@ IS3D_HD void mod_nq4(const ModLane& L, const double* X, double* num, double* q) 
 #pragma unroll
   for (int i = 0; i < 4; i++) {
     const double m = fma(T[i], p[i], T[i]);
-    // plus-form normal lanes: E = m 2^K lies in [~1/2, 2^251] (mod_setup's k), so the scale can go straight into
-    // the exponent field (one INT32 shift-add on the high word instead of v_ldexp_f64: IS3D_MOD_IEXP); the tail
-    // and en forms can underflow and keep ldexp
-    const double e = (IS3D_MOD_IEXP && IS3D_MOD_PLUS && !TAIL) ? exp_field_add(m, ki[i] >> IS3D_MOD_TAB_BITS)
-                                                                : ldexp(m, ki[i] >> IS3D_MOD_TAB_BITS);
+    const double e = ldexp(m, ki[i] >> kExpTabBits);
     if (TAIL) { num[i] = e; q[i] = 1.0; }
-    else if (IS3D_MOD_PLUS) { num[i] = 1.0; q[i] = e + L.sign; }
-    else { num[i] = e; q[i] = fma(L.sign, e, 1.0); }
+    else { num[i] = 1.0; q[i] = e + L.sign; }
   }
 }
 

@@ -18,12 +18,6 @@
 #ifndef IS3D_LDS_QROW_LIMIT
 #define IS3D_LDS_QROW_LIMIT (80 * 1024)   // above this k_spectra takes the F_LY launch (per-lane y-term rows)
 #endif
-#ifndef IS3D_ANISO_MERGE
-#define IS3D_ANISO_MERGE 1    // PTMA Newton sums over hadrons merged by identical (mass, sign)
-#endif
-#ifndef IS3D_MP
-#define IS3D_MP 1             // k_spectra's F_MP launch (several pT per workgroup) for few lane tasks per pT
-#endif
 #ifndef IS3D_FILL_WGS
 #define IS3D_FILL_WGS 8192    // k_spectra workgroups the cell splits aim for (>= 8k fills the chip evenly)
 #endif
@@ -38,9 +32,6 @@
 #endif
 #ifndef IS3D_CHAIN_W
 #define IS3D_CHAIN_W 4        // PTMA chain segments: wavefronts per segment sharing each Newton evaluation's terms
-#endif
-#ifndef IS3D_NEWTON_WAVES
-#define IS3D_NEWTON_WAVES 0   // PTMA Newton kernels (k_aniso, k_chain_pass): waves per SIMD to allocate for (0: compiler)
 #endif
 #ifndef IS3D_MAX_SPLITS
 #define IS3D_MAX_SPLITS 1024  // cap on k_spectra's cell splits (one output-sized slab each)
@@ -184,10 +175,10 @@ struct AnisoArgs {
 };
 
 // one wavefront per warm-start chain: cells chain, chain + C, chain + 2C, ... (MomentumSpectra.cpp:98-107)
-__global__ __launch_bounds__(64, IS3D_NEWTON_WAVES ? IS3D_NEWTON_WAVES : 1) void k_aniso(AnisoArgs A) {
+__global__ __launch_bounds__(64, 1) void k_aniso(AnisoArgs A) {
   const long chain = blockIdx.x;
   const int lane = threadIdx.x;
-  __shared__ double s_etab[kExpTabN];                       // aniso_math.h aexp (IS3D_ANISO_FAST)
+  __shared__ double s_etab[kExpTabN];                       // aniso_math.h aexp
   for (int i = lane; i < kExpTabN; i += 64) s_etab[i] = kExp2Tab[i];
   __syncthreads();
   Hadrons h = A.h;
@@ -304,7 +295,7 @@ __device__ __forceinline__ Hadrons chain_hadrons(const ChainArgs& A, double* s_e
 
 // one workgroup of IS3D_CHAIN_W wavefronts per segment (the lanes share each Newton evaluation's terms); every
 // branch below is uniform over the workgroup (the reductions hand all lanes the same bits)
-__global__ __launch_bounds__(64 * IS3D_CHAIN_W, IS3D_NEWTON_WAVES ? IS3D_NEWTON_WAVES : 1) void k_chain_pass(ChainArgs A, int pass) {
+__global__ __launch_bounds__(64 * IS3D_CHAIN_W, 1) void k_chain_pass(ChainArgs A, int pass) {
   const long seg = blockIdx.x, nseg = A.C * A.nspc;
   const long c = seg / A.nspc, s = seg % A.nspc;
   const int lane = threadIdx.x;
@@ -921,7 +912,7 @@ struct is3d_engine {
   long phtab2_cap = 0;
   hipStream_t side = nullptr; // F_TS chunks alternate between the launch stream and this one
   hipEvent_t fork = nullptr, join = nullptr;
-  // folded F_TS chunks (IS3D_SLAB_FOLD): k_fold runs on its own stream, in chunk order, after each chunk's k_spectra
+  // folded F_TS chunks: k_fold runs on its own stream, in chunk order, after each chunk's k_spectra
   // (ev_spec); a chunk reusing a slab buffer waits for the fold that emptied it (ev_fold)
   hipStream_t fold_st = nullptr;
   hipEvent_t ev_spec[2] = {nullptr, nullptr}, ev_fold[2] = {nullptr, nullptr}, fold_join = nullptr;
@@ -1261,29 +1252,29 @@ static SpectraPlan spectra_plan(const is3d_engine* e, bool allow_ts = true) {
     // workgroup
     // with include_baryon only as F_TS + F_BY (one phi block of 24 or 32 points: the baryon part of the linear
     // coefficients comes from the table as T3)
-    const bool ts_shape = IS3D_TS && IS3D_TS_BY && allow_ts && P.njb == 1 && (KJ == 24 || KJ == 32);
-    P.tb = (IS3D_GRAD_TB && (mode == GRAD || (mode == CE && IS3D_CE_TB)) && (!e->p.include_baryon || ts_shape) &&
+    const bool ts_shape = allow_ts && P.njb == 1 && (KJ == 24 || KJ == 32);
+    P.tb = ((mode == GRAD || mode == CE) && (!e->p.include_baryon || ts_shape) &&
             KJ % 4 == 0 && P.nqmax <= kTbQ) ? F_TB : 0;
   };
   int kTile = (mode >= PTM) ? IS3D_KTILE_MOD : is3d::kern::kTile;   // spectra_tile<MODE, FLAGS>()
   // k_spectra's LDS layout (kernels.h): record tiles x kRecBufs, per-tile tables x kTabBufs
   // F_TS (kernels.h TS): an F_TB launch with one phi block of 24 or 32 points
-  auto ts_ok = [&]() { return IS3D_TS && allow_ts && P.tb && P.njb == 1 && (P.KJ == 24 || P.KJ == 32); };
+  auto ts_ok = [&]() { return allow_ts && P.tb && P.njb == 1 && (P.KJ == 24 || P.KJ == 32); };
   bool fb_layout = false;               // sizing the F_FB launch (separable lanes of a modified mode)
   auto lds_bytes = [&](int qrows) {     // qrows = 0: F_LY layout (one y-term row per lane)
     const size_t nphp = (size_t)P.njb * P.KJ, tile = (size_t)kTile;
-    // modified launches (kernels.h MODMAIN): the modified lanes' exp table, no {b', Phi} rows (IS3D_MOD_TABLES)
+    // modified launches (kernels.h MODMAIN): no {b', Phi} rows
     const bool modmain = mode >= PTM && !fb_layout;
-    const size_t etab = modmain ? (size_t)is3d::kModTabN : (size_t)kExpTabN;
-    const size_t bprows = (modmain && IS3D_MOD_TABLES) ? 0 : 1;
+    const size_t etab = kExpTabN;
+    const size_t bprows = modmain ? 0 : 1;
     if (ts_ok()) {
       // records x 3, trig + {pc, ps}, grid, y-term rows x 2, exp table, T1 rows [tile][qrows][KJ + 2] (+ 1: alignment)
       return sizeof(double) * (3 * tile * NREC + 4 * nphp + (size_t)(nk + 2 * nl) +
                                2 * tile * std::min(qrows, P.nq) * kYRow + kExpTabN + tile * qrows * (P.KJ + 2) + 1 +
-                               (IS3D_TS_PF ? 128 : 0));
+                               128);     // + 128: the landing rows of the k_phitab L2 prefetch
     }
     // pipelined launches (F_TB, the modified path's 16-cell tiles): 3 record tiles, 2 table buffers
-    const bool pipe = IS3D_PIPE && (P.tb || (mode >= PTM && qrows && !P.t8 && !P.ly));
+    const bool pipe = (P.tb || (mode >= PTM && qrows && !P.t8 && !P.ly));
     const size_t rb = pipe ? 3 : 2, tb = pipe ? 2 : 1, qvf = (mode >= PTM || !pipe) ? 2 : 1;
     const size_t w = (size_t)P.npw;     // F_MP: pT blocks of {pc, ps} and of the per-(cell, phi) tables
     return sizeof(double) * (rb * tile * NREC + (2 + 2 * w) * nphp + bprows * tb * 2 * w * tile * nphp + tb * qvf * w * tile * nphp +
@@ -1293,14 +1284,10 @@ static SpectraPlan spectra_plan(const is3d_engine* e, bool allow_ts = true) {
                              (P.tb && mode == CE ? tb * 2 * tile * nphp : 0) +
                              // the per-lane RTA-CE launch's {TE, T2} table (kernels.h PDE)
                              // (+ 1: s_pe starts at the 16-byte-aligned end of the y-term rows)
-                             (IS3D_CE_PE && mode == CE && !P.tb && !P.mp && qrows && P.KJ % 4 == 0 ? tb * 2 * tile * nphp + 1 : 0) +
+                             (mode == CE && !P.tb && !P.mp && qrows && P.KJ % 4 == 0 ? tb * 2 * tile * nphp + 1 : 0) +
                              (mode >= PTM && qrows ? tile * qrows * (P.KJ + 1) + 1 : 0));
   };
-#ifdef IS3D_FORCE_KJ
-  shape(IS3D_FORCE_KJ);
-#else
   shape(spectra_kj_fill(nphi, (long)np * P.nq));
-#endif
   P.ly = 0;
   P.shmem = lds_bytes(P.nqmax);
   // RTA-CE's table launch adds {TE, T2} to the {PD, T1} rows: where that costs the third workgroup per CU
@@ -1334,7 +1321,7 @@ static SpectraPlan spectra_plan(const is3d_engine* e, bool allow_ts = true) {
   // most half a workgroup (pikp 2+1D: 3 x 24 = 72), a workgroup takes npw = 256 / tasks pT values and every
   // lane a whole phi row -- the lane setup (~4.5 points' work) is paid once per row instead of once per
   // 8-point block; chosen by the same cost model as spectra_kj_fill (lane slots x (KJ + 4.5))
-  if (IS3D_MP && mode <= CE && !P.tb && !P.ly && nphi <= 32) {
+  if (mode <= CE && !P.tb && !P.ly && nphi <= 32) {
     const long tpp = (long)np * P.nq;
     const int kjm = nphi <= 24 ? 24 : 32;
     if (tpp * 2 <= kBlock) {
@@ -1379,14 +1366,9 @@ static SpectraPlan spectra_plan(const is3d_engine* e, bool allow_ts = true) {
 // PTM's renormalisation n_linear / n_mod (MomentumSpectra.cpp:790-832) is a ratio of two sums that both carry the
 // degeneracy as a factor, so it depends on (mass, sign, baryon) alone -- except g = 0, where it is 0 / 0 = NaN and the
 // species is skipped.  The renormalisation classes and PTM's integrand classes therefore key on whether g is zero
-// (IS3D_PTM_GCLASS 0: SMASH 205 -> 193 PTM lane classes, the same as the other modes; the class representative's g
-// cancels to rounding, ~1e-16); IS3D_PTM_GCLASS 1 keys on g itself (round 3 / 4)
-#ifndef IS3D_PTM_GCLASS
-#define IS3D_PTM_GCLASS 0
-#endif
-static uint64_t ptm_gkey(double g) {
-  return IS3D_PTM_GCLASS ? __builtin_bit_cast(uint64_t, g) : (uint64_t)(g == 0.0 ? 1 : 0);
-}
+// (SMASH 205 -> 193 PTM lane classes, the same as the other modes; the class representative's g cancels to rounding,
+// ~1e-16; rounds 3 / 4 keyed on g itself)
+static uint64_t ptm_gkey(double g) { return (uint64_t)(g == 0.0 ? 1 : 0); }
 
 static int finalize_tables(is3d_engine* e) {
   if (!e->have_params) return e->fail(IS3D_ERR_STATE, "is3d_set_params not called");
@@ -1524,9 +1506,8 @@ static int finalize_tables(is3d_engine* e) {
     const int nh = std::min(320, (int)e->pdg_mass.size());
     for (int i = 0; i < nh; i++) {
       int k = -1;
-      if (IS3D_ANISO_MERGE)
-        for (size_t u = 0; u < am.size(); u++)
-          if (am[u] == e->pdg_mass[i] && as[u] == e->pdg_sign[i]) { k = (int)u; break; }
+      for (size_t u = 0; u < am.size(); u++)
+        if (am[u] == e->pdg_mass[i] && as[u] == e->pdg_sign[i]) { k = (int)u; break; }
       if (k < 0) { am.push_back(e->pdg_mass[i]); as.push_back(e->pdg_sign[i]); ag.push_back(e->pdg_degen[i]); }
       else ag[k] += e->pdg_degen[i];
     }
@@ -1818,10 +1799,6 @@ struct IntegralPlan {
   long slabs() const { return fold ? 1 + 2 * spc : nsplit + nsplit_fb; }
 };
 
-#ifndef IS3D_SLAB_FOLD
-#define IS3D_SLAB_FOLD 1
-#endif
-
 // F_TS chunking of plan I over nw cells: tables of the whole window up to phitab_one bytes in one chunk, larger ones in
 // chunks of whole cell splits of about phitab_chunk bytes; both within half the device's free memory (plus the table
 // buffers this engine already holds)
@@ -1842,7 +1819,7 @@ static void ts_chunking(is3d_engine* e, IntegralPlan& I) {
   const long budget = whole <= one ? whole : chunk;
   I.spc = std::max(1L, std::min(I.nsplit, budget / 8 / per_split));
   I.nchunk = (I.nsplit + I.spc - 1) / I.spc;
-  I.fold = IS3D_SLAB_FOLD && I.nchunk > 1 && e->p.dimension == 3 && I.nsplit_fb == 0;
+  I.fold = I.nchunk > 1 && e->p.dimension == 3 && I.nsplit_fb == 0;
 }
 
 static int integral_plan(is3d_engine* e, const SpectraPlan& P, long nw, IntegralPlan& I, long cap_slabs = 0) {
@@ -2377,16 +2354,16 @@ extern "C" int is3d_calculate_dN_dX(is3d_engine* e, double* dN_taudtaudy, double
     da.yv = e->d_y; da.etav = e->d_eta; da.etaw = e->d_etaw;
     da.npart = nc; da.npT = npT; da.nphi = nphi; da.nk = nk; da.nl = nl; da.nq = nk * nl; da.njb = njb; da.dim = dim;
     const size_t nphp = (size_t)njb * KJ;
-    // kernels.h k_dndx's layout: records, trig / {pc, ps} / phi weights, {b', Phi} rows (not in the modified launch:
-    // IS3D_MOD_TABLES), Qv rows, per-lane cell sums, grid, y-term rows, exp table, PTM's renorm factors [kTile][Sl]
+    // kernels.h k_dndx's layout: records, trig / {pc, ps} / phi weights, {b', Phi} rows (not in the modified
+    // launch), Qv rows ({PDm, Qv} pairs in the modified launch with phi blocks of fours), per-lane cell sums, grid, y-term rows, exp table, PTM's renorm factors [kTile][Sl]
     auto dndx_lds = [&](bool modmain, bool fb = false) {
-      const bool bp = !(modmain && IS3D_MOD_TABLES);
+      const bool bp = !modmain;
       // kernels.h dndx_tile: the launch's record tile
       const size_t kTile = fb ? is3d::kern::kTile : modmain ? IS3D_DNDX_TILE_MOD : IS3D_DNDX_TILE;
       return sizeof(double) * ((size_t)kTile * NREC + 2 * nphp + 2 * nphp + nphp + (bp ? 2 : 0) * (size_t)kTile * nphp +
-                               (modmain && IS3D_DNDX_PDM && KJ % 4 == 0 ? 2 : 1) * (size_t)kTile * nphp +
+                               (modmain && KJ % 4 == 0 ? 2 : 1) * (size_t)kTile * nphp +
                                (size_t)kTile * kBlock + (size_t)(nk + 2 * nl) +
-                               (size_t)kTile * da.nq * kYRowLY + (size_t)(modmain ? is3d::kModTabN : kExpTabN) +
+                               (size_t)kTile * da.nq * kYRowLY + (size_t)kExpTabN +
                                (mode == PTM ? (size_t)kTile * da.Sl : 0));
     };
     const size_t shmem = dndx_lds(mode >= PTM), shmem_fb = dndx_lds(false, true);

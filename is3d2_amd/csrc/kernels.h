@@ -11,98 +11,108 @@ namespace is3d {
 namespace kern {
 
 constexpr int kBlock = 256;
+
+// ---- sizing parameters: plain numbers with no code path behind them, overridable for A/B builds
+// (make variant EXTRA=-DIS3D_KTILE=...).  How each value was chosen is noted where it is used.
 #ifndef IS3D_KTILE
-#define IS3D_KTILE 8
+#define IS3D_KTILE 8               // k_spectra: cells per LDS tile (Grad / RTA-CE per-lane and F_TB launches, F_T8, F_LY)
 #endif
-constexpr int kTile = IS3D_KTILE;   // cells per LDS tile
 #ifndef IS3D_KTILE_MOD
-#define IS3D_KTILE_MOD 8    // modified path: 8 cells per tile since it runs 3 waves/SIMD (3 workgroups' LDS per CU;
-                            // 16 paid at 2 waves: 1279 -> 1245 ms, r2t A/B)
+#define IS3D_KTILE_MOD 8           // k_spectra: cells per tile of the modified launch
 #endif
+#ifndef IS3D_KTILE_TS
+#define IS3D_KTILE_TS 12           // k_spectra: cells per tile of the F_TS launches
+#endif
+#ifndef IS3D_SPECTRA_WAVES_SEP
+#define IS3D_SPECTRA_WAVES_SEP 3   // k_spectra: waves per SIMD Grad is register-allocated for
+#endif
+#ifndef IS3D_SPECTRA_WAVES_MOD
+#define IS3D_SPECTRA_WAVES_MOD 3   // ... the modified launch
+#endif
+#ifndef IS3D_SPECTRA_WAVES_CE
+#define IS3D_SPECTRA_WAVES_CE 3    // ... RTA-CE
+#endif
+#ifndef IS3D_DNDX_WAVES_MOD
+#define IS3D_DNDX_WAVES_MOD 2      // k_dndx: waves per SIMD of the modified-lane launch
+#endif
+#ifndef IS3D_DNDX_MOD_UNROLL
+#define IS3D_DNDX_MOD_UNROLL 2     // k_dndx modified lanes: fours of phi points per unrolled loop trip
+#endif
+#ifndef IS3D_DNDX_TILE_MOD
+#define IS3D_DNDX_TILE_MOD 4       // k_dndx: cells per record tile of the modified launch (engine.hip sizes its LDS the same way)
+#endif
+#ifndef IS3D_DNDX_TILE
+#define IS3D_DNDX_TILE 8           // k_dndx: cells per record tile of the Grad / RTA-CE launches
+#endif
+#ifndef IS3D_PHITAB_ONE
+#define IS3D_PHITAB_ONE (8L << 30)     // F_TS tables up to this size are written and integrated in one chunk
+#endif
+#ifndef IS3D_PHITAB_BYTES
+#define IS3D_PHITAB_BYTES (2L << 30)   // larger ones in chunks of whole cell splits of about this size
+#endif
+#ifndef IS3D_SPLIT_BYTES
+#define IS3D_SPLIT_BYTES (512L << 10)  // record bytes per cell split (k_spectra grid sizing)
+#endif
+#ifndef IS3D_TS_PF_DIST_GRAD
+#define IS3D_TS_PF_DIST_GRAD 1     // F_TS: L2 prefetch distance of the k_phitab rows in tiles, Grad
+#endif
+#ifndef IS3D_TS_PF_DIST_CE
+#define IS3D_TS_PF_DIST_CE 1       // ... RTA-CE
+#endif
+#ifndef IS3D_TS_AHEAD_CE
+#define IS3D_TS_AHEAD_CE 1         // F_TS: fours whose operands load one four ahead (bit 1 tail lanes, bit 2 other lanes), RTA-CE
+#endif
+#ifndef IS3D_TS_AHEAD_GRAD
+#define IS3D_TS_AHEAD_GRAD 3       // ... Grad without baryon terms
+#endif
+#ifndef IS3D_TS_AHEAD_GRAD_BY
+#define IS3D_TS_AHEAD_GRAD_BY 1    // ... Grad with baryon terms (F_BY)
+#endif
+
+constexpr int kTile = IS3D_KTILE;   // cells per LDS tile
 // cells per k_spectra tile of one delta-f mode and launch (8 for Grad / RTA-CE: 16 costs them 18% / 11%,
 // r2t; the modified path's F_T8 and F_LY launches keep 8 where 16 cells' q-row tables would not fit:
-// config 1's shape in F_LY ran 11.2 ms with 8-cell tiles, 13.6 ms with 16)
-#ifndef IS3D_KTILE_TS
-#define IS3D_KTILE_TS 12      // F_TS launches (LDS: records, y-terms and T1 rows only). Each k_phitab row a
-                              // wave reads through the scalar cache serves the tile's cells: config 2 Grad
-                              // 155.5 ms at 8 cells, 154.2 at 10, 151.5 at 12 and 14, 188.5 at 16 (LDS
-                              // occupancy); RTA-CE 241.6 / 239.0 / 237.8 / 240.3; config 4 flat at 8-14
-                              // (profiles/round5_r5h_ab_ts_tile.log)
-#endif
+// config 1's shape in F_LY ran 11.2 ms with 8-cell tiles, 13.6 ms with 16).
+// Modified launch: 8 cells per tile since it runs 3 waves/SIMD (3 workgroups' LDS per CU; 16 paid at 2 waves:
+// 1279 -> 1245 ms, r2t A/B).
+// F_TS launches (LDS: records, y-terms and T1 rows only): 12.  Each k_phitab row a wave reads through the scalar
+// cache serves the tile's cells: config 2 Grad 155.5 ms at 8 cells, 154.2 at 10, 151.5 at 12 and 14, 188.5 at 16
+// (LDS occupancy); RTA-CE 241.6 / 239.0 / 237.8 / 240.3; config 4 flat at 8-14 (profiles/round5_r5h_ab_ts_tile.log)
 template <int MODE, int FLAGS>
 constexpr int spectra_tile() {
   return (MODE >= PTM && !(FLAGS & (32 | 16 | 8))) ? IS3D_KTILE_MOD : ((FLAGS & 128) && (FLAGS & 4)) ? IS3D_KTILE_TS : kTile;
 }
 // waves per SIMD the spectra kernel is register-allocated for (measured on MI355X, config2):
-// Grad and RTA-CE run best at 3 (168 VGPRs), the modified-momentum modes at 2
-#ifndef IS3D_SPECTRA_WAVES_SEP
-#define IS3D_SPECTRA_WAVES_SEP 3
-#endif
-#ifndef IS3D_SPECTRA_WAVES_MOD
-#define IS3D_SPECTRA_WAVES_MOD 3   // without the separable code (F_FB launch): 164 VGPRs; config2 PTM 1242 -> 1044 ms (r3 A/B)
-#endif
-#ifndef IS3D_SPECTRA_WAVES_CE
-#define IS3D_SPECTRA_WAVES_CE 3      // RTA-CE: 3 (16 spilled VGPRs, 3 scratch accesses per 32 points) beat 2 by 4.3% once
-                                     // the lane setup shrank (profiles/round1_r1z_ab_ce3.log; 2 won before, r1n)
-#endif
-// waves per SIMD of one spectra / dN/dX instantiation
+// Grad runs best at 3 (168 VGPRs);
+// the modified launch, without the separable code (F_FB launch), at 3: 164 VGPRs; config2 PTM 1242 -> 1044 ms (r3 A/B);
+// RTA-CE: 3 (16 spilled VGPRs, 3 scratch accesses per 32 points) beat 2 by 4.3% once the lane setup shrank
+// (profiles/round1_r1z_ab_ce3.log; 2 won before, r1n)
 template <int MODE>
 constexpr int spectra_waves() {
   return MODE >= PTM ? IS3D_SPECTRA_WAVES_MOD : MODE == CE ? IS3D_SPECTRA_WAVES_CE : IS3D_SPECTRA_WAVES_SEP;
 }
-#ifndef IS3D_SPECTRA_WAVES_KJ16
-#define IS3D_SPECTRA_WAVES_KJ16 4     // Grad with 16-point phi blocks (acc in 32 VGPRs)
-#endif
-template <int MODE, int KJ>
-constexpr int spectra_waves_kj() { return (KJ == 16 && MODE == GRAD) ? IS3D_SPECTRA_WAVES_KJ16 : spectra_waves<MODE>(); }
-#ifndef IS3D_WAVES_TS
-#define IS3D_WAVES_TS 0       // F_TS launches: waves per SIMD (0: as the mode's other launches)
-#endif
-// the F_FB launch (separable lanes of a modified mode: per-point exp, RTA-CE-like lane setup) stays at 2
-template <int MODE, int FLAGS, int KJ>
-constexpr int spectra_waves_f() {
-  return (MODE >= PTM && (FLAGS & 32)) ? 2 : (IS3D_WAVES_TS && (FLAGS & 128)) ? IS3D_WAVES_TS : spectra_waves_kj<MODE, KJ>();
-}
+// waves per SIMD of one k_spectra instantiation: the F_FB launch (separable lanes of a modified mode: per-point
+// exp, RTA-CE-like lane setup) stays at 2; F_TS launches run as the mode's other launches
+template <int MODE, int FLAGS>
+constexpr int spectra_waves_f() { return (MODE >= PTM && (FLAGS & 32)) ? 2 : spectra_waves<MODE>(); }
 // k_dndx keeps RTA-CE and the modified modes at 2 (its pT loop holds more live state: 215 VGPRs; it keeps
 // the separable fallback inline)
 template <int MODE>
 constexpr int dndx_waves() { return (MODE == CE || MODE >= PTM) ? 2 : spectra_waves<MODE>(); }
-#ifndef IS3D_DNDX_WAVES_MOD
-#define IS3D_DNDX_WAVES_MOD 2      // k_dndx's modified-lane launch (the separable fallback in its own F_FB launch)
-#endif
-#ifndef IS3D_DNDX_MOD_UNROLL
-#define IS3D_DNDX_MOD_UNROLL 2     // k_dndx modified lanes: phi pairs per loop trip (fully unrolled, 16 at 32 points, the
-                                   // PTM / PTB launch held 256 VGPRs + 95 spilled; two: 129 VGPRs, 3 waves per SIMD)
-#endif
-#ifndef IS3D_DNDX_QUAD
-#define IS3D_DNDX_QUAD 1           // k_dndx lanes in fours (one reciprocal per four points; modified lanes: staged exp).
-                                   // Config 2 operation 0 against pairs: Grad 345 -> 322 ms (168 VGPRs with 15-37
-                                   // spilled -> 124), RTA-CE 506 -> 480, PTM 834 -> 741, PTB 732 -> 660 ms
-                                   // (profiles/round5_r5m_ab_dndx_quad.log)
-#endif
+// k_dndx's modified-lane launch (the separable fallback in its own F_FB launch) has its own waves per SIMD.  Its
+// phi loop runs IS3D_DNDX_MOD_UNROLL fours per trip: fully unrolled (16 pairs at 32 points) the PTM / PTB launch
+// held 256 VGPRs + 95 spilled; two: 129 VGPRs, 3 waves per SIMD
 template <int MODE, int FLAGS>
 constexpr int dndx_waves_f() { return (MODE >= PTM && !(FLAGS & 32)) ? IS3D_DNDX_WAVES_MOD : dndx_waves<MODE>(); }
-#ifndef IS3D_DNDX_TILE_MOD
-#define IS3D_DNDX_TILE_MOD 4       // k_dndx's modified launch: cells per record tile (engine.hip sizes its LDS the same way).
-                                   // 4: ~28 KB of LDS and 126-128 VGPRs, 4 workgroups per CU; config 2 operation 0 against
-                                   // 8-cell tiles (53 KB, 3 per CU): PTM 661 -> 645 ms, PTB 661 -> 640 ms
-                                   // (profiles/round6_r6q_ab_dndx_tile.log)
-#endif
-#ifndef IS3D_DNDX_TILE
-#define IS3D_DNDX_TILE 8           // k_dndx's Grad / RTA-CE launches: cells per record tile
-#endif
-#ifndef IS3D_DNDX_PD
-#define IS3D_DNDX_PD 2             // k_dndx's separable launches with per-(cell, phi) PD = p.dsigma_perp b' rows (k_spectra's
-                                   // PD-table fours: w p.dsigma f_eq = fma(D0, b', escw PD), one op fewer per point); bit 1
-                                   // Grad, bit 2 RTA-CE.  Config 2 operation 0 (profiles/round6_r6v_ab_dndx_pd.log): RTA-CE
-                                   // 485.2 -> 474.7 ms; Grad 317.6 -> 330.3 ms (its Boltzmann-tail pairs become fours): off
-#endif
+// k_dndx's separable launches take per-(cell, phi) PD = p.dsigma_perp b' rows (k_spectra's PD-table fours:
+// w p.dsigma f_eq = fma(D0, b', escw PD), one op fewer per point) for RTA-CE only.  Config 2 operation 0
+// (profiles/round6_r6v_ab_dndx_pd.log): RTA-CE 485.2 -> 474.7 ms; Grad 317.6 -> 330.3 ms (its Boltzmann-tail
+// pairs would become fours), so Grad keeps its pairs
 template <int MODE>
-constexpr bool dndx_pd() { return (MODE == GRAD && (IS3D_DNDX_PD & 1)) || (MODE == CE && (IS3D_DNDX_PD & 2)); }
-#ifndef IS3D_DNDX_PDM
-#define IS3D_DNDX_PDM 1            // k_dndx's modified launch: per-(cell, phi) {PDm, Qv} rows, p.dsigma = fma(Dw, PDm, D0)
-#endif
-// cells per record tile of a k_dndx launch (the F_FB launch keeps kTile)
+constexpr bool dndx_pd() { return MODE == CE; }
+// cells per record tile of a k_dndx launch (the F_FB launch keeps kTile).  Modified launch, 4: ~28 KB of LDS and
+// 126-128 VGPRs, 4 workgroups per CU; config 2 operation 0 against 8-cell tiles (53 KB, 3 per CU): PTM 661 -> 645 ms,
+// PTB 661 -> 640 ms (profiles/round6_r6q_ab_dndx_tile.log)
 template <int MODE, int FLAGS>
 constexpr int dndx_tile() { return (FLAGS & 32) ? kTile : (MODE >= PTM ? IS3D_DNDX_TILE_MOD : IS3D_DNDX_TILE); }
 
@@ -176,136 +186,25 @@ constexpr int F_REG = 1, F_OUT = 2, F_TB = 4, F_LY = 8, F_T8 = 16, F_FB = 32, F_
 constexpr int kTbQ = 4;
 // doubles per F_TS table row of one (cell, pT): {b', Phi}[nphp] | PD[nphp] | RTA-CE {TE, T2}[nphp] | F_BY T3[nphp]
 __host__ __device__ constexpr int phitab_row(int mode, int nphp, bool by = false) { return ((mode == CE ? 5 : 3) + (by ? 1 : 0)) * nphp; }
-#ifndef IS3D_TS
-#define IS3D_TS 1             // F_TB launches with one phi block take the scalar-table form (F_TS)
-#endif
-#ifndef IS3D_TS_BY
-#define IS3D_TS_BY 1          // ... with include_baryon too (F_BY); otherwise the per-lane launch
-#endif
-#ifndef IS3D_PHITAB_ONE
-#define IS3D_PHITAB_ONE (8L << 30)     // F_TS tables up to this size are written and integrated in one chunk
-#endif
-#ifndef IS3D_PHITAB_BYTES
-#define IS3D_PHITAB_BYTES (2L << 30)   // larger ones in chunks of whole cell splits of about this size, alternating
-                                       // over two streams (config 4: 2 GB chunks 2738 ms, 6 GB 2770 ms, one 61 GB
-                                       // chunk 2734 ms; config 2 RTA-CE in one 6.1 GB chunk 249 ms, 2 GB chunks 254 ms)
-#endif
-
-#ifndef IS3D_SPLIT_BYTES
-#define IS3D_SPLIT_BYTES (512L << 10) // record bytes per cell split (k_spectra grid sizing): 0.5 MB (2 MB before round 3:
-                                      // config2 PTM 467 -> 461 ms, PTB 437 -> 431, config4 3194 -> 3180 ms, Grad unchanged;
-                                      // profiles/round3_r3j_ab_split.log; 2 MB for Grad / RTA-CE alone -- a quarter
-                                      // of the slabs -- measured again on the round-3 final kernels: Grad 195 -> 196 ms,
-                                      // RTA-CE 313 -> 321 ms, config4 3153 -> 3175 ms, round3_r3x_ab_split_dndx_tail.log)
-#endif
-#ifndef IS3D_NOPF_MODES
-#define IS3D_NOPF_MODES 0     // bit m: mode m's fours skip the one-quad-ahead prefetch (register-starved builds)
-#endif
-#ifndef IS3D_QUAD_RCP
-#define IS3D_QUAD_RCP 1       // fast path: four phi points per reciprocal where sep_quads() says so
-#endif
-#ifndef IS3D_MOD_PF
-#define IS3D_MOD_PF 0         // modified table fours: one-quad-ahead prefetch of the {PDm, Qv} / T2 rows (helped at
-                              // 2 waves/SIMD; at 3 it does not fit the 168-VGPR budget)
-#endif
-#ifndef IS3D_MOD_QUAD
-#define IS3D_MOD_QUAD 1       // modified path: four phi points per reciprocal when KJ % 4 == 0
-#endif
-#ifndef IS3D_PD_TABLE
-#define IS3D_PD_TABLE 1       // Grad / RTA-CE fast lanes: p.dsigma b' from the per-(cell, phi) PD table (sep_quad_pd_t)
-#endif
-#ifndef IS3D_PD_PREFETCH
-#define IS3D_PD_PREFETCH 0    // PD fours without the one-quad-ahead prefetch (with it Grad spilled 64 VGPRs)
-#endif
-#ifndef IS3D_CS_SCALAR
-#define IS3D_CS_SCALAR 1      // PD fours with one phi block: {pc, ps} by scalar loads (SGPR operands)
-#endif
-#ifndef IS3D_GRAD_TB
-#define IS3D_GRAD_TB 1        // Grad without baryon: the F_TB {PD, T1} table launch (engine.hip)
-#endif
-#ifndef IS3D_CE_TB
-#define IS3D_CE_TB 1          // RTA-CE without baryon also takes the F_TB launch ({PD, T1} + {TE, T2} tables)
-#endif
-#ifndef IS3D_TAIL
-#define IS3D_TAIL 1           // Boltzmann-tail lanes skip the per-point reciprocal (kTailX): Grad F_TB 497 -> 481 ms (r2d)
-#endif
-#ifndef IS3D_TAIL_WAVE
-#define IS3D_TAIL_WAVE 1      // the tail decision per wavefront: a wave mixing tail and other lanes runs one loop
-#endif
-#ifndef IS3D_TAIL_PDL
-#define IS3D_TAIL_PDL 1       // Boltzmann-tail lanes in the per-lane Grad / RTA-CE launches too (sep_quad_pd_tail_t)
-#endif
-#ifndef IS3D_CE_PE
-#define IS3D_CE_PE 1          // RTA-CE per-lane launch: E and the linear delta-f part from a {TE, T2} table (sep_quad_pde_t)
-#endif
-#ifndef IS3D_TAIL_DNDX
-#define IS3D_TAIL_DNDX 1      // operation 0 (k_dndx): Boltzmann-tail Grad lanes in pairs (sep_pair_tail_t)
-#endif
-#ifndef IS3D_TS_PF
-#define IS3D_TS_PF 1          // F_TS: the table rows of tile i + PFD are touched into L2 (LDS-DMA of one dword per 128 B)
-#endif
+// F_TB launches with one phi block take the scalar-table form (F_TS), with include_baryon too (F_BY).
+// How the sizing parameters of these launches (top of this file; the host plan in engine.hip reads them) were chosen:
+// F_TS tables larger than IS3D_PHITAB_ONE are written and integrated in chunks of whole cell splits of about
+// IS3D_PHITAB_BYTES, alternating over two streams (config 4: 2 GB chunks 2738 ms, 6 GB 2770 ms, one 61 GB chunk
+// 2734 ms; config 2 RTA-CE in one 6.1 GB chunk 249 ms, 2 GB chunks 254 ms).
+// IS3D_SPLIT_BYTES, record bytes per cell split: 0.5 MB (2 MB before round 3: config2 PTM 467 -> 461 ms,
+// PTB 437 -> 431, config4 3194 -> 3180 ms, Grad unchanged; profiles/round3_r3j_ab_split.log; 2 MB for Grad / RTA-CE
+// alone -- a quarter of the slabs -- measured again on the round-3 final kernels: Grad 195 -> 196 ms,
+// RTA-CE 313 -> 321 ms, config4 3153 -> 3175 ms, round3_r3x_ab_split_dndx_tail.log).
 // F_TS prefetch distance in tiles (Grad / RTA-CE): one tile of lane work covers the HBM latency, and the nearer tile
 // keeps fewer rows in L2 (12-cell tiles, distance 1 vs 2: config 2 Grad 152.4 / 152.7 ms, RTA-CE 239.4 / 240.6,
-// config 3 RTA-CE 258.4 / 261.5, config 4 2399 / 2435; 3 slower still; profiles/round5_r5j_ab_ts_prefetch.log)
-#ifndef IS3D_TS_PF_DIST_GRAD
-#define IS3D_TS_PF_DIST_GRAD 1
-#endif
-#ifndef IS3D_TS_PF_DIST_CE
-#define IS3D_TS_PF_DIST_CE 1
-#endif
+// config 3 RTA-CE 258.4 / 261.5, config 4 2399 / 2435; 3 slower still; profiles/round5_r5j_ab_ts_prefetch.log).
 // F_TS: the operands of the next four loaded before this four's arithmetic (bit 1 tail lanes, bit 2 other
-// lanes), per mode: RTA-CE 260.8 -> 250.8 ms (config 2), 2663 -> 2511 ms (config 4); Grad 167.5 -> 168.9 ms (r4d)
-#ifndef IS3D_TS_AHEAD_CE
-#define IS3D_TS_AHEAD_CE 1
-#endif
+// lanes), per mode: RTA-CE 260.8 -> 250.8 ms (config 2), 2663 -> 2511 ms (config 4); Grad 167.5 -> 168.9 ms (r4d).
 // Grad without baryon terms ahead on every four since round 5 (12-cell tiles, prefetch distance 1: config 2 Grad
 // 151.9 -> 150.6 ms; the same for RTA-CE and F_BY Grad lost 1-4%: profiles/round5_r5k_ab_tiles_ahead.log)
-#ifndef IS3D_TS_AHEAD_GRAD
-#define IS3D_TS_AHEAD_GRAD 3
-#endif
-#ifndef IS3D_TS_AHEAD_GRAD_BY
-#define IS3D_TS_AHEAD_GRAD_BY 1
-#endif
-#ifndef IS3D_TS_SLOW
-#define IS3D_TS_SLOW 0        // F_TS kernels with the slow-path loop (0: such surfaces take F_TB, sep_slow_cell)
-#endif
-#ifndef IS3D_NEAR
-#define IS3D_NEAR 1           // F_TS Grad: near-tail lanes (sep_quad_tb_near_t, kNearX), no reciprocal per point
-#endif
-#ifndef IS3D_TAIL_PD
-#define IS3D_TAIL_PD 0        // Grad tail lanes: PD table + scalar {pc, ps} instead of {PD, T1}: 2.2% slower (r2d A/B)
-#endif
-#ifndef IS3D_TAIL_CE
-#define IS3D_TAIL_CE 0        // RTA-CE tail lanes (sep_quad_tb_tail_t): 3% slower on MI355X (r2d A/B: 697 vs 675 ms)
-#endif
-// (a modified-path tail loop, mod_quad_tail_t, ran 2.5% fewer VALU ops but 11% slower: r2d, 1445 vs 1297 ms)
-#ifndef IS3D_PIPE
-#define IS3D_PIPE 1           // k_spectra: tables of tile i + 1 built between the lane work of tile i (2 barriers per tile)
-#endif
-#ifndef IS3D_EARLY_SKIP
-// k_spectra tests a lane's overflow skip before its setup, so a wavefront whose lanes all skip a cell branches
-// past the setup: bit 1 separable lanes (sep_skips; config 2 Grad 222.0 -> 215.4 ms, RTA-CE 320.4 -> 317.5 ms),
-// bit 2 modified lanes (mod_skips; round 3: PTM 465.1 -> 471.8 ms, PTMA unchanged, profiles/round3_r3i_ab_skip.log;
-// round 6, on the g-free classes and the table-only modified tiles: PTM 405.9 -> 397.3 ms, PTMA 397.5 -> 391.2 ms,
-// profiles/round6_r6d_ab_tables.log -- on)
-#define IS3D_EARLY_SKIP 3
-#endif
-#ifndef IS3D_PAIR_RCP
-#define IS3D_PAIR_RCP 1       // fast path: two phi points per reciprocal (sep_pair_t)
-#endif
-// timing ablations of k_spectra (wrong results; tools/ab.sh variants only, never a product build): 1 = lanes stop
-// after their setup (no phi loop), 2 = lanes stop before their setup, 3 = modified lanes run the tail fours,
-// 4 = no per-lane cell work at all (tiles, tables, barriers only), 5 = 4 without the per-tile tables
-#ifndef IS3D_ABLATE
-#define IS3D_ABLATE 0
-#endif
-// IS3D_MOD_TABLES (cf_math.h): the modified launch builds only the per-tile tables its lanes read
-// per-tile table loops split their flat index into (cell, row, phi) with a float reciprocal of the runtime row count
-// instead of integer divisions
-#ifndef IS3D_TAB_FDIV
-#define IS3D_TAB_FDIV 1
-#endif
 
+// The modified launch's per-tile table loops split their flat index into (cell, row, phi) with a float reciprocal of
+// the runtime row count instead of integer divisions:
 // q = r / d, m = r % d for 0 <= r < 2^24, d >= 1 (rd = 1 / d in float): float(r) is exact and the float quotient is
 // within (r / d) 2^-23 < 1 of the true one, so one correction step makes it exact
 __device__ __forceinline__ void fdivmod(int r, int d, float rd, int& q, int& m) {
@@ -351,9 +250,6 @@ void launch_phitab(hipStream_t st, const PhiTabArgs& a);
 
 // phi blocks launch_spectra has an instantiation for (the host plan must pick one of these)
 __host__ __device__ constexpr bool spectra_kj_supported(int kj) {
-#ifdef IS3D_KJ16
-  if (kj == 16) return true;
-#endif
   return kj == 32 || kj == 24 || kj == 8 || kj == 2;
 }
 
@@ -368,21 +264,7 @@ template <int MODE, int FLAGS, bool FAST, int KJ, typename ACC>
 __device__ __forceinline__ void sep_phi_loop(const SepLane& L, const dbl2* CS, const dbl2* BP, ACC acc) {
   constexpr int FL = (MODE == GRAD) ? SEP_GRAD : (MODE == CE || MODE == PTM) ? SEP_CE : (MODE == PTB) ? SEP_PTB : SEP_FEQ;
   constexpr bool REG = (FLAGS & F_REG) != 0, OUT = (FLAGS & F_OUT) != 0;
-  if (FAST && IS3D_QUAD_RCP && ((IS3D_NOPF_MODES >> MODE) & 1) && sep_quads(MODE, KJ)) {
-    // fours without the one-quad-ahead prefetch (for register-starved builds)
-#pragma unroll
-    for (int jj = 0; jj < KJ; jj += 4) {
-      dbl2 c[4], b[4];
-#pragma unroll
-      for (int i = 0; i < 4; i++) { c[i] = CS[jj + i]; b[i] = BP[jj + i]; }
-      double v[4];
-      sep_quad_t<FL, REG, OUT>(L, c, b, v);
-#pragma unroll
-      for (int i = 0; i < 4; i++) acc[jj + i] += v[i];
-    }
-    return;
-  }
-  if (FAST && IS3D_QUAD_RCP && sep_quads(MODE, KJ)) {
+  if (FAST && sep_quads(MODE, KJ)) {     // four phi points per reciprocal
     dbl2 c[4], b[4];
 #pragma unroll
     for (int i = 0; i < 4; i++) { c[i] = CS[i]; b[i] = BP[i]; }
@@ -401,7 +283,7 @@ __device__ __forceinline__ void sep_phi_loop(const SepLane& L, const dbl2* CS, c
     }
     return;
   }
-  if (FAST && IS3D_PAIR_RCP) {
+  if (FAST) {                            // two phi points per reciprocal
     dbl2 c0 = CS[0], b0 = BP[0], c1 = CS[1], b1 = BP[1];
 #pragma unroll
     for (int jj = 0; jj < KJ; jj += 2) {   // phi rows are padded to a multiple of KJ
@@ -433,42 +315,22 @@ __device__ __forceinline__ dbl2 cs_at(cs_sptr p, int k) {
   return v;
 }
 
-// sep_phi_loop's fours for fast Grad / RTA-CE lanes with p.dsigma b' from the PD table (sep_quad_pd_t)
+// sep_phi_loop's fours for fast Grad / RTA-CE lanes with p.dsigma b' from the PD table (sep_quad_pd_t); no
+// one-quad-ahead prefetch of the operands (with it Grad spilled 64 VGPRs)
 template <int MODE, int FLAGS, int KJ, bool SC, typename CSP>
 __device__ __forceinline__ void sep_phi_loop_pd(const SepLane& L, CSP CS, const dbl2* BP, const double* PD,
                                                 double* acc) {
   constexpr int FL = (MODE == GRAD) ? SEP_GRAD : (MODE == CE || MODE == PTM) ? SEP_CE : (MODE == PTB) ? SEP_PTB : SEP_FEQ;
   constexpr bool REG = (FLAGS & F_REG) != 0, OUT = (FLAGS & F_OUT) != 0;
-  if (!IS3D_PD_PREFETCH) {
-#pragma unroll
-    for (int jj = 0; jj < KJ; jj += 4) {
-      dbl2 c[4], b[4];
-      double pd[4], v[4];
-#pragma unroll
-      for (int i = 0; i < 4; i++) { c[i] = cs_at(CS, jj + i); b[i] = BP[jj + i]; pd[i] = PD[jj + i]; }
-      sep_quad_pd_t<FL, REG, OUT, SC>(L, c, b, pd, v);
-#pragma unroll
-      for (int i = 0; i < 4; i++) acc[jj + i] += v[i];
-    }
-    return;
-  }
-  dbl2 c[4], b[4];
-  double pd[4];
-#pragma unroll
-  for (int i = 0; i < 4; i++) { c[i] = cs_at(CS, i); b[i] = BP[i]; pd[i] = PD[i]; }
 #pragma unroll
   for (int jj = 0; jj < KJ; jj += 4) {
-    dbl2 nc[4], nb[4];
-    double np[4];
+    dbl2 c[4], b[4];
+    double pd[4], v[4];
 #pragma unroll
-    for (int i = 0; i < 4; i++) {
-      nc[i] = c[i]; nb[i] = b[i]; np[i] = pd[i];
-      if (jj + 4 < KJ) { nc[i] = cs_at(CS, jj + 4 + i); nb[i] = BP[jj + 4 + i]; np[i] = PD[jj + 4 + i]; }
-    }
-    double v[4];
+    for (int i = 0; i < 4; i++) { c[i] = cs_at(CS, jj + i); b[i] = BP[jj + i]; pd[i] = PD[jj + i]; }
     sep_quad_pd_t<FL, REG, OUT, SC>(L, c, b, pd, v);
 #pragma unroll
-    for (int i = 0; i < 4; i++) { acc[jj + i] += v[i]; c[i] = nc[i]; b[i] = nb[i]; pd[i] = np[i]; }
+    for (int i = 0; i < 4; i++) acc[jj + i] += v[i];
   }
 }
 
@@ -606,31 +468,11 @@ __device__ __forceinline__ void sep_phi_loop_pd_tail(const SepLane& L, CSP CS, c
 template <int FLAGS, bool CLAMP, int KJ, typename ACC>
 __device__ __forceinline__ void mod_phi_loop_tab(const ModLane& M, const dbl2* MW, const double* MT, ACC acc) {
   constexpr bool OUT = (FLAGS & F_OUT) != 0;
-  if (IS3D_MOD_QUAD && !IS3D_MOD_PF && KJ % 4 == 0) {
+  if (KJ % 4 == 0) {
+    // no one-quad-ahead prefetch of the table rows: it helped at 2 waves per SIMD; at 3 it does not fit the
+    // 168-VGPR budget
 #pragma unroll
     for (int jj = 0; jj < KJ; jj += 4) mod_quad_tab_t<OUT, CLAMP>(M, MW + jj, MT + jj, acc + jj);
-    return;
-  }
-  if (IS3D_MOD_QUAD && KJ % 4 == 0) {
-    // the next four points' table rows are loaded before the current four are evaluated (at 2 waves per
-    // SIMD the LDS latency is not hidden by other waves)
-    dbl2 mw[4];
-    double mt[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) { mw[i] = MW[i]; mt[i] = MT[i]; }
-#pragma unroll
-    for (int jj = 0; jj < KJ; jj += 4) {
-      dbl2 nw[4];
-      double nt[4];
-#pragma unroll
-      for (int i = 0; i < 4; i++) {
-        nw[i] = mw[i]; nt[i] = mt[i];
-        if (jj + 4 < KJ) { nw[i] = MW[jj + 4 + i]; nt[i] = MT[jj + 4 + i]; }
-      }
-      mod_quad_tab_t<OUT, CLAMP>(M, mw, mt, acc + jj);
-#pragma unroll
-      for (int i = 0; i < 4; i++) { mw[i] = nw[i]; mt[i] = nt[i]; }
-    }
     return;
   }
 #pragma unroll
@@ -661,42 +503,6 @@ __device__ __forceinline__ void mod_phi_loop_lane(const ModLane& M, const dbl2* 
     double v0, v1;
     mod_pair_lane_t<OUT, CLAMP>(M, CS[jj], CS[jj + 1], MW[jj].y, MW[jj + 1].y, v0, v1);
     acc[jj] += v0; acc[jj + 1] += v1;
-  }
-}
-
-template <int FLAGS, bool CLAMP, int KJ>
-__device__ __forceinline__ void mod_phi_loop(const ModLane& M, const dbl2* CS, const dbl2* QV, double* acc) {
-  constexpr bool OUT = (FLAGS & F_OUT) != 0;
-  if (IS3D_MOD_QUAD && KJ % 4 == 0) {
-    dbl2 c[4], qa = QV[0], qb = QV[1];
-#pragma unroll
-    for (int i = 0; i < 4; i++) c[i] = CS[i];
-#pragma unroll
-    for (int jj = 0; jj < KJ; jj += 4) {
-      dbl2 nc[4], na = qa, nb = qb;
-#pragma unroll
-      for (int i = 0; i < 4; i++) {
-        nc[i] = c[i];
-        if (jj + 4 < KJ) nc[i] = CS[jj + 4 + i];
-      }
-      if (jj + 4 < KJ) { na = QV[(jj >> 1) + 2]; nb = QV[(jj >> 1) + 3]; }
-      double v[4];
-      mod_quad_t<OUT, CLAMP>(M, c, qa, qb, v);
-#pragma unroll
-      for (int i = 0; i < 4; i++) { acc[jj + i] += v[i]; c[i] = nc[i]; }
-      qa = na; qb = nb;
-    }
-    return;
-  }
-  dbl2 c0 = CS[0], c1 = CS[1], q = QV[0];
-#pragma unroll
-  for (int jj = 0; jj < KJ; jj += 2) {
-    dbl2 n0 = c0, n1 = c1, nq = q;
-    if (jj + 2 < KJ) { n0 = CS[jj + 2]; n1 = CS[jj + 3]; nq = QV[(jj >> 1) + 1]; }
-    double v0, v1;
-    mod_pair_t<OUT, CLAMP>(M, c0, c1, q, v0, v1);
-    acc[jj] += v0; acc[jj + 1] += v1;
-    c0 = n0; c1 = n1; q = nq;
   }
 }
 
@@ -738,7 +544,7 @@ __device__ __forceinline__ void wait_fetch() { asm volatile("s_waitcnt vmcnt(0)"
 // (species, q, phi block) with q = (y, eta node): in 2+1D the eta nodes are spread over lanes and
 // summed by k_reduce, so a few species still fill the wavefronts
 template <int MODE, int FLAGS, int KJ>
-__global__ __launch_bounds__(kBlock, (spectra_waves_f<MODE, FLAGS, KJ>())) void k_spectra(SpecArgs A) {
+__global__ __launch_bounds__(kBlock, (spectra_waves_f<MODE, FLAGS>())) void k_spectra(SpecArgs A) {
   if (gate_closed(A.gate, A.gate_want)) return;
   constexpr int kTile = spectra_tile<MODE, FLAGS>();      // cells per LDS tile for this mode / launch
   extern __shared__ double smem[];
@@ -750,9 +556,9 @@ __global__ __launch_bounds__(kBlock, (spectra_waves_f<MODE, FLAGS, KJ>())) void 
   constexpr bool MODMAIN = MODE >= PTM && !FB;              // modified launch: separable lanes left to F_FB
   constexpr bool LY = (FLAGS & F_LY) != 0 || FB;
   // Boltzmann-tail lanes of the per-lane Grad / RTA-CE launches (PD-table fours, sep_quad_pd_tail_t)
-  constexpr bool PDT = IS3D_TAIL_PDL && !TB && MODE <= CE && IS3D_PD_TABLE && KJ % 4 == 0;
+  constexpr bool PDT = !TB && MODE <= CE && KJ % 4 == 0;
   // RTA-CE per-lane launch with the per-(cell, phi) {TE, T2} table (one pT per workgroup, workgroup y-term rows)
-  constexpr bool PDE = IS3D_CE_PE && MODE == CE && !TB && (FLAGS & F_MP) == 0 && !LY && IS3D_PD_TABLE && KJ % 4 == 0;
+  constexpr bool PDE = MODE == CE && !TB && (FLAGS & F_MP) == 0 && !LY && KJ % 4 == 0;
   constexpr bool MP = (FLAGS & F_MP) != 0;                  // several pT per workgroup, one phi block per lane
   const int npw = MP ? A.npw : 1;                           // pT values of this launch's workgroups
   // per-(cell, q, phi) tables built from the per-tile tables (phase C below): Grad / RTA-CE {PD, T1},
@@ -762,15 +568,14 @@ __global__ __launch_bounds__(kBlock, (spectra_waves_f<MODE, FLAGS, KJ>())) void 
   // double-buffered.  Only the launches whose tables are small (F_TB: <= kTbQ rows per cell; the modified
   // path's 16-cell tiles, which fall back to F_T8 when they do not fit): double y-term rows of many q
   // values would cost a workgroup per CU (config 1's shape: 4.8 -> 5.7 ms, r2z)
-  constexpr bool PIPE = IS3D_PIPE && (TB || (MODE >= PTM && !(FLAGS & (F_LY | F_T8 | F_FB))));
+  constexpr bool PIPE = (TB || (MODE >= PTM && !(FLAGS & (F_LY | F_T8 | F_FB))));
   constexpr int kRecBufs = PIPE ? 3 : 2, kTabBufs = PIPE ? 2 : 1;
   constexpr int kQvF = (MODE >= PTM || !PIPE) ? 2 : 1;    // doubles per (cell, phi) of s_qv
   const int nqm = A.nqmax;                                // rows per cell (>= every workgroup's nqw)
   const long recsz = (long)kTile * NREC, bpsz = TS ? 0L : (long)npw * kTile * nphp, qvsz = kQvF * bpsz;
   // the {b', Phi} rows: none in F_TS launches, nor in modified launches that build only the tables their lanes read
-  const long bpa = (MODMAIN && IS3D_MOD_TABLES) ? 0L : bpsz;
-  // exp table entries at LDS offset 0: the modified lanes' own table in the modified launches (IS3D_MOD_TAB_BITS)
-  constexpr int kET = MODMAIN ? kModTabN : kExpTabN;
+  const long bpa = MODMAIN ? 0L : bpsz;
+  constexpr int kET = kExpTabN;     // exp table entries at LDS offset 0 (the modified lanes share the table)
   // y-term rows per cell: per row, or per q once the rows cover every q (nyr below): min(nqm, nq);
   // LY launches: one y-term row per lane instead ([kBlock][kYRowLY], single; odd row stride: no conflicts)
   const long ysz = LY ? (long)kBlock * kYRowLY : (long)kTile * min(nqm, A.nq) * kYRow;
@@ -800,7 +605,7 @@ __global__ __launch_bounds__(kBlock, (spectra_waves_f<MODE, FLAGS, KJ>())) void 
   double* s_t1 = (double*)s_pt;
 
   const int tid = threadIdx.x;
-  for (int i = tid; i < kET; i += kBlock) s_etab[i] = MODMAIN ? kModExp2Tab[i] : kExp2Tab[i];
+  for (int i = tid; i < kET; i += kBlock) s_etab[i] = kExp2Tab[i];
   // XCD-aware block order (cdna_hip_programming.md T1): blocks that share an XCD (same
   // blockIdx % 8) take one contiguous range of logical ids, and logical ids run split-major, so
   // each XCD's L2 sees only its own cell splits (sized to fit) instead of every split
@@ -891,7 +696,6 @@ __global__ __launch_bounds__(kBlock, (spectra_waves_f<MODE, FLAGS, KJ>())) void 
   // the modified path's {PDm, Qv}) per (cell, phi), {TE, T2} for RTA-CE's table launch, y-terms per
   // (cell, row)
   auto tables_ab = [&](const double* s_rec, int ntx, int tb) __attribute__((always_inline)) {
-    if (IS3D_ABLATE >= 5) return;
     dbl2* bp = s_bp + tb * bpsz;
     double* qvt = s_qv + tb * qvsz;
     dbl2* mw = (dbl2*)qvt;
@@ -910,10 +714,10 @@ __global__ __launch_bounds__(kBlock, (spectra_waves_f<MODE, FLAGS, KJ>())) void 
       if (j < A.nphi && R[R_KIND] != 0.0) {
         const dbl2 tr = s_trig[j];
         // the modified launch reads only {PDm, Qv}: {b', Phi} serve the separable lanes (the F_FB launch)
-        if constexpr (!(MODMAIN && IS3D_MOD_TABLES)) v = phiterms(MODE, R, pTl, tr.x, tr.y, s_etab);
+        if constexpr (!MODMAIN) v = phiterms(MODE, R, pTl, tr.x, tr.y, s_etab);
         if (MODE >= PTM && R[R_KIND] == 2.0) qv = modqv(R, csj);
       }
-      if constexpr (!(MODMAIN && IS3D_MOD_TABLES)) bp[o] = v;
+      if constexpr (!MODMAIN) bp[o] = v;
       if constexpr (MODE >= PTM) {
         dbl2 m; m.x = modpdm(R, csj); m.y = qv;           // zero rows / padding give 0
         mw[o] = m;
@@ -936,7 +740,7 @@ __global__ __launch_bounds__(kBlock, (spectra_waves_f<MODE, FLAGS, KJ>())) void 
         const double y = s_grid[kk];
         const double eta = (A.dim == 3) ? R[R_ETA] : s_grid[A.nk + l];
         yterms(MODE, A.op, R, y, eta, s_grid[A.nk + A.nl + l], yb + ((long)t * nyr + qq) * kYRow, true,
-               MODMAIN && IS3D_MOD_TABLES);
+               MODMAIN);
       }
     }
   };
@@ -946,16 +750,10 @@ __global__ __launch_bounds__(kBlock, (spectra_waves_f<MODE, FLAGS, KJ>())) void 
   auto tab_index = [&](int idx, int& jj, int& t, int& qq, int& jb, int& qm) __attribute__((always_inline)) {
     jj = idx % KJ;
     const int r = idx / KJ;
-    if (IS3D_TAB_FDIV) {
-      fdivmod(r, nqw, rnqw, t, qq);
-      fdivmod((int)r0 + qq, A.nq, rnq, jb, qm);
-    } else {
-      qq = r % nqw; t = r / nqw;
-      jb = (int)((r0 + qq) / A.nq); qm = (int)((r0 + qq) % A.nq);
-    }
+    fdivmod(r, nqw, rnqw, t, qq);
+    fdivmod((int)r0 + qq, A.nq, rnq, jb, qm);
   };
   auto tables_c = [&](const double* s_rec, int ntx, int tb) __attribute__((always_inline)) {
-    if (IS3D_ABLATE >= 5) return;
     const double* qvt = s_qv + tb * qvsz;
     const double* yb = s_y + tb * ysz;
     if constexpr (MODE >= PTM && !LY) {
@@ -1023,7 +821,7 @@ __global__ __launch_bounds__(kBlock, (spectra_waves_f<MODE, FLAGS, KJ>())) void 
     if (i + kRecBufs - 1 < ntiles) fetch_tile<kTile>(A.rec, tile_cb(i + kRecBufs - 1), c_end, recbuf(i + kRecBufs - 1), fbl);
     constexpr int PFD = (MODE == GRAD) ? IS3D_TS_PF_DIST_GRAD : IS3D_TS_PF_DIST_CE;
     if (i + PFD < ntiles) {
-      if constexpr (TS && IS3D_TS_PF) {
+      if constexpr (TS) {
         // the k_phitab rows of tile i + PFD (contiguous: cells x RW doubles of this pT) into L2, so the scalar loads of
         // its first points miss the K$ into L2 instead of HBM; one dword per 128-byte line, landing in a dummy LDS row
         constexpr int RW = phitab_row(MODE, KJ, (FLAGS & F_BY) != 0);
@@ -1059,7 +857,6 @@ __global__ __launch_bounds__(kBlock, (spectra_waves_f<MODE, FLAGS, KJ>())) void 
       double rn_next = (MODE == PTM && ntx > 0) ? rn_load(0) : 0.0;
       for (int t = 0; t < ntx; t++) {
         const double rn_cell = rn_next;
-        if (IS3D_ABLATE >= 4) { acc[0] += s_rec[t * NREC]; continue; }
         if (MODE == PTM && t + 1 < ntx) rn_next = rn_load(t + 1);
         const double* R = s_rec + t * NREC;
         const double kind = R[R_KIND];
@@ -1087,40 +884,37 @@ __global__ __launch_bounds__(kBlock, (spectra_waves_f<MODE, FLAGS, KJ>())) void 
         if (MODMAIN && sep) continue;
         if (FB && !sep) continue;
         if constexpr (!MODMAIN) {     // Grad / RTA-CE lanes (sep throughout), the F_FB launch's separable lanes
-          if ((IS3D_EARLY_SKIP & 1) && sep_skips(R, Y, mT, pT, baryon)) continue;
-          if (IS3D_ABLATE == 2) { acc[0] += R[R_KIND] * Y[0]; continue; }
+          // the lane's overflow skip before its setup, so a wavefront whose lanes all skip a cell branches past the
+          // setup (config 2 Grad 222.0 -> 215.4 ms, RTA-CE 320.4 -> 317.5 ms)
+          if (sep_skips(R, Y, mT, pT, baryon)) continue;
           SepLane L;
-          // near-tail lanes: F_TS Grad launches without regulate or baryon (IS3D_NEAR: config 2 166.2 -> 162.7 ms;
+          // near-tail lanes: F_TS Grad launches without regulate or baryon (config 2 166.2 -> 162.7 ms;
           // the F_BY launch, config 3, 176.8 -> 179.5 ms: off there)
-          constexpr bool NEAR = TS && MODE == GRAD && !(FLAGS & (F_REG | F_BY)) && IS3D_NEAR && IS3D_TAIL && IS3D_TAIL_WAVE;
+          constexpr bool NEAR = TS && MODE == GRAD && !(FLAGS & (F_REG | F_BY));
+          // Boltzmann-tail lanes skip the per-point reciprocal (kTailX; Grad F_TB 497 -> 481 ms, r2d), decided per
+          // wavefront: a wave mixing tail and other lanes runs one loop.  Not RTA-CE's F_TB launch: its tail fours
+          // were 3% slower (r2d A/B: 697 vs 675 ms)
           sep_setup(sep_flavor(MODE), R, Y, mT, mT2, m2, mTb, pT, sign, baryon, s_etab, L,
-                    ((TB && IS3D_TAIL && (MODE == GRAD || IS3D_TAIL_CE || TS)) || PDT) ? (IS3D_TAIL_WAVE ? 2 : 1) : 0,
-                    NEAR ? 2 : 0);
+                    ((TB && (MODE == GRAD || TS)) || PDT) ? 2 : 0, NEAR ? 2 : 0);
           if (L.skip) continue;
-          if (IS3D_ABLATE == 1) { acc[0] += L.a + L.D0 + L.S0 + L.Sc + L.Ss + L.E0 + L.L0 + L.escw + L.ssc + L.Dc + L.Ds; continue; }
           if constexpr (TS) {
             // this cell's k_phitab row (wave-uniform: ipt, the tile and t are) and the lane's T1 row
             constexpr int RW = phitab_row(MODE, KJ, (FLAGS & F_BY) != 0);   // one phi block: nphp = KJ
             const long go = ((long)ipt * A.phn + (cbx - A.phc0)) * RW + t * RW;
             const dbl2* T1 = (const dbl2*)(s_t1 + ((long)t * nqw + row) * prow2);
-            if (IS3D_TAIL && L.tail) sep_phi_loop_ts<MODE, FLAGS, KJ, true>(L, mT, baryon, (cs_sptr)A.phtab + go, T1, acc);
+            if (L.tail) sep_phi_loop_ts<MODE, FLAGS, KJ, true>(L, mT, baryon, (cs_sptr)A.phtab + go, T1, acc);
             else if (NEAR && L.near) sep_phi_loop_ts<MODE, FLAGS, KJ, false, NEAR>(L, mT, baryon, (cs_sptr)A.phtab + go, T1, acc);
             else if (L.fast) sep_phi_loop_ts<MODE, FLAGS, KJ, false>(L, mT, baryon, (cs_sptr)A.phtab + go, T1, acc);
             // lanes off the fast path never reach F_TS (sep_slow_cell, engine.hip launch_end): their loop, inlined
-            // here, was the kernels' register peak (IS3D_TS_SLOW = 1 keeps it)
-            else if constexpr (IS3D_TS_SLOW) sep_phi_loop<MODE, FLAGS, false, KJ>(L, CSl, (const dbl2*)(A.phtab + go), acc);
+            // here, was the kernels' register peak
             else atomicMax(A.err, (int)DF_TS_SLOW);
           } else if constexpr (TB) {
             const dbl2* PT = s_pt + ((long)t * nqw + row) * prow;
-            if (IS3D_TAIL && L.tail) {
-              if (MODE == GRAD && IS3D_TAIL_PD)
-                sep_phi_loop_pd_tail<MODE, FLAGS, KJ>(L, (cs_sptr)A.csg + 2L * (ipt * nphp + j0), BP, qvt + t * nphp + j0, acc);
-              else
-                sep_phi_loop_tb_tail<MODE, FLAGS, KJ>(L, mT, BP, PT, pet + t * nphp + j0, acc);
-            }
+            // (the tail lanes' PD-table form with scalar {pc, ps} was 2.2% slower for Grad, r2d A/B)
+            if (L.tail) sep_phi_loop_tb_tail<MODE, FLAGS, KJ>(L, mT, BP, PT, pet + t * nphp + j0, acc);
             else if (L.fast) sep_phi_loop_tb<MODE, FLAGS, KJ>(L, mT, BP, PT, pet + t * nphp + j0, acc);
             else sep_phi_loop<MODE, FLAGS, false, KJ>(L, CSl, BP, acc);
-          } else if (IS3D_PD_TABLE && IS3D_CS_SCALAR && !MP && MODE <= CE && KJ % 4 == 0 && L.fast && A.njb == 1) {
+          } else if (!MP && MODE <= CE && KJ % 4 == 0 && L.fast && A.njb == 1) {
             // one phi block: every lane reads the same {pc, ps}, so they come by scalar loads into SGPRs
             // (VALU operands) instead of LDS (not F_MP: a wavefront can straddle two pT blocks)
             if constexpr (PDE) {
@@ -1130,7 +924,7 @@ __global__ __launch_bounds__(kBlock, (spectra_waves_f<MODE, FLAGS, KJ>())) void 
               if (PDT && L.tail) sep_phi_loop_pd_tail<MODE, FLAGS, KJ>(L, (cs_sptr)A.csg + 2L * ipt * nphp, BP, qvt + t * nphp, acc);
               else sep_phi_loop_pd<MODE, FLAGS, KJ, true>(L, (cs_sptr)A.csg + 2L * ipt * nphp, BP, qvt + t * nphp, acc);
             }
-          } else if (IS3D_PD_TABLE && MODE <= CE && KJ % 4 == 0 && L.fast) {
+          } else if (MODE <= CE && KJ % 4 == 0 && L.fast) {
             if constexpr (PDE) {
               if (PDT && L.tail) sep_phi_loop_pde<FLAGS, KJ, true>(L, CSl, BP, qvt + tro, pet + tro, acc);
               else sep_phi_loop_pde<FLAGS, KJ, false>(L, CSl, BP, qvt + tro, pet + tro, acc);
@@ -1143,25 +937,23 @@ __global__ __launch_bounds__(kBlock, (spectra_waves_f<MODE, FLAGS, KJ>())) void 
           else sep_phi_loop<MODE, FLAGS, false, KJ>(L, CSl, BP, acc);
         }
         if constexpr (MODMAIN) {
-          if ((IS3D_EARLY_SKIP & 2) && IS3D_MOD_SQ_BOUNDS && mod_skips(R, Y, mT, m2, pT, baryon, !LY)) continue;
-          if (IS3D_ABLATE == 2) { acc[0] += R[R_KIND] * Y[0]; continue; }
+          // the overflow skip before the lane setup, as above (round 3: PTM 465.1 -> 471.8 ms, PTMA unchanged,
+          // profiles/round3_r3i_ab_skip.log; round 6, on the g-free classes and the table-only modified tiles:
+          // PTM 405.9 -> 397.3 ms, PTMA 397.5 -> 391.2 ms, profiles/round6_r6d_ab_tables.log)
+          if (mod_skips(R, Y, mT, m2, pT, baryon, !LY)) continue;
           ModLane M;
           const dbl2* MW = mwt + t * nphp + j0;
           const double* MT = s_mt + ((long)t * nqw + row) * prow;
           if constexpr (!LY && KJ % 4 == 0) mod_setup<KJ>(R, Y, mT, m2, pT, sign, baryon, rn_abs, s_etab, M, true, true, MW, MT);
           else mod_setup(R, Y, mT, m2, pT, sign, baryon, rn_abs, s_etab, M, !LY, false);
           if (M.skip) continue;
-          if (IS3D_ABLATE == 1) { acc[0] += M.E0 + M.D0 + M.Dw + M.mT + M.shiftk + M.sign + M.tail + M.clamp; continue; }
-          if constexpr (IS3D_ABLATE == 3 && !LY && KJ % 4 == 0) {
-            if (!M.clamp) { mod_phi_loop_tab_tail<FLAGS, KJ>(M, MW, MT, acc); continue; }
-          }
           if constexpr (LY) {        // no T2 rows: the lane's linear forms (mod_pair_lane_t)
             if (M.clamp) mod_phi_loop_lane<FLAGS, true, KJ>(M, CSl, MW, acc);
             else mod_phi_loop_lane<FLAGS, false, KJ>(M, CSl, MW, acc);
             continue;
           }
           if (M.clamp) mod_phi_loop_tab<FLAGS, true, KJ>(M, MW, MT, acc);
-          else if (IS3D_MOD_TAIL && M.tail) mod_phi_loop_tab_tail<FLAGS, KJ>(M, MW, MT, acc);
+          else if (M.tail) mod_phi_loop_tab_tail<FLAGS, KJ>(M, MW, MT, acc);
           else mod_phi_loop_tab<FLAGS, false, KJ>(M, MW, MT, acc);
         }
       }
@@ -1185,8 +977,10 @@ __device__ __forceinline__ double sep_phi_wsum(const SepLane& L, const dbl2* CS,
   constexpr int FL = (MODE == GRAD) ? SEP_GRAD : (MODE == CE || MODE == PTM) ? SEP_CE : (MODE == PTB) ? SEP_PTB : SEP_FEQ;
   constexpr bool REG = (FLAGS & F_REG) != 0, OUT = (FLAGS & F_OUT) != 0;
   double a0 = 0.0, a1 = 0.0;
-  if constexpr (FAST && IS3D_PAIR_RCP && IS3D_DNDX_QUAD && KJ % 4 == 0) {
-    // fours with one reciprocal (sep_quad_t, as k_spectra's lane-form launches)
+  if constexpr (FAST && KJ % 4 == 0) {
+    // fours with one reciprocal (sep_quad_t, as k_spectra's lane-form launches).  Config 2 operation 0 against pairs:
+    // Grad 345 -> 322 ms (168 VGPRs with 15-37 spilled -> 124), RTA-CE 506 -> 480, PTM 834 -> 741, PTB 732 -> 660 ms
+    // (profiles/round5_r5m_ab_dndx_quad.log)
 #pragma unroll
     for (int jj = 0; jj < KJ; jj += 4) {
       const dbl2 c[4] = {CS[jj], CS[jj + 1], CS[jj + 2], CS[jj + 3]}, b[4] = {BP[jj], BP[jj + 1], BP[jj + 2], BP[jj + 3]};
@@ -1198,7 +992,7 @@ __device__ __forceinline__ double sep_phi_wsum(const SepLane& L, const dbl2* CS,
     }
     return a0 + a1;
   }
-  if (FAST && IS3D_PAIR_RCP) {
+  if (FAST) {
     dbl2 c0 = CS[0], b0 = BP[0], c1 = CS[1], b1 = BP[1];
 #pragma unroll
     for (int jj = 0; jj < KJ; jj += 2) {
@@ -1237,7 +1031,7 @@ __device__ __forceinline__ double sep_phi_wsum_tail(const SepLane& L, const dbl2
   return a0 + a1;
 }
 
-// sep_phi_wsum for fast lanes with the per-(cell, phi) PD rows (IS3D_DNDX_PD): sep_quad_pd_t's fours
+// sep_phi_wsum for fast lanes with the per-(cell, phi) PD rows (dndx_pd): sep_quad_pd_t's fours
 template <int MODE, int FLAGS, int KJ>
 __device__ __forceinline__ double sep_phi_wsum_pd(const SepLane& L, const dbl2* CS, const dbl2* BP, const double* PD,
                                                   const dbl2* W) {
@@ -1258,28 +1052,7 @@ __device__ __forceinline__ double sep_phi_wsum_pd(const SepLane& L, const dbl2* 
   return a0 + a1;
 }
 
-// Boltzmann-tail Grad lanes with the PD rows: sep_quad_pd_tail_t's fours (w p.dsigma f_eq in two ops)
-template <int MODE, int FLAGS, int KJ>
-__device__ __forceinline__ double sep_phi_wsum_pd_tail(const SepLane& L, const dbl2* CS, const dbl2* BP, const double* PD,
-                                                       const dbl2* W) {
-  constexpr int FL = (MODE == GRAD) ? SEP_GRAD : SEP_CE;
-  constexpr bool REG = (FLAGS & F_REG) != 0, OUT = (FLAGS & F_OUT) != 0;
-  static_assert(KJ % 4 == 0, "fours");
-  double a0 = 0.0, a1 = 0.0;
-#pragma unroll
-  for (int jj = 0; jj < KJ; jj += 4) {
-    const dbl2 c[4] = {CS[jj], CS[jj + 1], CS[jj + 2], CS[jj + 3]}, b[4] = {BP[jj], BP[jj + 1], BP[jj + 2], BP[jj + 3]};
-    const double pd[4] = {PD[jj], PD[jj + 1], PD[jj + 2], PD[jj + 3]};
-    const dbl2 wa = W[jj >> 1], wb = W[(jj >> 1) + 1];
-    double v[4] = {0.0, 0.0, 0.0, 0.0};
-    sep_quad_pd_tail_t<FL, REG, OUT>(L, c, b, pd, v);
-    a0 = fma(wa.x, v[0], a0); a1 = fma(wa.y, v[1], a1);
-    a0 = fma(wb.x, v[2], a0); a1 = fma(wb.y, v[3], a1);
-  }
-  return a0 + a1;
-}
-
-// mod_phi_wsum with the per-(cell, phi) {PDm, Qv} rows (IS3D_DNDX_PDM): p.dsigma |renorm| = fma(Dw, PDm, D0), one op
+// mod_phi_wsum with the per-(cell, phi) {PDm, Qv} rows: p.dsigma |renorm| = fma(Dw, PDm, D0), one op
 // where the lane's linear form took two (the k_spectra table launch's form; Dw PDm = Dc pc + Ds ps to rounding)
 template <int FLAGS, bool CLAMP, int KJ>
 __device__ __forceinline__ double mod_phi_wsum_mw(const ModLane& M, const dbl2* CS, const dbl2* MW, const dbl2* W) {
@@ -1309,34 +1082,12 @@ __device__ __forceinline__ double mod_phi_wsum_mw(const ModLane& M, const dbl2* 
   return a0 + a1;
 }
 
+// modified lanes of a launch whose phi blocks are no fours (KJ = 2): Qv rows, pairs of points per reciprocal
 template <int FLAGS, bool CLAMP, int KJ>
 __device__ __forceinline__ double mod_phi_wsum(const ModLane& M, const dbl2* CS, const dbl2* QV, const dbl2* W) {
   constexpr bool OUT = (FLAGS & F_OUT) != 0;
   double a0 = 0.0, a1 = 0.0;
-  if constexpr (IS3D_DNDX_QUAD && KJ % 4 == 0) {
-    // fours: the staged table exp of mod_nq4 (four LDS reads per wait) and one reciprocal per four points
-#pragma unroll IS3D_DNDX_MOD_UNROLL
-    for (int jj = 0; jj < KJ; jj += 4) {
-      const dbl2 c[4] = {CS[jj], CS[jj + 1], CS[jj + 2], CS[jj + 3]};
-      const dbl2 qa = QV[jj >> 1], qb = QV[(jj >> 1) + 1], wa = W[jj >> 1], wb = W[(jj >> 1) + 1];
-      const double qv[4] = {qa.x, qa.y, qb.x, qb.y};
-      double X[4], num[4], q[4], rq[4];
-#pragma unroll
-      for (int i = 0; i < 4; i++) X[i] = fma(M.Ec, c[i].x, fma(M.Es, c[i].y, M.E0 + qv[i]));
-      mod_nq4<CLAMP>(M, X, num, q);
-      mod_quad_rq(q, rq);
-      double v[4];
-#pragma unroll
-      for (int i = 0; i < 4; i++) {
-        const double pds = lin(M.D0, M.Dc, M.Ds, c[i]);
-        const double g = pds * (num[i] * rq[i]);
-        v[i] = (OUT && pds <= 0.0) ? 0.0 : g;
-      }
-      a0 = fma(wa.x, v[0], a0); a1 = fma(wa.y, v[1], a1);
-      a0 = fma(wb.x, v[2], a0); a1 = fma(wb.y, v[3], a1);
-    }
-    return a0 + a1;
-  }
+  static_assert(KJ % 4 != 0, "phi blocks of fours take mod_phi_wsum_mw");
   dbl2 c0 = CS[0], c1 = CS[1], q = QV[0];
 #pragma unroll IS3D_DNDX_MOD_UNROLL
   for (int jj = 0; jj < KJ; jj += 2) {
@@ -1375,16 +1126,16 @@ __global__ __launch_bounds__(kBlock, (dndx_waves_f<MODE, FLAGS>())) void k_dndx(
   dbl2* s_cs = s_trig + nphp;                             // [nphp] {pT cos, pT sin} of the current pT
   double* s_w = (double*)(s_cs + nphp);                   // [nphp] phi weights (0 in the padding)
   dbl2* s_bp = (dbl2*)(s_w + nphp);                       // [kTile][nphp] {b', Phi} of the current pT
-  // (none in the modified launch, which builds only the tables its lanes read: IS3D_MOD_TABLES)
-  double* s_qv = (double*)(s_bp + ((MODMAIN && IS3D_MOD_TABLES) ? 0 : kTile * nphp));   // [kTile][nphp] Qv (modified path)
-  // the modified launch's rows are {PDm, Qv} pairs with IS3D_DNDX_PDM
-  constexpr bool MW = MODMAIN && IS3D_DNDX_PDM && KJ % 4 == 0;
+  // (none in the modified launch, which builds only the tables its lanes read)
+  double* s_qv = (double*)(s_bp + (MODMAIN ? 0 : kTile * nphp));   // [kTile][nphp] Qv (modified path)
+  // the modified launch's rows are {PDm, Qv} pairs: p.dsigma = fma(Dw, PDm, D0)
+  constexpr bool MW = MODMAIN && KJ % 4 == 0;
   double* s_red = s_qv + (MW ? 2 : 1) * kTile * nphp;     // [kTile][kBlock] per-lane cell sums
   double* s_grid = s_red + kTile * kBlock;                // y[nk] | eta[nl] | eta_w[nl]
   // y-term rows without the Y_MU2 / Y_MU slots (kYRowLY): two more doubles per row took config 2's Grad
   // launch past the LDS of three workgroups per CU (k_dndx 647 -> 784 ms)
   double* s_y = s_grid + A.nk + 2 * A.nl;                 // [kTile][nq][kYRowLY]
-  constexpr int kET = MODMAIN ? kModTabN : kExpTabN;      // the modified lanes' own table (IS3D_MOD_TAB_BITS)
+  constexpr int kET = kExpTabN;
   double* s_etab = s_y + (long)kTile * A.nq * kYRowLY;    // [kET] 2^(j/kET)
   // PTM: the renormalisation factor of the tile's cells for the workgroup's Sl species, loaded once per tile instead of
   // once per pT (the per-pT loads re-read the [cell][class] array 48 times: 7.3e11 B per config-2 pass); one entry
@@ -1393,7 +1144,7 @@ __global__ __launch_bounds__(kBlock, (dndx_waves_f<MODE, FLAGS>())) void k_dndx(
   double* s_rn = s_etab + kET;                             // [kTile][Sl]
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  for (int i = tid; i < kET; i += kBlock) s_etab[i] = MODMAIN ? kModExp2Tab[i] : kExp2Tab[i];
+  for (int i = tid; i < kET; i += kBlock) s_etab[i] = kExp2Tab[i];
   const long nwg = (long)A.nbx * A.nchunk;
   const long bid = blockIdx.x, q8 = nwg / 8, r8 = nwg % 8, xcd = bid % 8;
   const long lid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + bid / 8;
@@ -1449,7 +1200,7 @@ __global__ __launch_bounds__(kBlock, (dndx_waves_f<MODE, FLAGS>())) void k_dndx(
         const double y = s_grid[ky];
         const double eta = (A.dim == 3) ? R[R_ETA] : s_grid[A.nk + l];
         const double w = s_grid[A.nk + A.nl + l];
-        yterms(MODE, 0, R, y, eta, w, s_y + ((long)t * A.nq + q) * kYRowLY, false, MODMAIN && IS3D_MOD_TABLES);
+        yterms(MODE, 0, R, y, eta, w, s_y + ((long)t * A.nq + q) * kYRowLY, false, MODMAIN);
       }
     }
     for (int ipt = 0; ipt < A.npT; ipt++) {
@@ -1469,13 +1220,13 @@ __global__ __launch_bounds__(kBlock, (dndx_waves_f<MODE, FLAGS>())) void k_dndx(
         if (j < A.nphi && R[R_KIND] != 0.0) {
           const dbl2 tr = s_trig[j];
           // the modified launch reads Qv only ({b', Phi} serve the separable lanes of the F_FB launch)
-          if constexpr (!(MODMAIN && IS3D_MOD_TABLES)) v = phiterms(MODE, R, pT, tr.x, tr.y, s_etab);
+          if constexpr (!MODMAIN) v = phiterms(MODE, R, pT, tr.x, tr.y, s_etab);
           if (MODE >= PTM && R[R_KIND] == 2.0) {
             dbl2 c; c.x = pT * tr.x; c.y = pT * tr.y;
             qv = modqv(R, c);
           }
         }
-        if constexpr (!(MODMAIN && IS3D_MOD_TABLES)) s_bp[t * nphp + j] = v;
+        if constexpr (!MODMAIN) s_bp[t * nphp + j] = v;
         if constexpr (dndx_pd<MODE>() && KJ % 4 == 0) {
           dbl2 c; c.x = pT * s_trig[j].x; c.y = pT * s_trig[j].y;
           s_qv[t * nphp + j] = (j < A.nphi && R[R_KIND] != 0.0) ? sep_pd(R, c, v.x) : 0.0;   // PD rows (sep_pd)
@@ -1514,14 +1265,13 @@ __global__ __launch_bounds__(kBlock, (dndx_waves_f<MODE, FLAGS>())) void k_dndx(
             // Boltzmann-tail lanes of Grad / RTA-CE (decided per wavefront, as in k_spectra)
             // (Grad only: RTA-CE's tail pairs, one 1/E per pair, were slower -- 508 -> 560 ms at config 2 against
             // Grad's 404 -> 333 ms, profiles/round3_r3x_ab_split_dndx_tail.log)
-            constexpr bool TL = IS3D_TAIL_DNDX && MODE == GRAD;
+            constexpr bool TL = MODE == GRAD;
             sep_setup(sep_flavor(MODE), R, Y, mT, mT2, m2, mTb, pT, sign, baryon, s_etab, L, TL ? 2 : 0, 0, true);
             if (L.skip) continue;
             constexpr bool PDL = dndx_pd<MODE>() && KJ % 4 == 0;
             const double* PDr = s_qv + t * nphp + j0;
             if constexpr (PDL) {
-              if (TL && L.tail) cell += sep_phi_wsum_pd_tail<MODE, FLAGS, KJ>(L, s_cs + j0, BP, PDr, W);
-              else if (L.fast) cell += sep_phi_wsum_pd<MODE, FLAGS, KJ>(L, s_cs + j0, BP, PDr, W);
+              if (L.fast) cell += sep_phi_wsum_pd<MODE, FLAGS, KJ>(L, s_cs + j0, BP, PDr, W);
               else cell += sep_phi_wsum<MODE, FLAGS, false, KJ>(L, s_cs + j0, BP, W);
             } else
             if (TL && L.tail) cell += sep_phi_wsum_tail<MODE, FLAGS, KJ>(L, s_cs + j0, BP, W);
@@ -1690,9 +1440,6 @@ void launch_spectra_kj(dim3 grid, size_t shmem, hipStream_t st, const SpecArgs& 
 template <int MODE>
 void launch_spectra(dim3 grid, size_t shmem, hipStream_t st, const SpecArgs& a, int flags, int kj) {
   switch (kj) {
-#ifdef IS3D_KJ16
-    case 16: launch_spectra_kj<MODE, 16>(grid, shmem, st, a, flags); break;
-#endif
     case 32: launch_spectra_kj<MODE, 32>(grid, shmem, st, a, flags); break;
     case 24: launch_spectra_kj<MODE, 24>(grid, shmem, st, a, flags); break;
     case 8: launch_spectra_kj<MODE, 8>(grid, shmem, st, a, flags); break;

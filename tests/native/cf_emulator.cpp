@@ -11,8 +11,6 @@
 #include <cstring>
 #include <vector>
 
-// the modified path's Boltzmann-tail lanes are compiled in (taken only under variant 16)
-#define IS3D_MOD_TAIL 1
 #include "../../is3d2_amd/csrc/aniso_math.h"
 #include "../../is3d2_amd/csrc/cf_math.h"
 #include "../../is3d2_amd/csrc/spline_host.h"
@@ -69,7 +67,7 @@ struct EmuTables {
 // Boltzmann-tail lanes (sep_setup allow_tail + sep_quad_tb_tail_t under bit 1),
 // 4 = the modified path's table form (mod_quad_tab_t / mod_pair_tab_t), 8 = PTMA Newton sums over hadrons
 // merged by identical (mass, sign) with summed degeneracies, first-occurrence order (engine.hip
-// finalize_tables, IS3D_ANISO_MERGE); without it the sums run per hadron in PDG order as the reference
+// finalize_tables); without it the sums run per hadron in PDG order as the reference
 // optional lane census of the separable lanes (tools/lane_census.py): [pT][3] counts of skipped, Boltzmann-tail
 // and other lanes per (cell, species, q)
 static long* g_census = nullptr;
@@ -363,9 +361,9 @@ extern "C" int emu_spectra_v(const orc_params* p, const orc_setup* su, const orc
                 a[j] += sep_point(sep_flavor(mode), L, CS[j], BP[j], p->regulate_deltaf, p->outflow);
             } else {
               ModLane M;
-              // variant 16 (with 4): k_spectra's Boltzmann-tail table lanes (IS3D_MOD_TAIL builds; per lane here)
+              // variant 16 (with 4): k_spectra's Boltzmann-tail table lanes (per lane here)
               const bool mtail = (variant & 20) == 20 && op != 0 && nphi % 4 == 0;
-              // k_spectra's table lanes (variant 4) take the exact range of a wide lane's points (IS3D_MOD_EXACT)
+              // k_spectra's table lanes (variant 4) take the exact range of a wide lane's points (mod_setup<KJ>)
               std::vector<dbl2> MW(nphi);
               std::vector<double> MT(nphi);
               if ((variant & 4) && op != 0) {

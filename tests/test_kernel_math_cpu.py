@@ -246,7 +246,7 @@ def test_modified_table_lanes(mode, baryon):
 
 def test_modified_wide_lanes_exact_range():
     """Modified lanes whose momentum bounds |mT U| -+ pT |V|max span more than 250 binades (high pT, strong
-    modification): mod_setup<KJ> takes the exact range of the lane's points (IS3D_MOD_EXACT), so they run the
+    modification): mod_setup<KJ> takes the exact range of the lane's points, so they run the
     table / Boltzmann-tail fours instead of the clamped en form.  On the config-2 grid the clamped share falls from
     ~5% of the lanes to ~0.1% (tools: /tmp census of round 5); the spectra still meet the oracle."""
     s = synth.as_read(synth.surface(6, seed=31, dimension=3, full3d=True))
