@@ -27,6 +27,7 @@
  *   is3d_set_vorticity                thermal vorticity columns of a mode-5 surface (readindata.cpp:298-306)
  *   is3d_calculate_polarization       calculate_spin_polzn, mode = 5            (Polarization.cpp:25-263,
  *                                                                                EmissionFunction.cpp:1305-1310)
+ *   is3d_sample / is3d_get_particles  sample_dN_pTdpTdphidy, operation = 2      (ParticleSampler.cpp:638-1134)
  *
  * Conventions: caller-owned host buffers in and out; the engine owns its HBM
  * buffers.  Errors are return codes (never exit()); is3d_last_error() gives the
@@ -55,7 +56,7 @@ enum {
 typedef struct is3d_engine is3d_engine;
 
 typedef struct {
-  int operation;                  /* 1 continuous spectra, 0 spacetime distributions, 2 the sampler's yield estimate;
+  int operation;                  /* 1 continuous spectra, 0 spacetime distributions, 2 the particle sampler;
                                      informs the host facade -- each compute entry point fixes its own semantics */
   int dimension;                  /* 2 = boost-invariant (eta quadrature), 3 = 3+1d (y grid) */
   int df_mode;                    /* 1 Grad, 2 RTA-CE, 3 PTM, 4 PTB, 5 PTMA */
@@ -137,6 +138,7 @@ int is3d_set_params(is3d_engine *e, const is3d_params *p);
  *   "max_splits"          cap on k_spectra's cell splits, one output-sized partial slab each (default 1024)
  *   "slab_bytes"          cap on those slabs' memory (default 48 GiB; also at most half the device's free memory)
  *   "split_bytes"         record bytes per cell split the plan aims for (default 512 KiB: a split stays in an XCD's L2)
+ *   "sample_bytes"        bound on the working buffers of one is3d_sample batch of events (default 1 GiB)
  * A negative value restores the default.  is3d_get_tuning also reads "phitab_chunks": the F_TS chunks of the last
  * launch (0: not an F_TS launch), "splits": the cell splits of the last launch, and "slabs": the output-sized partial
  * slabs it held (several 3+1D F_TS chunks fold theirs into one accumulator as they finish: 1 + 2 x splits per chunk);
@@ -286,6 +288,67 @@ int is3d_set_vorticity(is3d_engine *e, long n_cells, const is3d_vorticity *w);
 long is3d_polarization_size(const is3d_engine *e);      /* 5 * is3d_output_size */
 int is3d_calculate_polarization(is3d_engine *e, double T_avg, double *S_out);
 int is3d_launch_polarization(is3d_engine *e, double T_avg, double *dev_out, void *stream);
+
+/* operation = 2, the particle sampler (EmissionFunctionArray::sample_dN_pTdpTdphidy, ParticleSampler.cpp:638-1134):
+ * df_mode 1-4, 2+1D and 3+1D, fast = 0 / 1, with and without baryon diffusion, n_events >= 1 sampled events.
+ * plasma = (T, E, P, muB, nB) averages (is3d_surface_averages), used by fast = 1: the species weights come from the
+ * Plasma-average densities of is3d_total_yield and PTM's breakdown test from the average temperature.  Needs what
+ * is3d_total_yield needs (params, species, df tables, the 32-point Gauss-Laguerre table, a surface); honours
+ * is3d_set_cell_window; a device-list engine samples each shard's window and concatenates the shard lists per event.
+ *
+ * Random numbers: Philox4x32-10; the stream of every draw is a pure function of (seed, purpose, global cell index,
+ * event, candidate index, draw counter) with the reference's four purposes (poisson, type, momentum, rapidity), so
+ * the list is bit-identical for every launch geometry, event batch, cell window split and number of shards -- that
+ * replaces the reference's "same seed, same list" (its serial std::default_random_engine stream is not reproduced).
+ * The engine takes a non-negative seed; the reference's "seed < 0: take the clock" is the host layer's.
+ * The Poisson draw is exact (inversion over equal parts of the mean of at most 16).  The momentum rejection loop and
+ * the Poisson search are capped; a candidate that reaches a cap is dropped and counted in `capped` (0 in practice).
+ *
+ * Output: within an event particles are ordered by (cell, candidate index) -- the reference's loop order -- and
+ * events are contiguous: offsets[n_events + 1].  The list stays in the engine until the next is3d_sample /
+ * is3d_destroy; is3d_sample_count and is3d_sample_offsets read its size, is3d_get_particles copies records
+ * [first, first + count) into caller-owned memory.  `species` is the index into the chosen species (the caller maps
+ * it to an MCID), `cell` the global cell index.
+ *
+ * Memory: the working buffers of one batch of events (12 bytes per (event, cell) plus 204 per candidate) stay below
+ * the "sample_bytes" knob of is3d_set_tuning (default 1 GiB); the batches do not change the result.  One event that
+ * alone exceeds the bound is sampled in batches of cells; a single (cell, event) that exceeds it is an error
+ * (IS3D_ERR_ARG with the size needed), never a truncation.  is3d_get_tuning("sample_batches") is the number of
+ * batches of the last call.
+ *
+ * Not covered: df_mode 5 (sample_dN_pTdpTdphidy_famod): IS3D_ERR_UNSUPPORTED; the test_sampler = 1 binned
+ * results/sampled files.  Errors: IS3D_ERR_STATE for a missing setup step, IS3D_ERR_ARG for n_events < 1,
+ * y_cut <= 0 or a negative seed, IS3D_ERR_DF_RANGE as elsewhere. */
+typedef struct {
+  long seed;                      /* >= 0 */
+  int n_events;                   /* >= 1 */
+  int fast;                       /* 1: species weights from the Plasma-average densities */
+  double y_cut;                   /* 2+1D: rapidity window [-y_cut, y_cut) and volume factor 2 y_cut; 3+1D: unused (> 0) */
+} is3d_sample_params;
+typedef struct {                  /* 96 bytes */
+  int species;
+  int event;
+  long cell;
+  double tau, x, y, eta, t, z, E, px, py, pz;
+} is3d_particle;
+typedef struct {
+  long cells;                     /* cells of the window */
+  long breakdown;                 /* PTM / PTB cells that fall back to the linear delta-f */
+  long candidates;                /* Poisson candidates over all events */
+  long kept;                      /* particles in the list */
+  long proposals, acceptances;    /* momentum rejection loop (the reference prints acceptances / proposals) */
+  long capped;                    /* candidates dropped at an iteration cap (expected 0) */
+  long clamped;                   /* linear delta-f corrections cut to [-1, 1] */
+  long batches;                   /* memory-bound batches the call ran */
+} is3d_sample_stats;
+int is3d_sample(is3d_engine *e, const is3d_sample_params *p, const double *plasma);
+long is3d_sample_count(const is3d_engine *e);
+int is3d_sample_offsets(const is3d_engine *e, long *offsets);
+int is3d_get_particles(const is3d_engine *e, long first, long count, is3d_particle *out);
+int is3d_get_sample_stats(const is3d_engine *e, is3d_sample_stats *out);
+/* Test hook: the first n uniforms in [0, 1) of the stream (seed, purpose 0 poisson / 1 type / 2 momentum /
+ * 3 rapidity, cell, event, candidate), generated on the device (tests compare them with sampler_math.h on the host). */
+int is3d_sample_uniforms(is3d_engine *e, long seed, int purpose, long cell, long event, long candidate, int n, double *out);
 
 #ifdef __cplusplus
 }

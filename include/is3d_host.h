@@ -8,6 +8,8 @@
  *   is3d_host_run_particlization_devices   the same with an explicit device per cell shard
  *   is3d_host_total_yield          IS3D::run_particlization(1) for operation = 2: the oversampling
  *                                  estimate Ntotal / Nevents (EmissionFunction.cpp:1235-1249)
+ *   is3d_host_sample               ... and the sampler: sample_dN_pTdpTdphidy + write_particle_list_OSC
+ *                                  (ParticleSampler.cpp:638-1134, EmissionFunction.cpp:1251-1301, 611-678)
  *   is3d_host_read_surface         FO_data_reader::read_freezeout_surface modes 1/5/6/7 (readindata.cpp:149-731)
  *   is3d_host_read_vorticity       the thermal-vorticity columns of a mode-5 surface    (readindata.cpp:298-306)
  *   is3d_host_polarization         calculate_spin_polzn + write_polzn_vector_toFile     (Polarization.cpp:25-263,
@@ -17,6 +19,7 @@
  */
 #ifndef IS3D_HOST_H
 #define IS3D_HOST_H
+#include "is3d_amd.h"
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -33,9 +36,26 @@ int is3d_host_run_particlization_devices(const char *workdir, const int *devices
                                          long out_capacity, char *err, int errlen);
 /* operation = 2 in <workdir>/iS3D_parameters.dat: n_total = the estimated total yield (0 unless
  * oversample = 1), n_events = min(ceil(min_num_hadrons / Ntotal), max_num_samples) (1 without
- * oversampling).  The particle sampler itself is not on this engine's path. */
+ * oversampling).  Estimate only: nothing is sampled and no file is written, as is3d_host_run_particlization of an
+ * operation = 2 directory; is3d_host_sample samples. */
 int is3d_host_total_yield(const char *workdir, int device, int num_devices, double *n_total, long *n_events,
                           char *err, int errlen);
+/* operation = 2 in <workdir>/iS3D_parameters.dat, df_mode 1-4: the estimate above, then the sampler
+ * (is3d_sample: sample_dN_pTdpTdphidy on the GPU) over Nevents events on HIP devices devices[0..num_devices), with
+ * the run directory's sampler_seed (< 0: the clock, as the reference; *seed receives the seed used), fast and y_cut.
+ * write_files: results/particle_list_osc_<event>.dat for event = 1..Nevents, exactly as write_particle_list_OSC;
+ * write_csv: also results/particle_list_<event>.dat (write_particle_list_toFile).  test_sampler = 1 writes the same
+ * lists: the binned results/sampled files are not produced.  A mode = 5 directory runs the polarization afterwards.
+ * out (optional, capacity records): the engine's records, events contiguous and ordered by (cell, candidate) inside
+ * an event; mcid_out (optional, capacity): each particle's MCID from the chosen table; offsets (optional,
+ * offsets_capacity >= Nevents + 1).  n_particles / n_events / n_total / seed are filled even when the buffers are too
+ * small (IS3D_ERR_ARG "output buffer too small"): with a fixed sampler_seed a second call returns the same list. */
+int is3d_host_sample(const char *workdir, const int *devices, int num_devices, int write_files, int write_csv,
+                     is3d_particle *out, long *mcid_out, long capacity, long *offsets, long offsets_capacity,
+                     long *n_particles, long *n_events, double *n_total, long *seed, char *err, int errlen);
+/* The two writers alone, for a list the caller holds: offsets[n_events + 1], list / mcid / mass per particle. */
+int is3d_host_write_particle_lists(const char *workdir, long n_events, const long *offsets, const is3d_particle *list,
+                                   const long *mcid, const double *mass, int write_csv, char *err, int errlen);
 /* Returns the number of cells (or < 0); fields (optional) receives [25][n] in is3d_surface order,
  * avg5 the Plasma averages T, E, P, muB, nB after the 15-digit round trip. */
 long is3d_host_read_surface(const char *workdir, int mode, int dimension, int include_baryon, double *fields,

@@ -23,7 +23,9 @@ EXPORTS = ["is3d_abi_version", "is3d_build_id", "is3d_create", "is3d_create_devi
            "is3d_calculate_dN_dX", "is3d_get_cell_yields", "is3d_total_yield", "is3d_set_chain_range",
            "is3d_launch_begin", "is3d_chain_passes", "is3d_chain_pass", "is3d_chain_end", "is3d_launch_end",
            "is3d_chain_boundary_size", "is3d_chain_boundary_get", "is3d_chain_boundary_put",
-           "is3d_set_vorticity", "is3d_polarization_size", "is3d_calculate_polarization", "is3d_launch_polarization"]
+           "is3d_set_vorticity", "is3d_polarization_size", "is3d_calculate_polarization", "is3d_launch_polarization",
+           "is3d_sample", "is3d_sample_count", "is3d_sample_offsets", "is3d_get_particles", "is3d_get_sample_stats",
+           "is3d_sample_uniforms"]
 
 VORTICITY_FIELDS = ["wtx", "wty", "wtn", "wxy", "wxn", "wyn"]
 
@@ -53,6 +55,25 @@ class Stats(C.Structure):
     _fields_ = [("cells", C.c_long), ("breakdown", C.c_long), ("pl_negative", C.c_long), ("recon_fail", C.c_long),
                 ("iterations", C.c_long), ("ms_prepass", C.c_double), ("ms_spectra", C.c_double),
                 ("ms_total", C.c_double)]
+
+
+class SampleParams(C.Structure):
+    _fields_ = [("seed", C.c_long), ("n_events", C.c_int), ("fast", C.c_int), ("y_cut", C.c_double)]
+
+
+class Particle(C.Structure):
+    """is3d_particle: the sampler's plain 96-byte record (PARTICLE_DTYPE is its numpy form)."""
+    _fields_ = [("species", C.c_int), ("event", C.c_int), ("cell", C.c_long)] + \
+               [(k, C.c_double) for k in ("tau", "x", "y", "eta", "t", "z", "E", "px", "py", "pz")]
+
+
+PARTICLE_DTYPE = [("species", "<i4"), ("event", "<i4"), ("cell", "<i8")] + \
+                 [(k, "<f8") for k in ("tau", "x", "y", "eta", "t", "z", "E", "px", "py", "pz")]
+
+
+class SampleStats(C.Structure):
+    _fields_ = [(k, C.c_long) for k in ("cells", "breakdown", "candidates", "kept", "proposals", "acceptances",
+                                        "capped", "clamped", "batches")]
 
 
 _lib = None
@@ -121,6 +142,13 @@ def load():
     lib.is3d_polarization_size.argtypes = [C.c_void_p]
     lib.is3d_calculate_polarization.argtypes = [C.c_void_p, d, pd]
     lib.is3d_launch_polarization.argtypes = [C.c_void_p, d, C.c_void_p, C.c_void_p]
+    lib.is3d_sample.argtypes = [C.c_void_p, P(SampleParams), pd]
+    lib.is3d_sample_count.restype = C.c_long
+    lib.is3d_sample_count.argtypes = [C.c_void_p]
+    lib.is3d_sample_offsets.argtypes = [C.c_void_p, P(C.c_long)]
+    lib.is3d_get_particles.argtypes = [C.c_void_p, C.c_long, C.c_long, C.c_void_p]
+    lib.is3d_get_sample_stats.argtypes = [C.c_void_p, P(SampleStats)]
+    lib.is3d_sample_uniforms.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_long, C.c_long, C.c_long, C.c_int, pd]
     _lib = lib
     return lib
 

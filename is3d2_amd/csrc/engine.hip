@@ -41,6 +41,9 @@
                                       // of 0.5 MB of records (44 GB of slabs): 2569 ms per pass, 512 splits 2679 ms,
                                       // 256 splits 2751 ms (profiles/round4_r4a_ab_ts.log)
 #endif
+#ifndef IS3D_SAMPLE_BYTES
+#define IS3D_SAMPLE_BYTES (1L << 30)  // bound on the working buffers of one is3d_sample batch of events
+#endif
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -60,6 +63,7 @@
 #include "kernels.h"
 #include "group.h"
 #include "polzn.h"
+#include "sampler.h"
 
 using namespace is3d;
 using namespace is3d::kern;
@@ -939,6 +943,15 @@ struct is3d_engine {
   bool have_surf = false;    // a surface was set (an empty one set from device memory has no d_surf)
   is3d::polzn::Tables pz;
   bool pz_dirty = true;
+  // particle sampler (operation 2, sampler.hip): species tables in the original order, the "sample_bytes" bound on
+  // a batch's working buffers, and the list / stats of the last is3d_sample
+  is3d::sampler::Tables smp;
+  bool smp_dirty = true;
+  long sample_bytes = IS3D_SAMPLE_BYTES;
+  std::vector<is3d::sampler::Particle> particles;
+  std::vector<long> particle_offsets;
+  is3d_sample_stats sst{};
+  bool sampled = false;
   is3d_stats st{};
   bool launched = false;
 
@@ -1001,6 +1014,7 @@ extern "C" void is3d_destroy(is3d_engine* e) {
   dfree(e->d_err); dfree(e->d_cnt);
   dfree(e->d_vort);
   is3d::polzn::tables_free(e->pz);
+  is3d::sampler::tables_free(e->smp);
   for (auto& v : e->ev) if (v) (void)hipEventDestroy(v);
   delete e;
 }
@@ -1038,6 +1052,7 @@ extern "C" int is3d_set_tuning(is3d_engine* e, const char* key, long value) {
   else if (!std::strcmp(key, "max_splits")) e->max_splits = value <= 0 ? (long)IS3D_MAX_SPLITS : value;
   else if (!std::strcmp(key, "slab_bytes")) e->slab_bytes = value <= 0 ? (long)IS3D_SLAB_BYTES : value;
   else if (!std::strcmp(key, "split_bytes")) e->split_bytes = value <= 0 ? (long)IS3D_SPLIT_BYTES : value;
+  else if (!std::strcmp(key, "sample_bytes")) e->sample_bytes = value <= 0 ? (long)IS3D_SAMPLE_BYTES : value;
   else return e->fail(IS3D_ERR_ARG, std::string("is3d_set_tuning: unknown key ") + key);
   return IS3D_OK;
 }
@@ -1053,13 +1068,15 @@ extern "C" long is3d_get_tuning(const is3d_engine* e, const char* key) {
   if (!std::strcmp(key, "split_bytes")) return e->split_bytes;
   if (!std::strcmp(key, "splits")) return e->last_nsplit;
   if (!std::strcmp(key, "slabs")) return e->last_nslab;
+  if (!std::strcmp(key, "sample_bytes")) return e->sample_bytes;
+  if (!std::strcmp(key, "sample_batches")) return e->sst.batches;
   return -1;
 }
 
 extern "C" int is3d_set_params(is3d_engine* e, const is3d_params* p) {
   if (e && e->grp) return p ? is3d::group_set_params(e->grp, p) : IS3D_ERR_ARG;
   if (!e || !p) return IS3D_ERR_ARG;
-  // operation 2 is accepted for its oversampling estimate (is3d_total_yield); the sampler itself is not on this path
+  // operation 2: the oversampling estimate (is3d_total_yield) and the particle sampler (is3d_sample)
   if (p->operation < 0 || p->operation > 2)
     return e->fail(IS3D_ERR_ARG, "calculate_spectra error: need to set operation = (0, 1, 2)");
   if (p->dimension != 2 && p->dimension != 3) return e->fail(IS3D_ERR_ARG, "EmissionFunctionArray error: need to set dimension = (2,3)");
@@ -1087,6 +1104,7 @@ extern "C" int is3d_set_species(is3d_engine* e, int n, const double* mass, const
   e->have_species = true;
   e->tables_dirty = true;
   e->pz_dirty = true;
+  e->smp_dirty = true;
   return IS3D_OK;
 }
 
@@ -2658,6 +2676,135 @@ extern "C" int is3d_total_yield(is3d_engine* e, const double* plasma, double y_c
   for (long b = 0; b < nb; b++) Ntot += part[b];
   if (e->p.dimension == 2) Ntot *= 2.0 * y_cut;     // :628-631
   *n_total = Ntot;
+  return IS3D_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// operation = 2 particle sampler (ParticleSampler.cpp:638-1134; kernels in sampler.hip)
+// ------------------------------------------------------------------------------------------
+static_assert(sizeof(is3d_particle) == 96 && sizeof(is3d::sampler::Particle) == sizeof(is3d_particle),
+              "is3d_particle is the sampler's 96-byte record");
+
+static int df_fail(is3d_engine* e, int derr) {
+  if (derr == DF_SPLINE_RANGE) return e->fail(IS3D_ERR_DF_RANGE, "gsl: interpolation error (df coefficient spline evaluated out of range)");
+  if (derr == DF_TABLE_RANGE) return e->fail(IS3D_ERR_DF_RANGE, "Error: (T,muB) outside df coefficient table");
+  if (derr == DF_PTB_BARYON) return e->fail(IS3D_ERR_UNSUPPORTED, "Bilinear interpolation error: Jonah df doesn't work for nonzero muB. Exiting..");
+  return e->fail(IS3D_ERR_ARG, "df coefficient error");
+}
+
+// cell_base: global index of this engine's cell 0 (a shard of a device-list engine holds only its window)
+int is3d_internal_sample(is3d_engine* e, const is3d_sample_params* sp, const double* plasma, long cell_base) {
+  if (!e || e->grp) return IS3D_ERR_ARG;
+  e->sampled = false;
+  if (!sp || !plasma) return e->fail(IS3D_ERR_ARG, "is3d_sample: null argument");
+  if (e->have_params && e->p.df_mode == PTMA)
+    return e->fail(IS3D_ERR_UNSUPPORTED, "is3d_sample: the df_mode 5 sampler (sample_dN_pTdpTdphidy_famod) is not built; df_mode 1-4 only");
+  if (sp->n_events < 1) return e->fail(IS3D_ERR_ARG, "is3d_sample: n_events must be >= 1");
+  if (!(sp->y_cut > 0.0)) return e->fail(IS3D_ERR_ARG, "is3d_sample: y_cut must be positive");
+  if (sp->seed < 0) return e->fail(IS3D_ERR_ARG, "is3d_sample: the seed must be non-negative (a negative sampler_seed takes the clock on the host)");
+  int rc = finalize_tables(e);
+  if (rc) return rc;
+  if (!e->have_surf) return e->fail(IS3D_ERR_STATE, "is3d_sample: no surface set");
+  if (!e->have_gla || e->gla_alpha < (sp->fast ? 4 : 3)) return e->fail(IS3D_ERR_STATE, "is3d_set_gauss_laguerre: alpha = 1..3 tables needed");
+  if (e->gla_pts > 64) return e->fail(IS3D_ERR_ARG, "Gauss-Laguerre table longer than 64 points");
+  HIPCHK(e, hipSetDevice(e->device));
+  if (e->smp_dirty) {
+    const std::string m = is3d::sampler::tables_build(e->smp, e->mass, e->sign, e->degen, e->baryon);
+    if (!m.empty()) return e->fail(IS3D_ERR_DEVICE, "is3d_sample: " + m);
+    e->smp_dirty = false;
+  }
+  const int np = (int)e->mass.size();
+  is3d::sampler::Config c;
+  c.run.k = make_consts(e);
+  c.run.fast = sp->fast ? 1 : 0;
+  c.run.y_max = e->p.dimension == 2 ? sp->y_cut : 0.5;
+  c.run.Tavg = plasma[0]; c.run.F_avg = 0.0; c.run.betabulk_avg = 1.0;
+  c.tb = e->dtb; c.surf = e->d_surf; c.n = e->ncell;
+  c.lo = e->win_hi >= 0 ? e->win_lo : 0; c.hi = e->win_hi >= 0 ? e->win_hi : e->ncell;
+  c.cell_base = cell_base; c.seed = (uint64_t)sp->seed; c.n_events = sp->n_events; c.sample_bytes = e->sample_bytes;
+  double* d_dens = nullptr;
+  if (sp->fast) {     // Plasma-average densities (DeltafData.cpp:555-690) and PTM's average df coefficients (:664-673)
+    d_dens = dalloc<double>(3 * (size_t)np);
+    if (!d_dens) return e->fail(IS3D_ERR_DEVICE, "hipMalloc failed");
+    HIPCHK(e, hipMemset(e->d_err, 0, sizeof(int)));
+    DensArgs da{};
+    da.tb = e->dtb; da.gla = e->d_gla; da.gla_alpha = e->gla_alpha; da.gla_pts = e->gla_pts;
+    da.T = plasma[0]; da.E = plasma[1]; da.P = plasma[2]; da.muB = plasma[3]; da.nB = plasma[4];
+    da.smass = e->d_smass; da.ssign = e->d_ssign; da.sdegen = e->d_sdegen; da.sbaryon = e->d_sbaryon; da.sorig = e->d_sorig;
+    da.npart = np; da.df_mode = e->p.df_mode; da.two_pi2_hbarC3 = 2.0 * std::pow(M_PI, 2) * std::pow(kHbarC, 3);
+    da.dens = d_dens; da.err = e->d_err;
+    hipLaunchKernelGGL(k_densities, dim3((unsigned)np), dim3(64), 0, 0, da);
+    hipError_t h = hipGetLastError();
+    if (h == hipSuccess) h = hipDeviceSynchronize();
+    int derr = 0;
+    if (h == hipSuccess) h = hipMemcpy(&derr, e->d_err, sizeof(int), hipMemcpyDeviceToHost);
+    if (h != hipSuccess || derr) dfree(d_dens);
+    if (h != hipSuccess) return hip_fail(e, h, "sampler densities");
+    if (derr) return df_fail(e, derr);
+    if (e->p.df_mode == PTM) {
+      double o[15];
+      rc = is3d_evaluate_df_coefficients(e, plasma[0], plasma[3], 0.0, 0.0, 0.0, o);
+      if (rc) { dfree(d_dens); return rc; }
+      c.run.F_avg = o[6]; c.run.betabulk_avg = o[8];
+    }
+    c.dens = d_dens;
+  }
+  is3d::sampler::Stats st;
+  int derr = 0;
+  std::string msg;
+  const int s = is3d::sampler::run(e->smp, c, e->particles, e->particle_offsets, st, derr, msg);
+  dfree(d_dens);
+  if (s == is3d::sampler::S_DF) return df_fail(e, derr);
+  if (s == is3d::sampler::S_DEVICE) return e->fail(IS3D_ERR_DEVICE, "is3d_sample: " + msg);
+  if (s == is3d::sampler::S_BUDGET) return e->fail(IS3D_ERR_ARG, "is3d_sample: " + msg);
+  e->sst = is3d_sample_stats{st.cells, st.breakdown, st.candidates, st.kept, st.proposals, st.acceptances, st.capped,
+                             st.clamped, st.batches};
+  e->sampled = true;
+  return IS3D_OK;
+}
+
+extern "C" int is3d_sample(is3d_engine* e, const is3d_sample_params* sp, const double* plasma) {
+  if (e && e->grp) return is3d::group_sample(e->grp, sp, plasma);
+  return is3d_internal_sample(e, sp, plasma, 0);
+}
+
+extern "C" long is3d_sample_count(const is3d_engine* e) {
+  if (e && e->grp) return is3d::group_sample_count(e->grp);
+  return (e && e->sampled) ? (long)e->particles.size() : -1;
+}
+
+extern "C" int is3d_sample_offsets(const is3d_engine* e, long* offsets) {
+  if (e && e->grp) return is3d::group_sample_offsets(e->grp, offsets);
+  if (!e || !offsets) return IS3D_ERR_ARG;
+  if (!e->sampled) return IS3D_ERR_STATE;
+  std::copy(e->particle_offsets.begin(), e->particle_offsets.end(), offsets);
+  return IS3D_OK;
+}
+
+extern "C" int is3d_get_particles(const is3d_engine* e, long first, long count, is3d_particle* out) {
+  if (e && e->grp) return is3d::group_get_particles(e->grp, first, count, out);
+  if (!e || (!out && count > 0)) return IS3D_ERR_ARG;
+  if (!e->sampled) return IS3D_ERR_STATE;
+  if (first < 0 || count < 0 || first + count > (long)e->particles.size()) return IS3D_ERR_ARG;
+  if (count > 0) std::memcpy(out, e->particles.data() + first, (size_t)count * sizeof(is3d_particle));
+  return IS3D_OK;
+}
+
+extern "C" int is3d_get_sample_stats(const is3d_engine* e, is3d_sample_stats* out) {
+  if (e && e->grp) return out ? is3d::group_get_sample_stats(e->grp, out) : IS3D_ERR_ARG;
+  if (!e || !out) return IS3D_ERR_ARG;
+  if (!e->sampled) return IS3D_ERR_STATE;
+  *out = e->sst;
+  return IS3D_OK;
+}
+
+extern "C" int is3d_sample_uniforms(is3d_engine* e, long seed, int purpose, long cell, long event, long candidate, int n,
+                                    double* out) {
+  if (e && e->grp) return is3d::group_fail(e->grp, IS3D_ERR_UNSUPPORTED, "is3d_sample_uniforms: a one-device test hook");
+  if (!e || !out || n < 0 || seed < 0 || purpose < 0 || purpose > 3 || cell < 0 || event < 0 || candidate < 0)
+    return e ? e->fail(IS3D_ERR_ARG, "is3d_sample_uniforms: bad argument") : IS3D_ERR_ARG;
+  HIPCHK(e, hipSetDevice(e->device));
+  HIPCHK(e, is3d::sampler::uniforms((uint64_t)seed, purpose, cell, event, candidate, n, out));
   return IS3D_OK;
 }
 

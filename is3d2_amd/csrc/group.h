@@ -53,6 +53,13 @@ int group_get_jonah_table(const Group* g, double* l2, double* z, double* bp, dou
 int group_set_vorticity(Group* g, long n, const is3d_vorticity* w);
 int group_launch_polarization(Group* g, double T_avg, double* dev_out, void* stream);
 int group_calculate_polarization(Group* g, double T_avg, double* S_out);
+// particle sampler (operation 2): every shard samples its own cell window with the global cell indices in its
+// streams; per event the shard lists are concatenated in shard order, which is the one-device list
+int group_sample(Group* g, const is3d_sample_params* p, const double* plasma);
+long group_sample_count(const Group* g);
+int group_sample_offsets(const Group* g, long* offsets);
+int group_get_particles(const Group* g, long first, long count, is3d_particle* out);
+int group_get_sample_stats(const Group* g, is3d_sample_stats* out);
 }  // namespace is3d
 
 // engine.hip internals the group uses on its shard engines (not part of the public ABI)
@@ -66,6 +73,8 @@ int is3d_internal_launch_end(is3d_engine* e);
 int is3d_internal_chain_npass(const is3d_engine* e);
 double* is3d_internal_chain_bnd(is3d_engine* e, int out, int slot);
 long is3d_internal_chain_bnd_bytes(const is3d_engine* e);
+// is3d_sample on a shard whose cell 0 is the surface's cell cell_base
+int is3d_internal_sample(is3d_engine* e, const is3d_sample_params* p, const double* plasma, long cell_base);
 extern "C" {
 // engine-owned copy of cells [lo, lo + n) of a field-major device surface (25 x src_n doubles) on src_device
 int is3d_internal_copy_surface(is3d_engine* e, long n, const double* src, long src_n, int src_device, long lo);

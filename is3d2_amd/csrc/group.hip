@@ -59,6 +59,11 @@ struct Group {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool launched = false;
   is3d_stats stats{};
+  // particle sampler: the merged list of the last group_sample
+  std::vector<is3d_particle> particles;
+  std::vector<long> particle_offsets;
+  is3d_sample_stats sstats{};
+  bool sampled = false;
   std::string err;
   int fail(int code, const std::string& m) { err = m; return code; }
   int shard_fail(int k, int rc) {
@@ -645,6 +650,68 @@ int group_total_yield(Group* g, const double* plasma, double y_cut, double* n_to
   double s = 0.0;
   for (int k = 0; k < K; k++) s += nt[k];
   *n_total = s;
+  return IS3D_OK;
+}
+
+int group_sample(Group* g, const is3d_sample_params* p, const double* plasma) {
+  g->sampled = false;
+  if (!p || !plasma) return g->fail(IS3D_ERR_ARG, "is3d_sample: null argument");
+  if (stale_split(g)) return g->fail(IS3D_ERR_STATE, kStaleSplit);
+  const int K = (int)g->sh.size();
+  // a shard holding the whole surface (PTMA chains: rejected by the shard anyway) samples its window of it
+  const int rc = each_parallel(g, [&](int k) -> int { return is3d_internal_sample(g->sh[k], p, plasma, g->full ? 0 : (k < (int)g->lo.size() ? g->lo[k] : 0)); });
+  if (rc) return rc;
+  const long nev = p->n_events;
+  std::vector<std::vector<long>> off(K, std::vector<long>((size_t)nev + 1, 0));
+  long total = 0;
+  is3d_sample_stats agg{};
+  for (int k = 0; k < K; k++) {
+    is3d_sample_stats s{};
+    int r = is3d_sample_offsets(g->sh[k], off[k].data());
+    if (!r) r = is3d_get_sample_stats(g->sh[k], &s);
+    if (r) return g->shard_fail(k, r);
+    total += off[k][nev];
+    agg.cells += s.cells; agg.breakdown += s.breakdown; agg.candidates += s.candidates; agg.kept += s.kept;
+    agg.proposals += s.proposals; agg.acceptances += s.acceptances; agg.capped += s.capped; agg.clamped += s.clamped;
+    agg.batches += s.batches;
+  }
+  g->particles.resize((size_t)total);
+  g->particle_offsets.assign((size_t)nev + 1, 0);
+  long at = 0;
+  for (long ev = 0; ev < nev; ev++) {
+    g->particle_offsets[ev] = at;
+    for (int k = 0; k < K; k++) {
+      const long n = off[k][ev + 1] - off[k][ev];
+      const int r = is3d_get_particles(g->sh[k], off[k][ev], n, g->particles.data() + at);
+      if (r) return g->shard_fail(k, r);
+      at += n;
+    }
+  }
+  g->particle_offsets[nev] = at;
+  g->sstats = agg;
+  g->sampled = true;
+  return IS3D_OK;
+}
+
+long group_sample_count(const Group* g) { return g->sampled ? (long)g->particles.size() : -1; }
+
+int group_sample_offsets(const Group* g, long* offsets) {
+  if (!offsets) return IS3D_ERR_ARG;
+  if (!g->sampled) return IS3D_ERR_STATE;
+  std::copy(g->particle_offsets.begin(), g->particle_offsets.end(), offsets);
+  return IS3D_OK;
+}
+
+int group_get_particles(const Group* g, long first, long count, is3d_particle* out) {
+  if (!g->sampled) return IS3D_ERR_STATE;
+  if (first < 0 || count < 0 || first + count > (long)g->particles.size() || (!out && count > 0)) return IS3D_ERR_ARG;
+  std::copy(g->particles.begin() + first, g->particles.begin() + first + count, out);
+  return IS3D_OK;
+}
+
+int group_get_sample_stats(const Group* g, is3d_sample_stats* out) {
+  if (!g->sampled) return IS3D_ERR_STATE;
+  *out = g->sstats;
   return IS3D_OK;
 }
 

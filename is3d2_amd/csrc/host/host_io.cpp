@@ -423,6 +423,41 @@ std::string write_polzn_files(const std::string& dir, const PolznView& v) {
   return "";
 }
 
+std::string write_particle_list_osc(const std::string& dir, const std::vector<SampledParticle>& list, const std::vector<long>& offsets) {
+  const std::string out = join(dir, "results");
+  mkdirs(out);
+  for (size_t ev = 0; ev + 1 < offsets.size(); ev++) {
+    const std::string path = out + "/particle_list_osc_" + std::to_string(ev + 1) + ".dat";
+    FILE* f = std::fopen(path.c_str(), "w");
+    if (!f) return "cannot write " + path;
+    std::fprintf(f, "n pid px py pz E m x y z t\n");
+    for (long i = offsets[ev]; i < offsets[ev + 1]; i++) {
+      const SampledParticle& p = list[(size_t)i];
+      std::fprintf(f, "%ld %ld %.16e %.16e %.16e %.16e %.16e %.16e %.16e %.16e %.16e\n", i - offsets[ev], p.mcid, p.px, p.py,
+                   p.pz, p.E, p.mass, p.x, p.y, p.z, p.t);
+    }
+    std::fclose(f);
+  }
+  return "";
+}
+
+std::string write_particle_list_csv(const std::string& dir, const std::vector<SampledParticle>& list, const std::vector<long>& offsets) {
+  const std::string out = join(dir, "results");
+  mkdirs(out);
+  for (size_t ev = 0; ev + 1 < offsets.size(); ev++) {
+    const std::string path = out + "/particle_list_" + std::to_string(ev + 1) + ".dat";
+    FILE* f = std::fopen(path.c_str(), "w");
+    if (!f) return "cannot write " + path;
+    std::fprintf(f, "mcid,tau,x,y,eta,E,px,py,pz\n");
+    for (long i = offsets[ev]; i < offsets[ev + 1]; i++) {
+      const SampledParticle& p = list[(size_t)i];
+      std::fprintf(f, "%5ld,%.8e,%.8e,%.8e,%.8e,%.8e,%.8e,%.8e,%.8e\n", p.mcid, p.tau, p.x, p.y, p.eta, p.E, p.px, p.py, p.pz);
+    }
+    std::fclose(f);
+  }
+  return "";
+}
+
 std::string write_spectra_files(const std::string& dir, const SpectraView& v) {
   const std::string out = join(dir, "results/continuous");
   mkdirs(out);

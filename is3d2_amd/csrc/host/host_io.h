@@ -109,5 +109,15 @@ struct SpacetimeView {
 };
 std::string write_spacetime_files(const std::string& dir, const SpacetimeView& v);
 
+// Sampled particle lists of operation = 2, one file per event (numbered from 1):
+//   write_particle_list_osc  results/particle_list_osc_<event>.dat  (write_particle_list_OSC, EmissionFunction.cpp:645-678)
+//       header "n pid px py pz E m x y z t", rows "index mcid" then the nine values, scientific with 16 digits
+//   write_particle_list_csv  results/particle_list_<event>.dat      (write_particle_list_toFile, :611-642)
+//       header "mcid,tau,x,y,eta,E,px,py,pz", rows: the mcid right-aligned in 5 columns, the values with 8 digits
+// offsets: n_events + 1 positions into the list (events contiguous).
+struct SampledParticle { long mcid; double mass, tau, x, y, eta, t, z, E, px, py, pz; };
+std::string write_particle_list_osc(const std::string& dir, const std::vector<SampledParticle>& list, const std::vector<long>& offsets);
+std::string write_particle_list_csv(const std::string& dir, const std::vector<SampledParticle>& list, const std::vector<long>& offsets);
+
 }  // namespace host
 }  // namespace is3d

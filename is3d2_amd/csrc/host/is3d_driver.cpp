@@ -100,7 +100,7 @@ void EmissionFunctionArray::run_sharded(const RunOptions& opt, int operation) {
   const bool polzn_only = operation < 0;
   if (polzn_only && !((int)p_.get("mode") == 5 && surf_.has_vorticity()))
     throw EngineError(IS3D_ERR_STATE, "polarization needs a mode = 5 surface (thermal vorticity columns)");
-  const is3d_params prm = engine_params(p_, polzn_only ? 1 : operation, dimension_);
+  const is3d_params prm = engine_params(p_, polzn_only ? 1 : std::min(operation, 2), dimension_);
   const is3d_spacetime_bins bins = spacetime_bins(p_);
   const int ndev = opt.devices.empty() ? std::max(1, opt.num_devices) : (int)opt.devices.size();
   std::vector<int> devs(ndev);
@@ -135,6 +135,17 @@ void EmissionFunctionArray::run_sharded(const RunOptions& opt, int operation) {
     } else if (operation == 2) {
       const double plasma[5] = {plasma_.T, plasma_.E, plasma_.P, plasma_.muB, plasma_.nB};
       set_or_throw(e, is3d_total_yield(e, plasma, p_.get("y_cut", 0.5), &ntotal_, nullptr));
+    } else if (operation == 3) {
+      const double plasma[5] = {plasma_.T, plasma_.E, plasma_.P, plasma_.muB, plasma_.nB};
+      is3d_sample_params sp{};
+      sp.seed = sample_seed_; sp.n_events = (int)sample_events_; sp.fast = (int)p_.get("fast", 0.0);
+      sp.y_cut = p_.get("y_cut", 0.5);
+      set_or_throw(e, is3d_sample(e, &sp, plasma));
+      records_.assign((size_t)is3d_sample_count(e), is3d_particle{});
+      sample_offsets_.assign((size_t)sample_events_ + 1, 0);
+      set_or_throw(e, is3d_sample_offsets(e, sample_offsets_.data()));
+      set_or_throw(e, is3d_get_particles(e, 0, (long)records_.size(), records_.data()));
+      set_or_throw(e, is3d_get_sample_stats(e, &sample_stats_));
     } else if (operation == 0) {
       set_or_throw(e, is3d_set_momentum_weights(e, pTw.data(), phiw.data()));
       set_or_throw(e, is3d_set_spacetime_bins(e, &bins));
@@ -169,6 +180,18 @@ double EmissionFunctionArray::estimate_total_yield(const RunOptions& opt) {
 }
 
 void EmissionFunctionArray::calculate_polarization(const RunOptions& opt) { run_sharded(opt, -1); }
+
+void EmissionFunctionArray::sample_particles(const RunOptions& opt, long seed, long n_events) {
+  sample_seed_ = seed;
+  sample_events_ = n_events;
+  run_sharded(opt, 3);
+  sampled_.resize(records_.size());
+  for (size_t i = 0; i < records_.size(); i++) {
+    const is3d_particle& r = records_[i];
+    sampled_[i] = SampledParticle{mcid_[(size_t)r.species], mass_[(size_t)r.species], r.tau, r.x, r.y, r.eta, r.t, r.z,
+                                  r.E, r.px, r.py, r.pz};
+  }
+}
 
 void EmissionFunctionArray::write_polzn_files(const std::string& dir) const {
   const int ny = (dimension_ == 3) ? (int)y_.rows() : 1;
@@ -273,6 +296,31 @@ void IS3D::run_particlization(int fo_from_file, const RunOptions& opt) {
       std::printf("\nSampling 1 particlization event...\n\n");
     }
     dN_.clear();
+    final_particles_.clear(); particle_offsets_.clear(); particle_records_.clear();
+    if (opt.sample) {            // EmissionFunction.cpp:1251-1301: sample, then write the lists
+      // sampler_seed < 0: the clock, as the reference (ParticleSampler.cpp:646-648); the engine sees a seed >= 0
+      seed_ = (long)prm.get("sampler_seed", -1.0);
+      if (seed_ < 0) seed_ = (long)(std::chrono::system_clock::now().time_since_epoch().count() & 0x7fffffffffffffffLL);
+      efa.sample_particles(opt, seed_, nevents_);
+      final_particles_ = efa.sampled();
+      particle_offsets_ = efa.sample_offsets();
+      particle_records_ = efa.sampled_records();
+      sample_stats_ = efa.sample_stats();
+      if (!opt.quiet) {
+        const is3d_sample_stats& st = sample_stats_;
+        std::printf("\nMomentum sampling efficiency = %f %%\n", st.proposals ? 100.0 * (double)st.acceptances / (double)st.proposals : 0.0);
+        std::printf("Sampled %ld particles in %ld events (%ld candidates, %ld dropped at an iteration cap)\n", st.kept, nevents_,
+                    st.candidates, st.capped);
+      }
+      if ((int)prm.get("test_sampler", 0.0) && !opt.quiet)
+        std::printf("test_sampler = 1: the binned results/sampled files are not produced; writing the particle lists\n");
+      if (opt.write_files) {
+        if (!opt.quiet) std::printf("Writing sampled particles list to OSCAR File...\n");
+        std::string werr = write_particle_list_osc(dir_, final_particles_, particle_offsets_);
+        if (werr.empty() && opt.particle_list_csv) werr = write_particle_list_csv(dir_, final_particles_, particle_offsets_);
+        check(werr.empty(), werr);
+      }
+    }
   } else if (operation == 1) {
     efa.calculate_spectra(opt);
     if (opt.write_files) efa.write_files(dir_);
@@ -365,6 +413,57 @@ extern "C" int is3d_host_total_yield(const char* workdir, int device, int num_de
     put_err(err, errlen, ex.what());
     return IS3D_ERR_ARG;
   }
+}
+
+extern "C" int is3d_host_sample(const char* workdir, const int* devices, int num_devices, int write_files, int write_csv,
+                                is3d_particle* out, long* mcid_out, long capacity, long* offsets, long offsets_capacity,
+                                long* n_particles, long* n_events, double* n_total, long* seed, char* err, int errlen) {
+  if (!devices || num_devices <= 0) { put_err(err, errlen, "empty device list"); return IS3D_ERR_ARG; }
+  try {
+    IS3D run(workdir ? workdir : ".");
+    RunOptions opt;
+    opt.devices.assign(devices, devices + num_devices);
+    opt.quiet = true;
+    opt.sample = true;
+    opt.write_files = write_files != 0;
+    opt.particle_list_csv = write_csv != 0;
+    run.run_particlization(1, opt);
+    if (run.particle_offsets().empty()) { put_err(err, errlen, "is3d_host_sample: operation = 2 expected in iS3D_parameters.dat"); return IS3D_ERR_ARG; }
+    const long n = (long)run.final_particles().size(), nev = run.events();
+    if (n_particles) *n_particles = n;
+    if (n_events) *n_events = nev;
+    if (n_total) *n_total = run.total_yield();
+    if (seed) *seed = run.sampler_seed();
+    if ((out && n > capacity) || (offsets && nev + 1 > offsets_capacity)) { put_err(err, errlen, "output buffer too small"); return IS3D_ERR_ARG; }
+    if (out) std::copy(run.particle_records().begin(), run.particle_records().end(), out);
+    if (mcid_out) {
+      if (n > capacity) { put_err(err, errlen, "output buffer too small"); return IS3D_ERR_ARG; }
+      for (long i = 0; i < n; i++) mcid_out[i] = run.final_particles()[(size_t)i].mcid;
+    }
+    if (offsets) std::copy(run.particle_offsets().begin(), run.particle_offsets().end(), offsets);
+    return IS3D_OK;
+  } catch (const EngineError& ex) {
+    put_err(err, errlen, ex.what());
+    return ex.code;
+  } catch (const std::exception& ex) {
+    put_err(err, errlen, ex.what());
+    return IS3D_ERR_ARG;
+  }
+}
+
+extern "C" int is3d_host_write_particle_lists(const char* workdir, long n_events, const long* offsets, const is3d_particle* list,
+                                              const long* mcid, const double* mass, int write_csv, char* err, int errlen) {
+  if (!offsets || n_events < 0 || (offsets[n_events] > 0 && (!list || !mcid || !mass))) { put_err(err, errlen, "bad particle list"); return IS3D_ERR_ARG; }
+  std::vector<long> off(offsets, offsets + n_events + 1);
+  std::vector<SampledParticle> v((size_t)offsets[n_events]);
+  for (size_t i = 0; i < v.size(); i++) {
+    const is3d_particle& r = list[i];
+    v[i] = SampledParticle{mcid[i], mass[i], r.tau, r.x, r.y, r.eta, r.t, r.z, r.E, r.px, r.py, r.pz};
+  }
+  std::string w = write_particle_list_osc(workdir ? workdir : ".", v, off);
+  if (w.empty() && write_csv) w = write_particle_list_csv(workdir ? workdir : ".", v, off);
+  if (!w.empty()) { put_err(err, errlen, w); return IS3D_ERR_ARG; }
+  return IS3D_OK;
 }
 
 extern "C" int is3d_host_polarization(const char* workdir, const int* devices, int num_devices, double* S_out,

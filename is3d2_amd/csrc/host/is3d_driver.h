@@ -7,8 +7,9 @@
 //
 // Same inputs (iS3D_parameters.dat, input/surface.dat, PDG/, deltaf_coefficients/, tables/
 // relative to a working directory) and the same outputs (results/continuous/*.dat).
-// Differences from the reference: errors are returned / thrown instead of exit(); of operation = 2
-// only the oversampling estimate (Ntotal, Nevents) is on this path, not the particle sampler itself;
+// Differences from the reference: errors are returned / thrown instead of exit(); operation = 2 gives the
+// oversampling estimate (Ntotal, Nevents) and, with RunOptions::sample, the sampled particle lists of df_mode 1-4
+// (the engine's counter-based streams, not the reference's serial random engine; no test_sampler binned files);
 // cells may be sharded over several GPUs in one process.
 #pragma once
 #include <string>
@@ -35,6 +36,11 @@ struct RunOptions {
   bool write_files = true;
   bool quiet = false;
   bool polarization_only = false;   // mode = 5: run only calculate_spin_polzn and its writer, not the operation
+  // operation = 2: after the estimate, sample Nevents events (sample_dN_pTdpTdphidy) and write
+  // results/particle_list_osc_<event>.dat; off: the estimate only, no files (is3d_host_total_yield and
+  // is3d_host_run_particlization); the iS3D_amd executable and is3d_host_sample set it
+  bool sample = false;
+  bool particle_list_csv = false;   // also write results/particle_list_<event>.dat (write_particle_list_toFile)
 };
 
 // EmissionFunctionArray(paraRdr, chosen, pT, phi, y, eta, particles, Nparticles, surface, FO_length, df tables)
@@ -58,6 +64,14 @@ class EmissionFunctionArray {
   const std::vector<long>& mcid() const { return mcid_; }
   // operation = 2 oversampling estimate (ParticleSampler.cpp:447-636): the reference's Ntotal
   double estimate_total_yield(const RunOptions& opt);
+  // operation = 2, the sampler (ParticleSampler.cpp:638-1134, df_mode 1-4): n_events events with the given
+  // non-negative seed; sampled() = the list with the chosen table's mcID and mass filled, sample_offsets() its
+  // n_events + 1 event offsets, sampled_records() the engine's records (species index, event, cell)
+  void sample_particles(const RunOptions& opt, long seed, long n_events);
+  const std::vector<SampledParticle>& sampled() const { return sampled_; }
+  const std::vector<is3d_particle>& sampled_records() const { return records_; }
+  const std::vector<long>& sample_offsets() const { return sample_offsets_; }
+  const is3d_sample_stats& sample_stats() const { return sample_stats_; }
   // mode = 5 (EmissionFunction.cpp:1305-1310): calculate_spin_polzn at T = the Plasma average temperature, on an
   // engine of its own that holds only params, species, grid, surface and vorticity.  IS3D::run_particlization calls
   // it after the chosen operation (0, 1 or 2) and after that operation's files are written.
@@ -87,7 +101,12 @@ class EmissionFunctionArray {
   is3d_spacetime_bins bins_{};
   double seconds_ = 0.0;
   double ntotal_ = 0.0;
-  // operation 2: the yield estimate; -1: the polarization alone (an engine without PDG, Gauss-Laguerre and df tables)
+  long sample_seed_ = 0, sample_events_ = 1;
+  std::vector<SampledParticle> sampled_;
+  std::vector<is3d_particle> records_;
+  std::vector<long> sample_offsets_;
+  is3d_sample_stats sample_stats_{};
+  // operation 3: the sampler (engine operation 2); 2: the yield estimate; -1: the polarization alone (an engine without PDG, Gauss-Laguerre and df tables)
   void run_sharded(const RunOptions& opt, int operation);
 };
 
@@ -109,9 +128,16 @@ class IS3D {
   // mode = 5: the raw polarization sums [5][species][pT][phi][y] of the run (empty otherwise)
   const std::vector<double>& polarization() const { return S_; }
   // operation = 2: Ntotal and Nevents = min(ceil(min_num_hadrons / Ntotal), max_num_samples) if
-  // oversample, else 1 (EmissionFunction.cpp:1237-1249); the sampling itself is not on this path
+  // oversample, else 1 (EmissionFunction.cpp:1237-1249)
   double total_yield() const { return ntotal_; }
   long events() const { return nevents_; }
+  // operation = 2 with RunOptions::sample: the sampled list, events contiguous (the reference's final_particles_ /
+  // particle_event_list for in-memory callers), its events() + 1 offsets and the engine's records and stats
+  const std::vector<SampledParticle>& final_particles() const { return final_particles_; }
+  const std::vector<long>& particle_offsets() const { return particle_offsets_; }
+  const std::vector<is3d_particle>& particle_records() const { return particle_records_; }
+  const is3d_sample_stats& sample_stats() const { return sample_stats_; }
+  long sampler_seed() const { return seed_; }
 
  private:
   std::string dir_;
@@ -120,6 +146,11 @@ class IS3D {
   Surface mem_;
   std::vector<double> dN_;
   std::vector<double> S_;
+  std::vector<SampledParticle> final_particles_;
+  std::vector<long> particle_offsets_;
+  std::vector<is3d_particle> particle_records_;
+  is3d_sample_stats sample_stats_{};
+  long seed_ = 0;
 };
 
 }  // namespace host

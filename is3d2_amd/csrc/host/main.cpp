@@ -1,5 +1,6 @@
 // iS3D_amd -- drop-in replacement of the reference executable (src/cpp/Main.cpp) for
-// operations 1 (continuous spectra) and 0 (spacetime distributions): run in a directory laid out
+// operations 1 (continuous spectra), 0 (spacetime distributions) and 2 (the particle sampler, df_mode 1-4: writes
+// results/particle_list_osc_<event>.dat; IS3D_PARTICLE_CSV=1 also results/particle_list_<event>.dat): run in a directory laid out
 // like the reference's (iS3D_parameters.dat,
 // input/surface.dat, PDG/, deltaf_coefficients/, tables/, results/continuous/).
 // Environment: IS3D_DEVICE (first GPU, default 0), IS3D_NUM_GPUS (cells sharded, default 1), or
@@ -45,6 +46,8 @@ int main(int argc, char** argv) {
       opt.devices.push_back((int)v);
     }
   }
+  opt.sample = true;       // operation = 2 samples, as the reference executable does
+  if (const char* c = std::getenv("IS3D_PARTICLE_CSV")) opt.particle_list_csv = std::string(c) == "1";
   try {
     is3d::host::IS3D particlization(argc > 1 ? argv[1] : ".");
     particlization.run_particlization(1, opt);

@@ -1,0 +1,57 @@
+// sampler.h -- private interface between engine.hip and the operation = 2 particle sampler (sampler.hip).
+//
+// The GPU form of EmissionFunctionArray::sample_dN_pTdpTdphidy (ParticleSampler.cpp:638-1134; df_mode 1-4).  The
+// math, the random-number streams and the iteration caps are in sampler_math.h; the engine passes its surface and
+// tables as plain pointers, sampler.hip owns the working buffers of a call and returns the list on the host.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "sampler_math.h"
+
+namespace is3d {
+namespace sampler {
+
+// chosen species in their original order (the species draw follows the reference's discrete_distribution order)
+struct Tables {
+  double* d = nullptr;
+  int npart = 0;
+  const double *mass = nullptr, *sign = nullptr, *degen = nullptr, *baryon = nullptr;
+};
+std::string tables_build(Tables& t, const std::vector<double>& mass, const std::vector<double>& sign,
+                         const std::vector<double>& degen, const std::vector<double>& baryon);
+void tables_free(Tables& t);
+
+struct Config {
+  Run run;
+  DfTables tb;
+  const double* surf = nullptr;    // [25][n] field-major
+  long n = 0, lo = 0, hi = 0;      // cells held and the window [lo, hi) sampled
+  long cell_base = 0;              // global index of held cell 0 (a shard of a device-list engine)
+  uint64_t seed = 0;
+  long n_events = 1;
+  const double* dens = nullptr;    // fast = 1: [3][npart] Plasma-average densities (device)
+  long sample_bytes = 0;           // bound on the working buffers of one batch
+};
+
+struct Stats {
+  long cells = 0, breakdown = 0, candidates = 0, kept = 0, proposals = 0, acceptances = 0, capped = 0, clamped = 0,
+       batches = 0;
+};
+
+enum Status : int { S_OK = 0, S_DEVICE = 1, S_DF = 2, S_BUDGET = 3 };
+
+// Samples n_events events of the window.  parts: kept particles, events contiguous, ordered by (cell, candidate)
+// within an event (the reference's loop order); offsets: n_events + 1.  Returns a Status; S_DF: df_err holds the
+// DfErr; msg says what went wrong otherwise.
+int run(const Tables& t, const Config& c, std::vector<Particle>& parts, std::vector<long>& offsets, Stats& st,
+        int& df_err, std::string& msg);
+
+// test hook: the first n uniforms of stream (seed, purpose, cell, event, candidate), generated on the device
+hipError_t uniforms(uint64_t seed, int purpose, long cell, long event, long candidate, int n, double* host_out);
+
+}  // namespace sampler
+}  // namespace is3d

@@ -85,7 +85,8 @@ class Engine:
 
     def set_tuning(self, key, value):
         """Engine knob (is3d_set_tuning): "phitab_one_bytes" / "phitab_chunk_bytes" (F_TS table chunking),
-        "max_splits" / "slab_bytes" / "split_bytes" (k_spectra's cell splits); a negative value restores the default."""
+        "max_splits" / "slab_bytes" / "split_bytes" (k_spectra's cell splits), "sample_bytes" (the sampler's batch
+        memory bound); a negative value restores the default."""
         self._chk(self.lib.is3d_set_tuning(self._e, key.encode(), int(value)))
 
     def get_tuning(self, key):
@@ -269,6 +270,36 @@ class Engine:
         dens = np.zeros(3 * self.npart)
         self._chk(self.lib.is3d_total_yield(self._e, _dp(pl), float(y_cut), _dp(nt), _dp(dens)))
         return float(nt[0]), dens.reshape(3, self.npart)
+
+    # --- operation = 2: the particle sampler (ParticleSampler.cpp:638-1134) -------------------------------
+    def sample(self, seed, n_events, y_cut=0.5, fast=0, plasma=None):
+        """Sample n_events events (df_mode 1-4).  plasma = (T, E, P, muB, nB) averages (surface_averages).
+        Returns (particles, offsets, stats): a numpy structured array (_lib.PARTICLE_DTYPE: species index, event,
+        global cell, tau x y eta t z E px py pz), events contiguous and ordered by (cell, candidate) inside an
+        event; offsets[n_events + 1]; and the is3d_sample_stats fields as a dict.  The list is a pure function
+        of the seed and the inputs: it does not depend on "sample_bytes" batches, cell windows or devices."""
+        pl = _arr(plasma)
+        sp = _lib.SampleParams(int(seed), int(n_events), int(fast), float(y_cut))
+        self._chk(self.lib.is3d_sample(self._e, C.byref(sp), _dp(pl)))
+        n = self.lib.is3d_sample_count(self._e)
+        parts = np.zeros(max(n, 0), dtype=_lib.PARTICLE_DTYPE)
+        offsets = np.zeros(int(n_events) + 1, dtype=np.int64)
+        self._chk(self.lib.is3d_sample_offsets(self._e, offsets.ctypes.data_as(C.POINTER(C.c_long))))
+        if n > 0:
+            self._chk(self.lib.is3d_get_particles(self._e, 0, n, C.c_void_p(parts.ctypes.data)))
+        return parts, offsets, self.sample_stats()
+
+    def sample_stats(self):
+        s = _lib.SampleStats()
+        self._chk(self.lib.is3d_get_sample_stats(self._e, C.byref(s)))
+        return {k: getattr(s, k) for k, _ in s._fields_}
+
+    def sample_uniforms(self, seed, purpose, cell, event, candidate, n):
+        """Test hook: the first n uniforms of one stream, generated on the device."""
+        out = np.zeros(int(n))
+        self._chk(self.lib.is3d_sample_uniforms(self._e, int(seed), int(purpose), int(cell), int(event),
+                                                int(candidate), int(n), _dp(out)))
+        return out
 
     def jonah_table(self):
         l2, z, bp, mx = np.zeros(301), np.zeros(301), np.zeros(301), np.zeros(1)

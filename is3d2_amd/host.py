@@ -27,6 +27,10 @@ def load():
         lib.is3d_host_read_vorticity.restype = C.c_long
         lib.is3d_host_read_vorticity.argtypes = [C.c_char_p, C.c_int, C.c_int, PD]
         lib.is3d_host_polarization.argtypes = [C.c_char_p, PI, C.c_int, PD, C.c_long, C.c_char_p, C.c_int]
+        lib.is3d_host_sample.argtypes = [C.c_char_p, PI, C.c_int, C.c_int, C.c_int, C.c_void_p, PL, C.c_long, PL, C.c_long,
+                                         PL, PL, PD, PL, C.c_char_p, C.c_int]
+        lib.is3d_host_write_particle_lists.argtypes = [C.c_char_p, C.c_long, PL, C.c_void_p, PL, PD, C.c_int, C.c_char_p,
+                                                       C.c_int]
         _lib = lib
     return _lib
 
@@ -128,3 +132,48 @@ def total_yield(workdir, device=0, num_devices=1):
     if rc:
         raise RuntimeError(err.value.decode())
     return nt.value, ne.value
+
+
+def sample(workdir, devices=(0,), write_files=True, write_csv=False):
+    """operation = 2 run directory (df_mode 1-4): the estimate, then the GPU sampler over Nevents events.  Writes
+    results/particle_list_osc_<event>.dat (and particle_list_<event>.dat with write_csv).  Returns a dict: particles
+    (structured array, _lib.PARTICLE_DTYPE), mcid (per particle), offsets (Nevents + 1), n_total, n_events, seed.
+    The list is sized by a first call that writes nothing, so a clock seed (sampler_seed < 0) is refused here:
+    the second call would sample another list."""
+    from ._lib import PARTICLE_DTYPE
+    lib = load()
+    if param(os.path.join(workdir, "iS3D_parameters.dat"), "sampler_seed") < 0:
+        raise HostError(1, "host.sample needs a fixed sampler_seed >= 0 in iS3D_parameters.dat")
+    dv = np.ascontiguousarray(devices, dtype=np.int32)
+    pdv = dv.ctypes.data_as(C.POINTER(C.c_int))
+    n, nev, nt, seed = C.c_long(), C.c_long(), C.c_double(), C.c_long()
+    err = C.create_string_buffer(512)
+    rc = lib.is3d_host_sample(workdir.encode(), pdv, len(dv), 0, 0, None, None, 0, None, 0, C.byref(n), C.byref(nev),
+                              C.byref(nt), C.byref(seed), err, 512)
+    if rc:
+        raise HostError(rc, err.value.decode())
+    parts = np.zeros(n.value, dtype=PARTICLE_DTYPE)
+    mcid = np.zeros(n.value, dtype=np.int64)
+    off = np.zeros(nev.value + 1, dtype=np.int64)
+    PL = C.POINTER(C.c_long)
+    rc = lib.is3d_host_sample(workdir.encode(), pdv, len(dv), int(write_files), int(write_csv), C.c_void_p(parts.ctypes.data),
+                              mcid.ctypes.data_as(PL), n.value, off.ctypes.data_as(PL), len(off), C.byref(n), C.byref(nev),
+                              C.byref(nt), C.byref(seed), err, 512)
+    if rc:
+        raise HostError(rc, err.value.decode())
+    return dict(particles=parts, mcid=mcid, offsets=off, n_total=nt.value, n_events=nev.value, seed=seed.value)
+
+
+def write_particle_lists(workdir, particles, offsets, mcid, mass, write_csv=True):
+    """The reference's two particle-list writers for a list the caller holds (host_io.cpp write_particle_list_*)."""
+    lib = load()
+    p = np.ascontiguousarray(particles)
+    off = np.ascontiguousarray(offsets, dtype=np.int64)
+    mc = np.ascontiguousarray(mcid, dtype=np.int64)
+    m = np.ascontiguousarray(mass, dtype=np.float64)
+    err = C.create_string_buffer(512)
+    rc = lib.is3d_host_write_particle_lists(workdir.encode(), len(off) - 1, off.ctypes.data_as(C.POINTER(C.c_long)),
+                                            C.c_void_p(p.ctypes.data), mc.ctypes.data_as(C.POINTER(C.c_long)),
+                                            m.ctypes.data_as(C.POINTER(C.c_double)), int(write_csv), err, 512)
+    if rc:
+        raise HostError(rc, err.value.decode())

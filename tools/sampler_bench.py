@@ -1,0 +1,72 @@
+#!/usr/bin/env python
+"""Rate of the particle sampler (operation = 2, is3d_sample) on one GPU, next to the serial CPU emulator of the same
+math (tests/native/sampler_emulator.cpp) on a prefix of the cells.
+
+Shape: BASELINE config-2-like -- 10^5 3+1D cells (synth, full3d), SMASH species, Grad and PTB, fast = 0 and 1, a few
+events.  Each configuration is sampled `warmup` untimed times and `repeats` timed ones; the time is the host wall
+time of Engine.sample: the cell prologue, every batch's kernels and scans, and the copy of the list to the host.
+There is no reference figure: the reference sampler needs GSL.  Prints one JSON line per configuration:
+
+  ms                       median wall time of one is3d_sample call
+  candidates_per_s         Poisson candidates / s
+  accepted_per_s           kept hadrons / s
+  efficiency               momentum rejection loop: acceptances / proposals
+  cpu_candidates_per_s     the serial emulator on the first --cpu-cells cells, one core
+  build_id                 is3d_build_id() of the library measured
+
+    python tools/sampler_bench.py [--cells 100000] [--events 8] [--repeats 3] [--warmup 1] [--cpu-cells 2000]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--cells", type=int, default=100000)
+    ap.add_argument("--events", type=int, default=8)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--cpu-cells", type=int, default=2000)
+    a = ap.parse_args()
+    from is3d2_amd import _lib, build_engine, make_spec, surface_averages, synth
+    s = synth.as_read(synth.surface(a.cells, seed=7, dimension=3, full3d=True))
+    plasma = surface_averages(s, 0)
+    for mode in (1, 4):
+        spec = make_spec(hrg_eos=2, chosen="smash", df_mode=mode, dimension=3)
+        e = build_engine(spec, s, T_avg=plasma[0])
+        for fast in (0, 1):
+            for _ in range(a.warmup):
+                e.sample(1, a.events, 0.5, fast, plasma)
+            ms = []
+            for r in range(a.repeats):
+                t0 = time.perf_counter()
+                p, off, st = e.sample(1, a.events, 0.5, fast, plasma)
+                ms.append(1e3 * (time.perf_counter() - t0))
+            t = float(np.median(ms)) * 1e-3
+            out = dict(df_mode=mode, fast=fast, cells=a.cells, events=a.events, species=len(spec["species"]["mass"]),
+                       ms=round(t * 1e3, 3), ms_all=[round(v, 3) for v in ms], candidates=st["candidates"],
+                       kept=st["kept"], candidates_per_s=st["candidates"] / t, accepted_per_s=st["kept"] / t,
+                       efficiency=st["acceptances"] / max(st["proposals"], 1), capped=st["capped"],
+                       batches=st["batches"], build_id=_lib.build_id())
+            if a.cpu_cells > 0:
+                import sampler_ref as R
+                t0 = time.perf_counter()
+                _, cst, _ = R.sample(spec, s, plasma, 1, a.events, 0.5, fast, 0, min(a.cpu_cells, a.cells))
+                ct = time.perf_counter() - t0
+                out.update(cpu_cells=min(a.cpu_cells, a.cells), cpu_ms=round(ct * 1e3, 3),
+                           cpu_candidates_per_s=cst["candidates"] / ct)
+            print(json.dumps(out), flush=True)
+        e.close()
+
+
+if __name__ == "__main__":
+    main()
