@@ -28,6 +28,8 @@
  *   is3d_calculate_polarization       calculate_spin_polzn, mode = 5            (Polarization.cpp:25-263,
  *                                                                                EmissionFunction.cpp:1305-1310)
  *   is3d_sample / is3d_get_particles  sample_dN_pTdpTdphidy, operation = 2      (ParticleSampler.cpp:638-1134)
+ *   is3d_sample_binned                ... with test_sampler = 1: the binned     (BinSampledParticle.cpp:9-133,
+ *                                     distributions of the kept particles        ParticleSampler.cpp:1112-1121)
  *
  * Conventions: caller-owned host buffers in and out; the engine owns its HBM
  * buffers.  Errors are return codes (never exit()); is3d_last_error() gives the
@@ -316,8 +318,8 @@ int is3d_launch_polarization(is3d_engine *e, double T_avg, double *dev_out, void
  * (IS3D_ERR_ARG with the size needed), never a truncation.  is3d_get_tuning("sample_batches") is the number of
  * batches of the last call.
  *
- * Not covered: df_mode 5 (sample_dN_pTdpTdphidy_famod): IS3D_ERR_UNSUPPORTED; the test_sampler = 1 binned
- * results/sampled files.  Errors: IS3D_ERR_STATE for a missing setup step, IS3D_ERR_ARG for n_events < 1,
+ * Not covered: df_mode 5 (sample_dN_pTdpTdphidy_famod): IS3D_ERR_UNSUPPORTED; bit parity with the reference's serial
+ * random stream.  Errors: IS3D_ERR_STATE for a missing setup step, IS3D_ERR_ARG for n_events < 1,
  * y_cut <= 0 or a negative seed, IS3D_ERR_DF_RANGE as elsewhere. */
 typedef struct {
   long seed;                      /* >= 0 */
@@ -346,6 +348,46 @@ long is3d_sample_count(const is3d_engine *e);
 int is3d_sample_offsets(const is3d_engine *e, long *offsets);
 int is3d_get_particles(const is3d_engine *e, long first, long count, is3d_particle *out);
 int is3d_get_sample_stats(const is3d_engine *e, is3d_sample_stats *out);
+
+/* test_sampler = 1: the sampler bins every kept particle on the device (BinSampledParticle.cpp:9-133) instead of --
+ * keep_list = 0 -- or next to -- keep_list = 1 -- listing it.  is3d_set_sample_bins takes the reference's bin
+ * parameters (widths as EmissionFunction.cpp:223-247: (max - min) / bins, 2 cut / bins, 2 pi / bins); y_cut is the
+ * binning window of dN_dy (in 2+1D pass the sampler's y_cut).  A particle outside a histogram's range is dropped from
+ * that histogram only.  Rapidity is 0.5 log((E + pz) / (E - pz)) in 3+1D and the drawn rapidity in 2+1D; eta is the
+ * particle record's.
+ *
+ * is3d_sample_binned samples like is3d_sample (same arguments, streams, cell window, device list, errors) and leaves
+ * the histograms in the engine until the next sampling call:
+ *   counts  one block of n_counts integers, each part [npart][bins] in chosen-species order:
+ *           dN_dy | dN_deta | dN_dphipdy | pT | tau | r | phis          (the pT part is both dN_2pipTdpTdy_count
+ *           and pT_count of the reference; phis uses phip_bins)
+ *   vn      n_vn = 2 x 7 x npart x pT_bins doubles, [2][7][npart][pT_bins]: the sums of cos(k phi), then of sin(k phi),
+ *           k = 1..7, over the particles of a pT bin.  Raw sums: the normalisation belongs to the writer.
+ * The counts are exact.  The vn sums are accumulated in fixed point -- every term rounded to a multiple of
+ * q = 2^-32 and added as a 64-bit integer, converted to double once -- so they carry at most q / 2 per particle and,
+ * like the counts, are bit-identical for every event batch, cell batch, cell window split, launch geometry and number
+ * of shards (a device-list engine adds its shards' integer histograms).  A bin holds up to 2^31 particles.
+ *
+ * keep_list = 0: no candidate slots, no compaction, no list -- a batch needs 12 bytes per (event, cell) whatever the
+ * number of candidates, so no (cell, event) can exceed "sample_bytes"; is3d_sample_count is 0, the offsets are 0 and
+ * is3d_get_sample_stats holds the true candidates, kept, ... and batches.  keep_list = 1: the list entry points
+ * behave exactly as after is3d_sample with the same arguments.
+ *
+ * Errors: IS3D_ERR_STATE when no bins are set; is3d_set_sample_bins: IS3D_ERR_ARG for a bin count < 1, a max <= min or
+ * a cut <= 0; IS3D_ERR_UNSUPPORTED for df_mode 5; otherwise what is3d_sample returns.  is3d_sample_hist_size returns
+ * n_counts + n_vn (either pointer may be null), -1 before the bins and the species are set. */
+typedef struct {
+  double pT_min, pT_max;   int pT_bins;
+  double y_cut;            int y_bins;
+  int phip_bins;
+  double eta_cut;          int eta_bins;
+  double tau_min, tau_max; int tau_bins;
+  double r_min, r_max;     int r_bins;
+} is3d_sample_bins;
+int is3d_set_sample_bins(is3d_engine *e, const is3d_sample_bins *b);
+int is3d_sample_binned(is3d_engine *e, const is3d_sample_params *p, const double *plasma, int keep_list);
+long is3d_sample_hist_size(const is3d_engine *e, long *n_counts, long *n_vn);
+int is3d_get_sample_hist(const is3d_engine *e, long *counts, double *vn);
 /* Test hook: the first n uniforms in [0, 1) of the stream (seed, purpose 0 poisson / 1 type / 2 momentum /
  * 3 rapidity, cell, event, candidate), generated on the device (tests compare them with sampler_math.h on the host). */
 int is3d_sample_uniforms(is3d_engine *e, long seed, int purpose, long cell, long event, long candidate, int n, double *out);

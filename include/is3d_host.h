@@ -10,6 +10,8 @@
  *                                  estimate Ntotal / Nevents (EmissionFunction.cpp:1235-1249)
  *   is3d_host_sample               ... and the sampler: sample_dN_pTdpTdphidy + write_particle_list_OSC
  *                                  (ParticleSampler.cpp:638-1134, EmissionFunction.cpp:1251-1301, 611-678)
+ *   is3d_host_sample_binned        ... with test_sampler = 1: the binned distributions and the results/sampled
+ *                                  files instead of the lists (BinSampledParticle.cpp, EmissionFunction.cpp:685-975)
  *   is3d_host_read_surface         FO_data_reader::read_freezeout_surface modes 1/5/6/7 (readindata.cpp:149-731)
  *   is3d_host_read_vorticity       the thermal-vorticity columns of a mode-5 surface    (readindata.cpp:298-306)
  *   is3d_host_polarization         calculate_spin_polzn + write_polzn_vector_toFile     (Polarization.cpp:25-263,
@@ -44,8 +46,10 @@ int is3d_host_total_yield(const char *workdir, int device, int num_devices, doub
  * (is3d_sample: sample_dN_pTdpTdphidy on the GPU) over Nevents events on HIP devices devices[0..num_devices), with
  * the run directory's sampler_seed (< 0: the clock, as the reference; *seed receives the seed used), fast and y_cut.
  * write_files: results/particle_list_osc_<event>.dat for event = 1..Nevents, exactly as write_particle_list_OSC;
- * write_csv: also results/particle_list_<event>.dat (write_particle_list_toFile).  test_sampler = 1 writes the same
- * lists: the binned results/sampled files are not produced.  A mode = 5 directory runs the polarization afterwards.
+ * write_csv: also results/particle_list_<event>.dat (write_particle_list_toFile).  test_sampler = 1: the particles
+ * are binned on the device and never listed, as in the reference (EmissionFunction.cpp:1279-1291) -- write_files
+ * writes the results/sampled tree and no particle list, n_particles is 0 and the offsets are 0; is3d_host_sample_binned
+ * also returns the histograms.  A mode = 5 directory runs the polarization afterwards.
  * out (optional, capacity records): the engine's records, events contiguous and ordered by (cell, candidate) inside
  * an event; mcid_out (optional, capacity): each particle's MCID from the chosen table; offsets (optional,
  * offsets_capacity >= Nevents + 1).  n_particles / n_events / n_total / seed are filled even when the buffers are too
@@ -53,6 +57,16 @@ int is3d_host_total_yield(const char *workdir, int device, int num_devices, doub
 int is3d_host_sample(const char *workdir, const int *devices, int num_devices, int write_files, int write_csv,
                      is3d_particle *out, long *mcid_out, long capacity, long *offsets, long offsets_capacity,
                      long *n_particles, long *n_events, double *n_total, long *seed, char *err, int errlen);
+/* operation = 2 and test_sampler = 1 in <workdir>/iS3D_parameters.dat: as is3d_host_sample, with every kept particle
+ * binned on the device (is3d_sample_binned, keep_list = 0) with the parameter file's pT / y / phip / eta / tau / r bins.
+ * write_files: the results/sampled tree of write_sampled_*_to_file_test (EmissionFunction.cpp:685-975), nine files per
+ * species, sub-directories created when missing; no particle list.  counts / vn (optional): is3d_get_sample_hist's
+ * arrays; is3d_host_sample_hist_size gives their sizes, the bins and the number of chosen species from the run
+ * directory alone (returns 0, or -1 when the parameter file or PDG/chosen_particles.dat cannot be read). */
+int is3d_host_sample_hist_size(const char *workdir, is3d_sample_bins *bins, int *npart, long *n_counts, long *n_vn);
+int is3d_host_sample_binned(const char *workdir, const int *devices, int num_devices, int write_files, long *counts,
+                            long counts_capacity, double *vn, long vn_capacity, long *n_events, double *n_total,
+                            long *seed, is3d_sample_stats *stats, char *err, int errlen);
 /* The two writers alone, for a list the caller holds: offsets[n_events + 1], list / mcid / mass per particle. */
 int is3d_host_write_particle_lists(const char *workdir, long n_events, const long *offsets, const is3d_particle *list,
                                    const long *mcid, const double *mass, int write_csv, char *err, int errlen);

@@ -25,7 +25,8 @@ EXPORTS = ["is3d_abi_version", "is3d_build_id", "is3d_create", "is3d_create_devi
            "is3d_chain_boundary_size", "is3d_chain_boundary_get", "is3d_chain_boundary_put",
            "is3d_set_vorticity", "is3d_polarization_size", "is3d_calculate_polarization", "is3d_launch_polarization",
            "is3d_sample", "is3d_sample_count", "is3d_sample_offsets", "is3d_get_particles", "is3d_get_sample_stats",
-           "is3d_sample_uniforms"]
+           "is3d_sample_uniforms", "is3d_set_sample_bins", "is3d_sample_binned", "is3d_sample_hist_size",
+           "is3d_get_sample_hist"]
 
 VORTICITY_FIELDS = ["wtx", "wty", "wtn", "wxy", "wxn", "wyn"]
 
@@ -74,6 +75,19 @@ PARTICLE_DTYPE = [("species", "<i4"), ("event", "<i4"), ("cell", "<i8")] + \
 class SampleStats(C.Structure):
     _fields_ = [(k, C.c_long) for k in ("cells", "breakdown", "candidates", "kept", "proposals", "acceptances",
                                         "capped", "clamped", "batches")]
+
+
+class SampleBins(C.Structure):
+    """is3d_sample_bins: the test_sampler = 1 bin parameters (SAMPLE_BIN_PARTS: the count parts in layout order)."""
+    _fields_ = [("pT_min", C.c_double), ("pT_max", C.c_double), ("pT_bins", C.c_int), ("y_cut", C.c_double),
+                ("y_bins", C.c_int), ("phip_bins", C.c_int), ("eta_cut", C.c_double), ("eta_bins", C.c_int),
+                ("tau_min", C.c_double), ("tau_max", C.c_double), ("tau_bins", C.c_int),
+                ("r_min", C.c_double), ("r_max", C.c_double), ("r_bins", C.c_int)]
+
+
+# (name in Engine.sample_binned's dict, the bins field that sizes it)
+SAMPLE_BIN_PARTS = [("dN_dy", "y_bins"), ("dN_deta", "eta_bins"), ("dN_dphipdy", "phip_bins"), ("pT_count", "pT_bins"),
+                    ("dN_taudtaudy", "tau_bins"), ("dN_2pirdrdy", "r_bins"), ("dN_dphisdy", "phip_bins")]
 
 
 _lib = None
@@ -149,6 +163,11 @@ def load():
     lib.is3d_get_particles.argtypes = [C.c_void_p, C.c_long, C.c_long, C.c_void_p]
     lib.is3d_get_sample_stats.argtypes = [C.c_void_p, P(SampleStats)]
     lib.is3d_sample_uniforms.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_long, C.c_long, C.c_long, C.c_int, pd]
+    lib.is3d_set_sample_bins.argtypes = [C.c_void_p, P(SampleBins)]
+    lib.is3d_sample_binned.argtypes = [C.c_void_p, P(SampleParams), pd, C.c_int]
+    lib.is3d_sample_hist_size.restype = C.c_long
+    lib.is3d_sample_hist_size.argtypes = [C.c_void_p, P(C.c_long), P(C.c_long)]
+    lib.is3d_get_sample_hist.argtypes = [C.c_void_p, P(C.c_long), pd]
     _lib = lib
     return lib
 

@@ -952,6 +952,14 @@ struct is3d_engine {
   std::vector<long> particle_offsets;
   is3d_sample_stats sst{};
   bool sampled = false;
+  // test_sampler = 1: the bins, the device histogram of a binned call (zeroed at its start) and its host copy in
+  // integer form (hist_nc counts, then hist_nv fixed-point vn sums)
+  is3d_sample_bins sbins{};
+  bool have_sbins = false;
+  unsigned long long* d_hist = nullptr; long hist_cap = 0;
+  std::vector<long long> hist;
+  long hist_nc = 0, hist_nv = 0;
+  bool binned = false;
   is3d_stats st{};
   bool launched = false;
 
@@ -1013,6 +1021,7 @@ extern "C" void is3d_destroy(is3d_engine* e) {
   dfree(e->d_ycell); dfree(e->d_part); dfree(e->d_keys); dfree(e->d_perm); dfree(e->d_offs);
   dfree(e->d_err); dfree(e->d_cnt);
   dfree(e->d_vort);
+  dfree(e->d_hist);
   is3d::polzn::tables_free(e->pz);
   is3d::sampler::tables_free(e->smp);
   for (auto& v : e->ev) if (v) (void)hipEventDestroy(v);
@@ -2693,15 +2702,22 @@ static int df_fail(is3d_engine* e, int derr) {
 }
 
 // cell_base: global index of this engine's cell 0 (a shard of a device-list engine holds only its window)
-int is3d_internal_sample(is3d_engine* e, const is3d_sample_params* sp, const double* plasma, long cell_base) {
+static is3d::sampler::Bins sampler_bins(const is3d_sample_bins& b) {
+  return is3d::sampler::make_bins(b.pT_min, b.pT_max, b.pT_bins, b.y_cut, b.y_bins, b.phip_bins, b.eta_cut, b.eta_bins,
+                                  b.tau_min, b.tau_max, b.tau_bins, b.r_min, b.r_max, b.r_bins);
+}
+
+int is3d_internal_sample(is3d_engine* e, const is3d_sample_params* sp, const double* plasma, long cell_base, int binned) {
   if (!e || e->grp) return IS3D_ERR_ARG;
   e->sampled = false;
+  e->binned = false;
   if (!sp || !plasma) return e->fail(IS3D_ERR_ARG, "is3d_sample: null argument");
   if (e->have_params && e->p.df_mode == PTMA)
     return e->fail(IS3D_ERR_UNSUPPORTED, "is3d_sample: the df_mode 5 sampler (sample_dN_pTdpTdphidy_famod) is not built; df_mode 1-4 only");
   if (sp->n_events < 1) return e->fail(IS3D_ERR_ARG, "is3d_sample: n_events must be >= 1");
   if (!(sp->y_cut > 0.0)) return e->fail(IS3D_ERR_ARG, "is3d_sample: y_cut must be positive");
   if (sp->seed < 0) return e->fail(IS3D_ERR_ARG, "is3d_sample: the seed must be non-negative (a negative sampler_seed takes the clock on the host)");
+  if (binned && !e->have_sbins) return e->fail(IS3D_ERR_STATE, "is3d_sample_binned: is3d_set_sample_bins not called");
   int rc = finalize_tables(e);
   if (rc) return rc;
   if (!e->have_surf) return e->fail(IS3D_ERR_STATE, "is3d_sample: no surface set");
@@ -2749,6 +2765,23 @@ int is3d_internal_sample(is3d_engine* e, const is3d_sample_params* sp, const dou
     }
     c.dens = d_dens;
   }
+  is3d::sampler::Bins sb{};
+  if (binned) {
+    sb = sampler_bins(e->sbins);
+    e->hist_nc = is3d::sampler::hist_counts(sb, np);
+    e->hist_nv = is3d::sampler::hist_vn(sb, np);
+    const long words = e->hist_nc + e->hist_nv;
+    hipError_t h = hipSuccess;
+    if (words > e->hist_cap) {
+      dfree(e->d_hist);
+      e->d_hist = nullptr; e->hist_cap = 0;
+      h = hipMalloc((void**)&e->d_hist, (size_t)words * sizeof(unsigned long long));
+      if (h == hipSuccess) e->hist_cap = words;
+    }
+    if (h == hipSuccess) h = hipMemset(e->d_hist, 0, (size_t)words * sizeof(unsigned long long));
+    if (h != hipSuccess) { dfree(d_dens); return hip_fail(e, h, "sampler histogram"); }
+    c.bins = &sb; c.hist = e->d_hist; c.keep_list = binned == 2;
+  }
   is3d::sampler::Stats st;
   int derr = 0;
   std::string msg;
@@ -2759,13 +2792,58 @@ int is3d_internal_sample(is3d_engine* e, const is3d_sample_params* sp, const dou
   if (s == is3d::sampler::S_BUDGET) return e->fail(IS3D_ERR_ARG, "is3d_sample: " + msg);
   e->sst = is3d_sample_stats{st.cells, st.breakdown, st.candidates, st.kept, st.proposals, st.acceptances, st.capped,
                              st.clamped, st.batches};
+  if (binned) {
+    e->hist.assign((size_t)(e->hist_nc + e->hist_nv), 0);
+    HIPCHK(e, hipMemcpy(e->hist.data(), e->d_hist, e->hist.size() * sizeof(long long), hipMemcpyDeviceToHost));
+    e->binned = true;
+  }
   e->sampled = true;
   return IS3D_OK;
 }
 
+const long long* is3d_internal_sample_hist(const is3d_engine* e) { return (e && e->binned) ? e->hist.data() : nullptr; }
+
 extern "C" int is3d_sample(is3d_engine* e, const is3d_sample_params* sp, const double* plasma) {
-  if (e && e->grp) return is3d::group_sample(e->grp, sp, plasma);
-  return is3d_internal_sample(e, sp, plasma, 0);
+  if (e && e->grp) return is3d::group_sample(e->grp, sp, plasma, 0);
+  return is3d_internal_sample(e, sp, plasma, 0, 0);
+}
+
+extern "C" int is3d_set_sample_bins(is3d_engine* e, const is3d_sample_bins* b) {
+  if (e && e->grp) return b ? is3d::group_set_sample_bins(e->grp, b) : IS3D_ERR_ARG;
+  if (!e || !b) return IS3D_ERR_ARG;
+  if (b->pT_bins < 1 || b->y_bins < 1 || b->phip_bins < 1 || b->eta_bins < 1 || b->tau_bins < 1 || b->r_bins < 1)
+    return e->fail(IS3D_ERR_ARG, "is3d_set_sample_bins: every bin count must be >= 1");
+  if (!(b->pT_max > b->pT_min) || !(b->tau_max > b->tau_min) || !(b->r_max > b->r_min))
+    return e->fail(IS3D_ERR_ARG, "is3d_set_sample_bins: pT, tau and r ranges must be increasing");
+  if (!(b->y_cut > 0.0) || !(b->eta_cut > 0.0)) return e->fail(IS3D_ERR_ARG, "is3d_set_sample_bins: y_cut and eta_cut must be positive");
+  e->sbins = *b;
+  e->have_sbins = true;
+  e->binned = false;
+  return IS3D_OK;
+}
+
+extern "C" int is3d_sample_binned(is3d_engine* e, const is3d_sample_params* sp, const double* plasma, int keep_list) {
+  if (e && e->grp) return is3d::group_sample(e->grp, sp, plasma, keep_list ? 2 : 1);
+  return is3d_internal_sample(e, sp, plasma, 0, keep_list ? 2 : 1);
+}
+
+extern "C" long is3d_sample_hist_size(const is3d_engine* e, long* n_counts, long* n_vn) {
+  if (e && e->grp) return is3d::group_sample_hist_size(e->grp, n_counts, n_vn);
+  if (!e || !e->have_sbins || e->mass.empty()) return -1;
+  const is3d::sampler::Bins sb = sampler_bins(e->sbins);
+  const long nc = is3d::sampler::hist_counts(sb, (int)e->mass.size()), nv = is3d::sampler::hist_vn(sb, (int)e->mass.size());
+  if (n_counts) *n_counts = nc;
+  if (n_vn) *n_vn = nv;
+  return nc + nv;
+}
+
+extern "C" int is3d_get_sample_hist(const is3d_engine* e, long* counts, double* vn) {
+  if (e && e->grp) return (counts && vn) ? is3d::group_get_sample_hist(e->grp, counts, vn) : IS3D_ERR_ARG;
+  if (!e || !counts || !vn) return IS3D_ERR_ARG;
+  if (!e->binned) return IS3D_ERR_STATE;
+  for (long i = 0; i < e->hist_nc; i++) counts[i] = (long)e->hist[(size_t)i];
+  for (long i = 0; i < e->hist_nv; i++) vn[i] = is3d::sampler::vn_value(e->hist[(size_t)(e->hist_nc + i)]);
+  return IS3D_OK;
 }
 
 extern "C" long is3d_sample_count(const is3d_engine* e) {

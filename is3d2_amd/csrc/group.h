@@ -55,7 +55,12 @@ int group_launch_polarization(Group* g, double T_avg, double* dev_out, void* str
 int group_calculate_polarization(Group* g, double T_avg, double* S_out);
 // particle sampler (operation 2): every shard samples its own cell window with the global cell indices in its
 // streams; per event the shard lists are concatenated in shard order, which is the one-device list
-int group_sample(Group* g, const is3d_sample_params* p, const double* plasma);
+// binned (0: the list only, 1: the binned distributions only, 2: both): the group adds the shards' integer
+// histograms, which is the one-device histogram bit for bit
+int group_sample(Group* g, const is3d_sample_params* p, const double* plasma, int binned);
+int group_set_sample_bins(Group* g, const is3d_sample_bins* b);
+long group_sample_hist_size(const Group* g, long* n_counts, long* n_vn);
+int group_get_sample_hist(const Group* g, long* counts, double* vn);
 long group_sample_count(const Group* g);
 int group_sample_offsets(const Group* g, long* offsets);
 int group_get_particles(const Group* g, long first, long count, is3d_particle* out);
@@ -74,7 +79,10 @@ int is3d_internal_chain_npass(const is3d_engine* e);
 double* is3d_internal_chain_bnd(is3d_engine* e, int out, int slot);
 long is3d_internal_chain_bnd_bytes(const is3d_engine* e);
 // is3d_sample on a shard whose cell 0 is the surface's cell cell_base
-int is3d_internal_sample(is3d_engine* e, const is3d_sample_params* p, const double* plasma, long cell_base);
+// (binned: as group_sample)
+int is3d_internal_sample(is3d_engine* e, const is3d_sample_params* p, const double* plasma, long cell_base, int binned);
+// the histogram of the last binned call in its integer form: n_counts counts, then the n_vn fixed-point vn sums
+const long long* is3d_internal_sample_hist(const is3d_engine* e);
 extern "C" {
 // engine-owned copy of cells [lo, lo + n) of a field-major device surface (25 x src_n doubles) on src_device
 int is3d_internal_copy_surface(is3d_engine* e, long n, const double* src, long src_n, int src_device, long lo);

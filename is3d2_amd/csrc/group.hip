@@ -64,6 +64,10 @@ struct Group {
   std::vector<long> particle_offsets;
   is3d_sample_stats sstats{};
   bool sampled = false;
+  // ... and the sum of the shards' integer histograms of the last binned call (counts, then fixed-point vn sums)
+  std::vector<long long> hist;
+  long hist_nc = 0, hist_nv = 0;
+  bool binned = false;
   std::string err;
   int fail(int code, const std::string& m) { err = m; return code; }
   int shard_fail(int k, int rc) {
@@ -653,13 +657,28 @@ int group_total_yield(Group* g, const double* plasma, double y_cut, double* n_to
   return IS3D_OK;
 }
 
-int group_sample(Group* g, const is3d_sample_params* p, const double* plasma) {
+int group_set_sample_bins(Group* g, const is3d_sample_bins* b) {
+  g->binned = false;
+  return each(g, [&](is3d_engine* e) { return is3d_set_sample_bins(e, b); });
+}
+
+long group_sample_hist_size(const Group* g, long* n_counts, long* n_vn) { return is3d_sample_hist_size(g->sh[0], n_counts, n_vn); }
+
+int group_get_sample_hist(const Group* g, long* counts, double* vn) {
+  if (!g->binned) return IS3D_ERR_STATE;
+  for (long i = 0; i < g->hist_nc; i++) counts[i] = (long)g->hist[(size_t)i];
+  for (long i = 0; i < g->hist_nv; i++) vn[i] = (double)g->hist[(size_t)(g->hist_nc + i)] * (1.0 / 4294967296.0);   // sampler_bins.h kVnQuantum
+  return IS3D_OK;
+}
+
+int group_sample(Group* g, const is3d_sample_params* p, const double* plasma, int binned) {
   g->sampled = false;
+  g->binned = false;
   if (!p || !plasma) return g->fail(IS3D_ERR_ARG, "is3d_sample: null argument");
   if (stale_split(g)) return g->fail(IS3D_ERR_STATE, kStaleSplit);
   const int K = (int)g->sh.size();
   // a shard holding the whole surface (PTMA chains: rejected by the shard anyway) samples its window of it
-  const int rc = each_parallel(g, [&](int k) -> int { return is3d_internal_sample(g->sh[k], p, plasma, g->full ? 0 : (k < (int)g->lo.size() ? g->lo[k] : 0)); });
+  const int rc = each_parallel(g, [&](int k) -> int { return is3d_internal_sample(g->sh[k], p, plasma, g->full ? 0 : (k < (int)g->lo.size() ? g->lo[k] : 0), binned); });
   if (rc) return rc;
   const long nev = p->n_events;
   std::vector<std::vector<long>> off(K, std::vector<long>((size_t)nev + 1, 0));
@@ -689,6 +708,16 @@ int group_sample(Group* g, const is3d_sample_params* p, const double* plasma) {
   }
   g->particle_offsets[nev] = at;
   g->sstats = agg;
+  if (binned) {      // integer sums: exact, so the shard order plays no part
+    if (is3d_sample_hist_size(g->sh[0], &g->hist_nc, &g->hist_nv) < 0) return g->shard_fail(0, IS3D_ERR_STATE);
+    g->hist.assign((size_t)(g->hist_nc + g->hist_nv), 0);
+    for (int k = 0; k < K; k++) {
+      const long long* h = is3d_internal_sample_hist(g->sh[k]);
+      if (!h) return g->shard_fail(k, IS3D_ERR_STATE);
+      for (size_t i = 0; i < g->hist.size(); i++) g->hist[i] += h[i];
+    }
+    g->binned = true;
+  }
   g->sampled = true;
   return IS3D_OK;
 }

@@ -595,5 +595,85 @@ std::string write_spacetime_files(const std::string& dir, const SpacetimeView& v
   return "";
 }
 
+std::string write_sampled_files(const std::string& dir, const SampledHistView& v) {
+  const std::string out = join(dir, "results/sampled");
+  const char* subs[9] = {"dN_dy", "dN_deta", "dN_2pipTdpTdy", "dN_dphipdy", "vn", "dN_taudtaudy", "dN_2pirdrdy", "dN_dphisdy", nullptr};
+  for (int k = 0; subs[k]; k++) mkdirs(out + "/" + subs[k]);
+  const double two_pi = 2.0 * M_PI, nev = (double)v.n_events;
+  const double pT_w = (v.pT_max - v.pT_min) / (double)v.pT_bins, y_w = 2.0 * v.y_cut / (double)v.y_bins;
+  const double phip_w = two_pi / (double)v.phip_bins, eta_w = 2.0 * v.eta_cut / (double)v.eta_bins;
+  const double tau_w = (v.tau_max - v.tau_min) / (double)v.tau_bins, r_w = (v.r_max - v.r_min) / (double)v.r_bins;
+  const long np = v.npart;
+  const long* c_y = v.counts;
+  const long* c_eta = c_y + np * v.y_bins;
+  const long* c_phip = c_eta + np * v.eta_bins;
+  const long* c_pT = c_phip + np * v.phip_bins;
+  const long* c_tau = c_pT + np * v.pT_bins;
+  const long* c_r = c_tau + np * v.tau_bins;
+  const long* c_phis = c_r + np * v.r_bins;
+  for (long ipart = 0; ipart < np; ipart++) {
+    const long mc = (*v.mcid)[(size_t)ipart];
+    auto open = [&](const char* sub, const char* tail) {
+      char fn[640];
+      std::snprintf(fn, sizeof(fn), "%s/%s/%s_%ld%s", out.c_str(), sub, sub, mc, tail);
+      return std::fopen(fn, "w");
+    };
+    FILE* f = open("dN_dy", "_test.dat");
+    FILE* g = open("dN_dy", "_average_test.dat");
+    if (!f || !g) { if (f) std::fclose(f); if (g) std::fclose(g); return "cannot write results/sampled/dN_dy of " + std::to_string(mc); }
+    double average = 0.0;
+    for (int i = 0; i < v.y_bins; i++) {
+      const double n = (double)c_y[ipart * v.y_bins + i];
+      average += n;
+      std::fprintf(f, "%.6g\t%.6g\n", -v.y_cut + y_w * ((double)i + 0.5), n / (y_w * nev));
+    }
+    std::fprintf(g, "%.6g\n", average / (2.0 * v.y_cut * nev));
+    std::fclose(f); std::fclose(g);
+    if (!(f = open("dN_deta", "_test.dat"))) return "cannot write results/sampled/dN_deta of " + std::to_string(mc);
+    for (int i = 0; i < v.eta_bins; i++)
+      std::fprintf(f, "%.6g\t%.6g\n", -v.eta_cut + eta_w * ((double)i + 0.5), (double)c_eta[ipart * v.eta_bins + i] / (eta_w * nev));
+    std::fclose(f);
+    if (!(f = open("dN_2pipTdpTdy", "_test.dat"))) return "cannot write results/sampled/dN_2pipTdpTdy of " + std::to_string(mc);
+    for (int i = 0; i < v.pT_bins; i++) {
+      const double mid = v.pT_min + pT_w * ((double)i + 0.5);
+      std::fprintf(f, "%.6e\t%.6e\n", mid, (double)c_pT[ipart * v.pT_bins + i] / (two_pi * 2.0 * v.y_cut * pT_w * mid * nev));
+    }
+    std::fclose(f);
+    if (!(f = open("dN_dphipdy", "_test.dat"))) return "cannot write results/sampled/dN_dphipdy of " + std::to_string(mc);
+    for (int i = 0; i < v.phip_bins; i++)
+      std::fprintf(f, "%.6e\t%.6e\n", phip_w * ((double)i + 0.5), (double)c_phip[ipart * v.phip_bins + i] / (2.0 * v.y_cut * phip_w * nev));
+    std::fclose(f);
+    if (!(f = open("vn", "_test.dat"))) return "cannot write results/sampled/vn of " + std::to_string(mc);
+    for (int i = 0; i < v.pT_bins; i++) {
+      std::fprintf(f, "%.6e", v.pT_min + pT_w * ((double)i + 0.5));
+      for (int k = 0; k < 7; k++) {
+        const double re = v.vn[((long)k * np + ipart) * v.pT_bins + i], im = v.vn[((long)(7 + k) * np + ipart) * v.pT_bins + i];
+        double vn_abs = std::abs(std::complex<double>(re, im)) / (double)c_pT[ipart * v.pT_bins + i];
+        if (std::isnan(vn_abs) || std::isinf(vn_abs)) vn_abs = 0.0;
+        std::fprintf(f, "\t%.6e", vn_abs);
+      }
+      std::fprintf(f, "\n");
+    }
+    std::fclose(f);
+    if (!(f = open("dN_2pirdrdy", "_test.dat"))) return "cannot write results/sampled/dN_2pirdrdy of " + std::to_string(mc);
+    for (int i = 0; i < v.r_bins; i++) {
+      const double mid = v.r_min + r_w * ((double)i + 0.5);
+      std::fprintf(f, "%.6e\t%.6e\n", mid, (double)c_r[ipart * v.r_bins + i] / (two_pi * mid * r_w * nev * 2.0 * v.y_cut));
+    }
+    std::fclose(f);
+    if (!(f = open("dN_taudtaudy", "_test.dat"))) return "cannot write results/sampled/dN_taudtaudy of " + std::to_string(mc);
+    for (int i = 0; i < v.tau_bins; i++) {
+      const double mid = v.tau_min + tau_w * ((double)i + 0.5);
+      std::fprintf(f, "%.6e\t%.6e\n", mid, (double)c_tau[ipart * v.tau_bins + i] / (mid * tau_w * nev * 2.0 * v.y_cut));
+    }
+    std::fclose(f);
+    if (!(f = open("dN_dphisdy", "_test.dat"))) return "cannot write results/sampled/dN_dphisdy of " + std::to_string(mc);
+    for (int i = 0; i < v.phip_bins; i++)
+      std::fprintf(f, "%.6e\t%.6e\n", phip_w * ((double)i + 0.5), (double)c_phis[ipart * v.phip_bins + i] / (phip_w * nev * 2.0 * v.y_cut));
+    std::fclose(f);
+  }
+  return "";
+}
+
 }  // namespace host
 }  // namespace is3d

@@ -119,5 +119,33 @@ struct SampledParticle { long mcid; double mass, tau, x, y, eta, t, z, E, px, py
 std::string write_particle_list_osc(const std::string& dir, const std::vector<SampledParticle>& list, const std::vector<long>& offsets);
 std::string write_particle_list_csv(const std::string& dir, const std::vector<SampledParticle>& list, const std::vector<long>& offsets);
 
+
+// test_sampler = 1 writers (EmissionFunction.cpp:685-975), all under <dir>/results/sampled/, one file per species;
+// the sub-directories are created when missing (the reference relies on a prepared tree).  Byte for byte what the
+// reference's streams produce:
+//   dN_dy/dN_dy_<mcid>_test.dat                   "midpoint \t count / (width Nevents)", both %.6g
+//   dN_dy/dN_dy_<mcid>_average_test.dat           one %.6g line: sum of counts / (2 y_cut Nevents)
+//   dN_deta/dN_deta_<mcid>_test.dat               as dN_dy, with the eta bins
+//   dN_2pipTdpTdy/dN_2pipTdpTdy_<mcid>_test.dat   %.6e: count / (2 pi 2 y_cut width pT_mid Nevents)
+//   dN_dphipdy/dN_dphipdy_<mcid>_test.dat         %.6e: count / (2 y_cut width Nevents)
+//   vn/vn_<mcid>_test.dat                         %.6e: pT midpoint, then seven |re + i im| / pT_count (NaN, inf -> 0)
+//   dN_taudtaudy/dN_taudtaudy_<mcid>_test.dat     %.6e: count / (tau_mid width Nevents 2 y_cut)
+//   dN_2pirdrdy/dN_2pirdrdy_<mcid>_test.dat       %.6e: count / (2 pi r_mid width Nevents 2 y_cut)
+//   dN_dphisdy/dN_dphisdy_<mcid>_test.dat         %.6e: count / (width Nevents 2 y_cut)
+struct SampledHistView {
+  const long* counts;       // is3d_get_sample_hist: dN_dy | dN_deta | dN_dphipdy | pT | tau | r | phis, each [npart][bins]
+  const double* vn;         // [2][7][npart][pT_bins] raw sums
+  int npart;
+  long n_events;
+  double pT_min, pT_max; int pT_bins;
+  double y_cut; int y_bins;
+  int phip_bins;
+  double eta_cut; int eta_bins;
+  double tau_min, tau_max; int tau_bins;
+  double r_min, r_max; int r_bins;
+  const std::vector<long>* mcid;
+};
+std::string write_sampled_files(const std::string& dir, const SampledHistView& v);
+
 }  // namespace host
 }  // namespace is3d

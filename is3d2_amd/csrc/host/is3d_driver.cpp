@@ -90,6 +90,18 @@ static is3d_spacetime_bins spacetime_bins(const ParameterReader& p) {
   return b;
 }
 
+// test_sampler = 1 binning from the parameter file (EmissionFunction.cpp:223-247; the reference's defaults)
+static is3d_sample_bins read_sample_bins(const ParameterReader& p) {
+  is3d_sample_bins b{};
+  b.pT_min = p.get("pT_min", 0.0); b.pT_max = p.get("pT_max", 3.0); b.pT_bins = (int)p.get("pT_bins", 100.0);
+  b.y_cut = p.get("y_cut", 5.0); b.y_bins = (int)p.get("y_bins", 100.0);
+  b.phip_bins = (int)p.get("phip_bins", 100.0);
+  b.eta_cut = p.get("eta_cut", 7.0); b.eta_bins = (int)p.get("eta_bins", 140.0);
+  b.tau_min = p.get("tau_min", 0.0); b.tau_max = p.get("tau_max", 12.0); b.tau_bins = (int)p.get("tau_bins", 120.0);
+  b.r_min = p.get("r_min", 0.0); b.r_max = p.get("r_max", 12.0); b.r_bins = (int)p.get("r_bins", 60.0);
+  return b;
+}
+
 // One engine over every requested device (is3d_create_devices): the library splits the cells into
 // cost-balanced windows, runs the devices concurrently and sums their spectra on the devices (RCCL
 // all-reduce over distinct GPUs), replacing the reference's OpenMP fan-out and thread reduction
@@ -135,12 +147,23 @@ void EmissionFunctionArray::run_sharded(const RunOptions& opt, int operation) {
     } else if (operation == 2) {
       const double plasma[5] = {plasma_.T, plasma_.E, plasma_.P, plasma_.muB, plasma_.nB};
       set_or_throw(e, is3d_total_yield(e, plasma, p_.get("y_cut", 0.5), &ntotal_, nullptr));
-    } else if (operation == 3) {
+    } else if (operation == 3 || operation == 4) {
       const double plasma[5] = {plasma_.T, plasma_.E, plasma_.P, plasma_.muB, plasma_.nB};
       is3d_sample_params sp{};
       sp.seed = sample_seed_; sp.n_events = (int)sample_events_; sp.fast = (int)p_.get("fast", 0.0);
       sp.y_cut = p_.get("y_cut", 0.5);
-      set_or_throw(e, is3d_sample(e, &sp, plasma));
+      if (operation == 4) {      // test_sampler = 1: binned only, no list (EmissionFunction.cpp:1279-1291)
+        sbins_ = read_sample_bins(p_);
+        set_or_throw(e, is3d_set_sample_bins(e, &sbins_));
+        set_or_throw(e, is3d_sample_binned(e, &sp, plasma, 0));
+        long nc = 0, nv = 0;
+        if (is3d_sample_hist_size(e, &nc, &nv) < 0) throw EngineError(IS3D_ERR_STATE, "is3d_sample_hist_size failed");
+        hist_counts_.assign((size_t)nc, 0);
+        hist_vn_.assign((size_t)nv, 0.0);
+        set_or_throw(e, is3d_get_sample_hist(e, hist_counts_.data(), hist_vn_.data()));
+      } else {
+        set_or_throw(e, is3d_sample(e, &sp, plasma));
+      }
       records_.assign((size_t)is3d_sample_count(e), is3d_particle{});
       sample_offsets_.assign((size_t)sample_events_ + 1, 0);
       set_or_throw(e, is3d_sample_offsets(e, sample_offsets_.data()));
@@ -191,6 +214,22 @@ void EmissionFunctionArray::sample_particles(const RunOptions& opt, long seed, l
     sampled_[i] = SampledParticle{mcid_[(size_t)r.species], mass_[(size_t)r.species], r.tau, r.x, r.y, r.eta, r.t, r.z,
                                   r.E, r.px, r.py, r.pz};
   }
+}
+
+void EmissionFunctionArray::sample_binned(const RunOptions& opt, long seed, long n_events) {
+  sample_seed_ = seed;
+  sample_events_ = n_events;
+  run_sharded(opt, 4);
+  sampled_.clear();
+}
+
+void EmissionFunctionArray::write_sampled_files(const std::string& dir) const {
+  const is3d_sample_bins& b = sbins_;
+  SampledHistView v{hist_counts_.data(), hist_vn_.data(), (int)mass_.size(), sample_events_, b.pT_min, b.pT_max, b.pT_bins,
+                    b.y_cut, b.y_bins, b.phip_bins, b.eta_cut, b.eta_bins, b.tau_min, b.tau_max, b.tau_bins, b.r_min, b.r_max,
+                    b.r_bins, &mcid_};
+  const std::string err = host::write_sampled_files(dir, v);
+  if (!err.empty()) throw std::runtime_error(err);
 }
 
 void EmissionFunctionArray::write_polzn_files(const std::string& dir) const {
@@ -297,11 +336,15 @@ void IS3D::run_particlization(int fo_from_file, const RunOptions& opt) {
     }
     dN_.clear();
     final_particles_.clear(); particle_offsets_.clear(); particle_records_.clear();
+    hist_counts_.clear(); hist_vn_.clear();
     if (opt.sample) {            // EmissionFunction.cpp:1251-1301: sample, then write the lists
       // sampler_seed < 0: the clock, as the reference (ParticleSampler.cpp:646-648); the engine sees a seed >= 0
       seed_ = (long)prm.get("sampler_seed", -1.0);
       if (seed_ < 0) seed_ = (long)(std::chrono::system_clock::now().time_since_epoch().count() & 0x7fffffffffffffffLL);
-      efa.sample_particles(opt, seed_, nevents_);
+      // test_sampler = 1 (EmissionFunction.cpp:1279-1291): the particles are binned, never listed
+      const bool binned = (int)prm.get("test_sampler", 0.0) != 0;
+      if (binned) efa.sample_binned(opt, seed_, nevents_);
+      else efa.sample_particles(opt, seed_, nevents_);
       final_particles_ = efa.sampled();
       particle_offsets_ = efa.sample_offsets();
       particle_records_ = efa.sampled_records();
@@ -312,9 +355,22 @@ void IS3D::run_particlization(int fo_from_file, const RunOptions& opt) {
         std::printf("Sampled %ld particles in %ld events (%ld candidates, %ld dropped at an iteration cap)\n", st.kept, nevents_,
                     st.candidates, st.capped);
       }
-      if ((int)prm.get("test_sampler", 0.0) && !opt.quiet)
-        std::printf("test_sampler = 1: the binned results/sampled files are not produced; writing the particle lists\n");
-      if (opt.write_files) {
+      if (binned) {
+        hist_counts_ = efa.hist_counts();
+        hist_vn_ = efa.hist_vn();
+        sample_bins_ = efa.sample_bins();
+        if (opt.write_files) {
+          if (!opt.quiet) {
+            std::printf("Writing event-averaged dN/dy of each species to file...\n");
+            std::printf("Writing event-averaged dN/deta of each species to file...\n");
+            std::printf("Writing event-averaged dN/2pipTdpTdy of each species to file...\n");
+            std::printf("Writing event-averaged dN/dphipdy of each species to file...\n");
+            std::printf("Writing event-averaged vn(pT) of each species to file...\n");
+            std::printf("Writing event-averaged boost invariant spacetime distributions dN_dX of each species to file...\n");
+          }
+          efa.write_sampled_files(dir_);
+        }
+      } else if (opt.write_files) {
         if (!opt.quiet) std::printf("Writing sampled particles list to OSCAR File...\n");
         std::string werr = write_particle_list_osc(dir_, final_particles_, particle_offsets_);
         if (werr.empty() && opt.particle_list_csv) werr = write_particle_list_csv(dir_, final_particles_, particle_offsets_);
@@ -441,6 +497,53 @@ extern "C" int is3d_host_sample(const char* workdir, const int* devices, int num
       for (long i = 0; i < n; i++) mcid_out[i] = run.final_particles()[(size_t)i].mcid;
     }
     if (offsets) std::copy(run.particle_offsets().begin(), run.particle_offsets().end(), offsets);
+    return IS3D_OK;
+  } catch (const EngineError& ex) {
+    put_err(err, errlen, ex.what());
+    return ex.code;
+  } catch (const std::exception& ex) {
+    put_err(err, errlen, ex.what());
+    return IS3D_ERR_ARG;
+  }
+}
+
+extern "C" int is3d_host_sample_hist_size(const char* workdir, is3d_sample_bins* bins, int* npart, long* n_counts, long* n_vn) {
+  const std::string dir = workdir ? workdir : ".";
+  ParameterReader prm;
+  Table chosen;
+  if (!prm.read_file(path_in(dir, "iS3D_parameters.dat")) || !load_table(path_in(dir, "PDG/chosen_particles.dat"), chosen)) return -1;
+  const is3d_sample_bins b = read_sample_bins(prm);
+  const long np = chosen.rows();
+  if (bins) *bins = b;
+  if (npart) *npart = (int)np;
+  if (n_counts) *n_counts = np * ((long)b.y_bins + b.eta_bins + 2L * b.phip_bins + b.pT_bins + b.tau_bins + b.r_bins);
+  if (n_vn) *n_vn = 14L * np * b.pT_bins;
+  return 0;
+}
+
+extern "C" int is3d_host_sample_binned(const char* workdir, const int* devices, int num_devices, int write_files, long* counts,
+                                       long counts_capacity, double* vn, long vn_capacity, long* n_events, double* n_total,
+                                       long* seed, is3d_sample_stats* stats, char* err, int errlen) {
+  if (!devices || num_devices <= 0) { put_err(err, errlen, "empty device list"); return IS3D_ERR_ARG; }
+  try {
+    IS3D run(workdir ? workdir : ".");
+    RunOptions opt;
+    opt.devices.assign(devices, devices + num_devices);
+    opt.quiet = true;
+    opt.sample = true;
+    opt.write_files = write_files != 0;
+    run.run_particlization(1, opt);
+    if (run.hist_counts().empty()) { put_err(err, errlen, "is3d_host_sample_binned: operation = 2 and test_sampler = 1 expected in iS3D_parameters.dat"); return IS3D_ERR_ARG; }
+    if (n_events) *n_events = run.events();
+    if (n_total) *n_total = run.total_yield();
+    if (seed) *seed = run.sampler_seed();
+    if (stats) *stats = run.sample_stats();
+    if ((counts && (long)run.hist_counts().size() > counts_capacity) || (vn && (long)run.hist_vn().size() > vn_capacity)) {
+      put_err(err, errlen, "output buffer too small");
+      return IS3D_ERR_ARG;
+    }
+    if (counts) std::copy(run.hist_counts().begin(), run.hist_counts().end(), counts);
+    if (vn) std::copy(run.hist_vn().begin(), run.hist_vn().end(), vn);
     return IS3D_OK;
   } catch (const EngineError& ex) {
     put_err(err, errlen, ex.what());

@@ -9,8 +9,8 @@
 // relative to a working directory) and the same outputs (results/continuous/*.dat).
 // Differences from the reference: errors are returned / thrown instead of exit(); operation = 2 gives the
 // oversampling estimate (Ntotal, Nevents) and, with RunOptions::sample, the sampled particle lists of df_mode 1-4
-// (the engine's counter-based streams, not the reference's serial random engine; no test_sampler binned files);
-// cells may be sharded over several GPUs in one process.
+// (the engine's counter-based streams, not the reference's serial random engine) or, with test_sampler = 1, the
+// binned results/sampled files instead of the lists; cells may be sharded over several GPUs in one process.
 #pragma once
 #include <string>
 #include <stdexcept>
@@ -37,7 +37,7 @@ struct RunOptions {
   bool quiet = false;
   bool polarization_only = false;   // mode = 5: run only calculate_spin_polzn and its writer, not the operation
   // operation = 2: after the estimate, sample Nevents events (sample_dN_pTdpTdphidy) and write
-  // results/particle_list_osc_<event>.dat; off: the estimate only, no files (is3d_host_total_yield and
+  // results/particle_list_osc_<event>.dat -- or, test_sampler = 1, bin them and write results/sampled/*; off: the estimate only, no files (is3d_host_total_yield and
   // is3d_host_run_particlization); the iS3D_amd executable and is3d_host_sample set it
   bool sample = false;
   bool particle_list_csv = false;   // also write results/particle_list_<event>.dat (write_particle_list_toFile)
@@ -72,6 +72,14 @@ class EmissionFunctionArray {
   const std::vector<is3d_particle>& sampled_records() const { return records_; }
   const std::vector<long>& sample_offsets() const { return sample_offsets_; }
   const is3d_sample_stats& sample_stats() const { return sample_stats_; }
+  // ... with test_sampler = 1 (ParticleSampler.cpp:1112-1121): the same events binned on the device with the parameter
+  // file's bins and no list; hist_counts() / hist_vn() = is3d_get_sample_hist's arrays, write_sampled_files the
+  // results/sampled/* tree (EmissionFunction.cpp:685-975)
+  void sample_binned(const RunOptions& opt, long seed, long n_events);
+  const std::vector<long>& hist_counts() const { return hist_counts_; }
+  const std::vector<double>& hist_vn() const { return hist_vn_; }
+  is3d_sample_bins sample_bins() const { return sbins_; }
+  void write_sampled_files(const std::string& dir) const;
   // mode = 5 (EmissionFunction.cpp:1305-1310): calculate_spin_polzn at T = the Plasma average temperature, on an
   // engine of its own that holds only params, species, grid, surface and vorticity.  IS3D::run_particlization calls
   // it after the chosen operation (0, 1 or 2) and after that operation's files are written.
@@ -106,7 +114,10 @@ class EmissionFunctionArray {
   std::vector<is3d_particle> records_;
   std::vector<long> sample_offsets_;
   is3d_sample_stats sample_stats_{};
-  // operation 3: the sampler (engine operation 2); 2: the yield estimate; -1: the polarization alone (an engine without PDG, Gauss-Laguerre and df tables)
+  is3d_sample_bins sbins_{};
+  std::vector<long> hist_counts_;
+  std::vector<double> hist_vn_;
+  // operation 3: the sampler (engine operation 2), 4: its binned-only form; 2: the yield estimate; -1: the polarization alone (an engine without PDG, Gauss-Laguerre and df tables)
   void run_sharded(const RunOptions& opt, int operation);
 };
 
@@ -138,6 +149,10 @@ class IS3D {
   const std::vector<is3d_particle>& particle_records() const { return particle_records_; }
   const is3d_sample_stats& sample_stats() const { return sample_stats_; }
   long sampler_seed() const { return seed_; }
+  // ... with test_sampler = 1: no list (the offsets are zero); the histograms of is3d_get_sample_hist and their bins
+  const std::vector<long>& hist_counts() const { return hist_counts_; }
+  const std::vector<double>& hist_vn() const { return hist_vn_; }
+  const is3d_sample_bins& sample_bins() const { return sample_bins_; }
 
  private:
   std::string dir_;
@@ -150,6 +165,9 @@ class IS3D {
   std::vector<long> particle_offsets_;
   std::vector<is3d_particle> particle_records_;
   is3d_sample_stats sample_stats_{};
+  std::vector<long> hist_counts_;
+  std::vector<double> hist_vn_;
+  is3d_sample_bins sample_bins_{};
   long seed_ = 0;
 };
 

@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "sampler_bins.h"
 #include "sampler_math.h"
 
 namespace is3d {
@@ -35,6 +36,12 @@ struct Config {
   long n_events = 1;
   const double* dens = nullptr;    // fast = 1: [3][npart] Plasma-average densities (device)
   long sample_bytes = 0;           // bound on the working buffers of one batch
+  // test_sampler = 1: kept particles are also binned into hist (device, hist_counts + hist_vn 8-byte words that the
+  // caller zeroed; the vn words in their integer form).  keep_list = false: binned only -- no candidate slots, no
+  // compaction and no list; a batch then costs only its (event, cell) counts.
+  const Bins* bins = nullptr;
+  unsigned long long* hist = nullptr;
+  bool keep_list = true;
 };
 
 struct Stats {
@@ -45,7 +52,8 @@ struct Stats {
 enum Status : int { S_OK = 0, S_DEVICE = 1, S_DF = 2, S_BUDGET = 3 };
 
 // Samples n_events events of the window.  parts: kept particles, events contiguous, ordered by (cell, candidate)
-// within an event (the reference's loop order); offsets: n_events + 1.  Returns a Status; S_DF: df_err holds the
+// within an event (the reference's loop order); offsets: n_events + 1 (a binned-only call leaves parts empty and the
+// offsets zero; st.kept and st.candidates then come from device tallies).  Returns a Status; S_DF: df_err holds the
 // DfErr; msg says what went wrong otherwise.
 int run(const Tables& t, const Config& c, std::vector<Particle>& parts, std::vector<long>& offsets, Stats& st,
         int& df_err, std::string& msg);

@@ -16,7 +16,14 @@
 //               delta-f / flux weights, keep draw, lab boost -- and write kept particles and a flag into their slots
 //   scan + k_compact   stable compaction of the kept slots; the batch is copied to the host list
 //
-// Nothing here appends with atomics; the only atomics are the integer tallies of the stats.
+// test_sampler = 1 (Config::bins): k_sample also bins every kept particle (sampler_bins.h) straight from its registers
+// into the call's histogram with no-return 64-bit integer atomics from the lanes -- counts, and the vn sums in
+// fixed point, so the histogram is the same bits for every batch, window, geometry and shard.  A binned-only call
+// (keep_list = false) runs k_count and the k_sample variant that writes no slot, and nothing else: no slot scan, no
+// flags, no compaction, no copy; its batches are sized by their (event, cell) counts alone, and the candidate and kept
+// totals are device tallies.
+//
+// Nothing here appends with atomics; the only atomics are the integer tallies of the stats and the histogram adds.
 #include "sampler.h"
 
 #include <hipcub/hipcub.hpp>
@@ -54,6 +61,9 @@ struct Args {
   const long* slots;           // exclusive sum of counts
   Particle* cand;
   int* flags;
+  // binned distributions
+  Bins bins;
+  unsigned long long* hist;
 };
 
 __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
@@ -127,6 +137,8 @@ __global__ __launch_bounds__(256) void k_count(Args A) {
   A.counts[i] = n;
 }
 
+// LIST: kept particles and flags go to their slots; BIN: kept particles are binned into A.hist
+template <bool LIST, bool BIN>
 __global__ __launch_bounds__(kWave) void k_sample(Args A) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   Cell& sc = *reinterpret_cast<Cell*>(smem);
@@ -142,6 +154,7 @@ __global__ __launch_bounds__(kWave) void k_sample(Args A) {
   __syncthreads();
   species_list(A, sc, cum, true);
   Tally t{0, 0, 0, 0};
+  unsigned long long ncand = 0, nkept = 0;     // binned-only: there is no scan to count them
   for (long evb = 0; evb < A.nev; evb += kWave) {
     const long ev = evb + lane;
     pre[lane + 1] = ev < A.nev ? (long)A.counts[ev * ncb + ci] : 0L;
@@ -159,12 +172,23 @@ __global__ __launch_bounds__(kWave) void k_sample(Args A) {
         if (pre[mid] <= j) lo = mid; else hi = mid - 1;
       }
       const long evl = evb + lo, nc = j - pre[lo];
-      const long slot = A.slots[evl * ncb + ci] + nc;
       Particle p;
+      double drawn = 0.0;
       const bool kept = candidate(A.run, sc, A.seed, A.cell_base + cell, A.e0 + evl, nc, cum, A.npart, A.mass, A.sign,
-                                  A.baryon, &p, t, nullptr);
-      A.flags[slot] = kept ? 1 : 0;
-      if (kept) A.cand[slot] = p;
+                                  A.baryon, &p, t, nullptr, drawn);
+      if (LIST) {
+        const long slot = A.slots[evl * ncb + ci] + nc;
+        A.flags[slot] = kept ? 1 : 0;
+        if (kept) A.cand[slot] = p;
+      } else {
+        ncand++;
+        nkept += kept ? 1 : 0;
+      }
+      if (BIN && kept) {
+        const Landing l = bin_particle(A.bins, particle_rapidity(A.run.k.dim, drawn, p.E, p.pz), p.eta, p.px, p.py, p.tau, p.x, p.y);
+        unsigned long long* hist = A.hist;
+        hist_accumulate(A.bins, A.npart, p.species, l, [hist](long word, long long v) { atomicAdd(hist + word, (unsigned long long)v); });
+      }
     }
     __syncthreads();
   }
@@ -173,6 +197,13 @@ __global__ __launch_bounds__(kWave) void k_sample(Args A) {
   if (lane == 0)
     for (int k = 0; k < 4; k++)
       if (v[k]) atomicAdd(&A.tally[1 + k], v[k]);
+  if (!LIST) {
+    const unsigned long long nk = wave_sum(nkept), nc = wave_sum(ncand);
+    if (lane == 0) {
+      if (nk) atomicAdd(&A.tally[6], nk);
+      if (nc) atomicAdd(&A.tally[7], nc);
+    }
+  }
 }
 
 __global__ __launch_bounds__(256) void k_compact(const Particle* cand, const int* flags, const long* pos, long n, Particle* out) {
@@ -312,11 +343,33 @@ int run(const Tables& t, const Config& c, std::vector<Particle>& parts, std::vec
   std::vector<double> acc((size_t)nw + 1, 0.0);
   for (long i = 0; i < nw; i++) acc[i + 1] = acc[i] + dn[i];
   const long budget = std::max(c.sample_bytes, 1L);
+  const bool binned_only = c.bins && !c.keep_list;
+  if (c.bins) { A.bins = *c.bins; A.hist = c.hist; }
+  if (binned_only) {
+    // a batch costs kPairBytes per (event, cell) and nothing per candidate, so its size is known before it runs:
+    // whole events while they fit, else windows of cells of one event (one (event, cell) always fits)
+    const long max_pairs = std::max(1L, std::min(budget / kPairBytes, 0x7ffffff0L));
+    long e0 = 0, a = 0;
+    while (e0 < c.n_events) {
+      long nev = 1, b = std::min(nw, a + max_pairs);
+      if (a == 0 && nw <= max_pairs) { nev = std::min(c.n_events - e0, max_pairs / nw); b = nw; }
+      const long ncb = b - a, np = nev * ncb;
+      SCHK(B.pairs(np));
+      A.e0 = e0; A.nev = nev; A.c0 = c.lo + a; A.c1 = c.lo + b; A.counts = B.counts; A.slots = B.slots;
+      hipLaunchKernelGGL(k_count, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, 0, A);
+      SCHK(hipGetLastError());
+      hipLaunchKernelGGL((k_sample<false, true>), dim3((unsigned)ncb), dim3(kWave), lds, 0, A);
+      SCHK(hipGetLastError());
+      st.batches++;
+      if (b == nw) { e0 += nev; a = 0; } else { a = b; }
+    }
+    SCHK(hipDeviceSynchronize());
+  }
   auto estimate = [&](long nev, long a, long b) {     // bytes of a batch of nev events over window cells [a, b)
     const double mean = (double)nev * (acc[b] - acc[a]);
     return (double)nev * (double)(b - a) * kPairBytes + (mean + 6.0 * std::sqrt(mean) + 16.0) * kCandBytes;
   };
-  long e0 = 0, a = 0;                                 // a: first window cell of the next batch (> 0: event e0 is split)
+  long e0 = binned_only ? c.n_events : 0, a = 0;      // a: first window cell of the next batch (> 0: event e0 is split)
   while (e0 < c.n_events) {
     long nev = 1, b = nw;
     if (a == 0) {
@@ -355,7 +408,8 @@ int run(const Tables& t, const Config& c, std::vector<Particle>& parts, std::vec
         SCHK(B.cands(total + 1));
         A.cand = B.cand; A.flags = B.flags;
         SCHK(hipMemsetAsync(B.flags + total, 0, sizeof(int), 0));
-        hipLaunchKernelGGL(k_sample, dim3((unsigned)ncb), dim3(kWave), lds, 0, A);
+        if (c.bins) hipLaunchKernelGGL((k_sample<true, true>), dim3((unsigned)ncb), dim3(kWave), lds, 0, A);
+        else hipLaunchKernelGGL((k_sample<true, false>), dim3((unsigned)ncb), dim3(kWave), lds, 0, A);
         SCHK(hipGetLastError());
         SCHK(scan(B.flags, B.pos, total + 1, B.tmp, B.tmp_cap));
         long kept = 0;
@@ -378,6 +432,7 @@ int run(const Tables& t, const Config& c, std::vector<Particle>& parts, std::vec
   st.breakdown = (long)tally[0]; st.proposals = (long)tally[1]; st.acceptances = (long)tally[2];
   st.capped = (long)(tally[3] + tally[5]); st.clamped = (long)tally[4];
   st.kept = (long)parts.size();
+  if (binned_only) { st.kept = (long)tally[6]; st.candidates = (long)tally[7]; }
   for (const Particle& p : parts) offsets[(size_t)p.event + 1]++;
   for (long e = 0; e < c.n_events; e++) offsets[e + 1] += offsets[e];
   return S_OK;

@@ -397,9 +397,10 @@ IS3D_HD double clamp_df(double df, Tally& t) {
 
 // Draws species, momentum and the keep decision of candidate n of (cell, event); true = kept, *out filled.
 // cum[npart]: the cell's running species weights; mass / sign / baryon: the chosen species in their original order.
+// drawn: the drawn rapidity of a kept 2+1D particle (the binned distributions take it as drawn; untouched in 3+1D).
 IS3D_HD bool candidate(const Run& R, const Cell& c, uint64_t seed, long cell, long event, long n, const double* cum,
                        int npart, const double* mass, const double* sign, const double* baryon_, Particle* out, Tally& t,
-                       int* branch_out) {
+                       int* branch_out, double& drawn) {
   const int mode = R.k.df_mode;
   Stream st = stream_open(seed, P_TYPE, cell, event, n);
   const int sp = species_draw(cum, npart, stream_next(st));
@@ -455,6 +456,7 @@ IS3D_HD bool candidate(const Run& R, const Cell& c, uint64_t seed, long cell, lo
   if (R.k.dim == 2) {              // :1079-1098
     Stream sr = stream_open(seed, P_RAPIDITY, cell, event, n);
     const double rapidity = R.y_max * (2.0 * stream_next(sr) - 1.0);
+    drawn = rapidity;
     const double sinhy = sinh(rapidity), coshy = sqrt(1.0 + sinhy * sinhy);
     const double tau_pn = c.tau * pn;
     const double mT = sqrt(m2 + lpx * lpx + lpy * lpy);   // = sqrt(ptau^2 - (tau pn)^2) of :1088, without its cancellation
@@ -472,6 +474,13 @@ IS3D_HD bool candidate(const Run& R, const Cell& c, uint64_t seed, long cell, lo
   out->t = c.tau * cosheta; out->z = c.tau * sinheta;
   out->E = E; out->px = lpx; out->py = lpy; out->pz = pz;
   return true;
+}
+
+IS3D_HD bool candidate(const Run& R, const Cell& c, uint64_t seed, long cell, long event, long n, const double* cum,
+                       int npart, const double* mass, const double* sign, const double* baryon_, Particle* out, Tally& t,
+                       int* branch_out) {
+  double drawn = 0.0;
+  return candidate(R, c, seed, cell, event, n, cum, npart, mass, sign, baryon_, out, t, branch_out, drawn);
 }
 
 }  // namespace sampler

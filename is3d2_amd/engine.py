@@ -31,6 +31,24 @@ SPACETIME_BINS = dict(tau_min=0.0, tau_max=12.0, tau_bins=120, r_min=0.0, r_max=
                       threads=0)
 
 
+# test_sampler = 1 binning of the sampled particles (iS3D_parameters.dat defaults; EmissionFunction.cpp:223-247)
+SAMPLE_BINS = dict(pT_min=0.0, pT_max=3.0, pT_bins=100, y_cut=5.0, y_bins=100, phip_bins=100, eta_cut=7.0, eta_bins=140,
+                   tau_min=0.0, tau_max=12.0, tau_bins=120, r_min=0.0, r_max=12.0, r_bins=60)
+
+
+def split_sample_hist(counts, vn, bins):
+    """The flat (counts, vn) of is3d_get_sample_hist as Engine.sample_hist's dict of arrays."""
+    sizes = [int(bins[key]) for _, key in _lib.SAMPLE_BIN_PARTS]
+    npart = len(counts) // sum(sizes)
+    hist, at = {}, 0
+    for (name, _), nb in zip(_lib.SAMPLE_BIN_PARTS, sizes):
+        hist[name] = counts[at:at + npart * nb].reshape(npart, nb)
+        at += npart * nb
+    v = np.asarray(vn).reshape(2, 7, npart, int(bins["pT_bins"]))
+    hist["vn_real"], hist["vn_imag"] = v[0], v[1]
+    return hist
+
+
 def _dp(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
 
@@ -288,6 +306,46 @@ class Engine:
         if n > 0:
             self._chk(self.lib.is3d_get_particles(self._e, 0, n, C.c_void_p(parts.ctypes.data)))
         return parts, offsets, self.sample_stats()
+
+    # --- test_sampler = 1: the binned distributions of the kept particles (BinSampledParticle.cpp:9-133) ---
+    def set_sample_bins(self, **bins):
+        """The reference's bin parameters (is3d_sample_bins): pT_min pT_max pT_bins, y_cut y_bins, phip_bins,
+        eta_cut eta_bins, tau_min tau_max tau_bins, r_min r_max r_bins; defaults SAMPLE_BINS."""
+        b = dict(SAMPLE_BINS)
+        b.update({k: v for k, v in bins.items() if k in SAMPLE_BINS})
+        self.sample_bins = b
+        self._chk(self.lib.is3d_set_sample_bins(self._e, C.byref(_lib.SampleBins(**b))))
+
+    def sample_hist(self):
+        """The histograms of the last sample_binned as a dict: the count parts (int64 [npart][bins]) dN_dy, dN_deta,
+        dN_dphipdy, pT_count, dN_taudtaudy, dN_2pirdrdy, dN_dphisdy, and the raw sums vn_real, vn_imag
+        ([7][npart][pT_bins]) of cos(k phi), sin(k phi), k = 1..7."""
+        nc, nv = C.c_long(0), C.c_long(0)
+        if self.lib.is3d_sample_hist_size(self._e, C.byref(nc), C.byref(nv)) < 0:
+            raise IS3DError(_lib.IS3D_ERR_STATE, "sample bins / species not set")
+        counts = np.zeros(nc.value, dtype=np.int64)
+        vn = np.zeros(nv.value, dtype=np.float64)
+        self._chk(self.lib.is3d_get_sample_hist(self._e, counts.ctypes.data_as(C.POINTER(C.c_long)), _dp(vn)))
+        return split_sample_hist(counts, vn, self.sample_bins)
+
+    def sample_binned(self, seed, n_events, y_cut=0.5, fast=0, plasma=None, keep_list=False):
+        """sample() with every kept particle binned on the device (set_sample_bins first).  keep_list = False:
+        (hist, stats) -- no list is built, a batch needs only its (event, cell) counts; keep_list = True:
+        (hist, stats, particles, offsets) with sample()'s list.  hist: see sample_hist(); it is bit-identical for
+        every "sample_bytes" batch, cell window split and device list."""
+        pl = _arr(plasma)
+        sp = _lib.SampleParams(int(seed), int(n_events), int(fast), float(y_cut))
+        self._chk(self.lib.is3d_sample_binned(self._e, C.byref(sp), _dp(pl), int(bool(keep_list))))
+        hist, stats = self.sample_hist(), self.sample_stats()
+        if not keep_list:
+            return hist, stats
+        n = self.lib.is3d_sample_count(self._e)
+        parts = np.zeros(max(n, 0), dtype=_lib.PARTICLE_DTYPE)
+        offsets = np.zeros(int(n_events) + 1, dtype=np.int64)
+        self._chk(self.lib.is3d_sample_offsets(self._e, offsets.ctypes.data_as(C.POINTER(C.c_long))))
+        if n > 0:
+            self._chk(self.lib.is3d_get_particles(self._e, 0, n, C.c_void_p(parts.ctypes.data)))
+        return hist, stats, parts, offsets
 
     def sample_stats(self):
         s = _lib.SampleStats()

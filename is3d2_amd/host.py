@@ -31,6 +31,10 @@ def load():
                                          PL, PL, PD, PL, C.c_char_p, C.c_int]
         lib.is3d_host_write_particle_lists.argtypes = [C.c_char_p, C.c_long, PL, C.c_void_p, PL, PD, C.c_int, C.c_char_p,
                                                        C.c_int]
+        from ._lib import SampleBins, SampleStats
+        lib.is3d_host_sample_hist_size.argtypes = [C.c_char_p, C.POINTER(SampleBins), PI, PL, PL]
+        lib.is3d_host_sample_binned.argtypes = [C.c_char_p, PI, C.c_int, C.c_int, PL, C.c_long, PD, C.c_long, PL, PD, PL,
+                                                C.POINTER(SampleStats), C.c_char_p, C.c_int]
         _lib = lib
     return _lib
 
@@ -139,15 +143,43 @@ def sample(workdir, devices=(0,), write_files=True, write_csv=False):
     results/particle_list_osc_<event>.dat (and particle_list_<event>.dat with write_csv).  Returns a dict: particles
     (structured array, _lib.PARTICLE_DTYPE), mcid (per particle), offsets (Nevents + 1), n_total, n_events, seed.
     The list is sized by a first call that writes nothing, so a clock seed (sampler_seed < 0) is refused here:
-    the second call would sample another list."""
-    from ._lib import PARTICLE_DTYPE
+    the second call would sample another list.
+
+    test_sampler = 1 in the run directory: the particles are binned on the device and never listed, as in the
+    reference -- write_files writes the results/sampled/* tree and no particle list, the returned list is empty and
+    "hist" holds the histograms (Engine.sample_hist's dict) and "stats" the sampler's counters; "hist" is None for
+    test_sampler = 0."""
+    from ._lib import PARTICLE_DTYPE, SampleBins, SampleStats
+    from .engine import split_sample_hist
     lib = load()
-    if param(os.path.join(workdir, "iS3D_parameters.dat"), "sampler_seed") < 0:
+    pfile = os.path.join(workdir, "iS3D_parameters.dat")
+    if param(pfile, "sampler_seed") < 0:
         raise HostError(1, "host.sample needs a fixed sampler_seed >= 0 in iS3D_parameters.dat")
     dv = np.ascontiguousarray(devices, dtype=np.int32)
     pdv = dv.ctypes.data_as(C.POINTER(C.c_int))
     n, nev, nt, seed = C.c_long(), C.c_long(), C.c_double(), C.c_long()
     err = C.create_string_buffer(512)
+    try:
+        binned = param(pfile, "test_sampler") != 0
+    except KeyError:
+        binned = False
+    if binned:
+        PL = C.POINTER(C.c_long)
+        bins, npart, nc, nv = SampleBins(), C.c_int(), C.c_long(), C.c_long()
+        if lib.is3d_host_sample_hist_size(workdir.encode(), C.byref(bins), C.byref(npart), C.byref(nc), C.byref(nv)):
+            raise HostError(1, "cannot read iS3D_parameters.dat / PDG/chosen_particles.dat")
+        counts = np.zeros(nc.value, dtype=np.int64)
+        vn = np.zeros(nv.value)
+        st = SampleStats()
+        rc = lib.is3d_host_sample_binned(workdir.encode(), pdv, len(dv), int(write_files), counts.ctypes.data_as(PL), len(counts),
+                                         vn.ctypes.data_as(C.POINTER(C.c_double)), len(vn), C.byref(nev), C.byref(nt),
+                                         C.byref(seed), C.byref(st), err, 512)
+        if rc:
+            raise HostError(rc, err.value.decode())
+        hist = split_sample_hist(counts, vn, {k: getattr(bins, k) for k, _ in bins._fields_})
+        return dict(particles=np.zeros(0, dtype=PARTICLE_DTYPE), mcid=np.zeros(0, dtype=np.int64),
+                    offsets=np.zeros(nev.value + 1, dtype=np.int64), n_total=nt.value, n_events=nev.value, seed=seed.value,
+                    hist=hist, stats={k: getattr(st, k) for k, _ in st._fields_})
     rc = lib.is3d_host_sample(workdir.encode(), pdv, len(dv), 0, 0, None, None, 0, None, 0, C.byref(n), C.byref(nev),
                               C.byref(nt), C.byref(seed), err, 512)
     if rc:
@@ -161,7 +193,7 @@ def sample(workdir, devices=(0,), write_files=True, write_csv=False):
                               C.byref(nt), C.byref(seed), err, 512)
     if rc:
         raise HostError(rc, err.value.decode())
-    return dict(particles=parts, mcid=mcid, offsets=off, n_total=nt.value, n_events=nev.value, seed=seed.value)
+    return dict(particles=parts, mcid=mcid, offsets=off, n_total=nt.value, n_events=nev.value, seed=seed.value, hist=None)
 
 
 def write_particle_lists(workdir, particles, offsets, mcid, mass, write_csv=True):

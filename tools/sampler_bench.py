@@ -14,7 +14,12 @@ There is no reference figure: the reference sampler needs GSL.  Prints one JSON 
   cpu_candidates_per_s     the serial emulator on the first --cpu-cells cells, one core
   build_id                 is3d_build_id() of the library measured
 
-    python tools/sampler_bench.py [--cells 100000] [--events 8] [--repeats 3] [--warmup 1] [--cpu-cells 2000]
+--binned: after the list call, and in the same process, the same protocol times Engine.sample_binned(keep_list=False)
+-- the test_sampler = 1 form that bins every kept particle on the device (the reference's default bins) and builds no
+list -- and adds binned_ms, binned_ms_all, binned_batches, binned_candidates_per_s, binned_accepted_per_s; the counts of
+the two calls must agree.
+
+    python tools/sampler_bench.py [--cells 100000] [--events 8] [--repeats 3] [--warmup 1] [--cpu-cells 2000] [--binned]
 """
 import argparse
 import json
@@ -36,6 +41,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--cpu-cells", type=int, default=2000)
+    ap.add_argument("--binned", action="store_true")
     a = ap.parse_args()
     from is3d2_amd import _lib, build_engine, make_spec, surface_averages, synth
     s = synth.as_read(synth.surface(a.cells, seed=7, dimension=3, full3d=True))
@@ -43,6 +49,8 @@ def main():
     for mode in (1, 4):
         spec = make_spec(hrg_eos=2, chosen="smash", df_mode=mode, dimension=3)
         e = build_engine(spec, s, T_avg=plasma[0])
+        if a.binned:
+            e.set_sample_bins()
         for fast in (0, 1):
             for _ in range(a.warmup):
                 e.sample(1, a.events, 0.5, fast, plasma)
@@ -57,6 +65,19 @@ def main():
                        kept=st["kept"], candidates_per_s=st["candidates"] / t, accepted_per_s=st["kept"] / t,
                        efficiency=st["acceptances"] / max(st["proposals"], 1), capped=st["capped"],
                        batches=st["batches"], build_id=_lib.build_id())
+            if a.binned:
+                for _ in range(a.warmup):
+                    e.sample_binned(1, a.events, 0.5, fast, plasma)
+                bms = []
+                for r in range(a.repeats):
+                    t0 = time.perf_counter()
+                    hist, bst = e.sample_binned(1, a.events, 0.5, fast, plasma)
+                    bms.append(1e3 * (time.perf_counter() - t0))
+                assert bst["kept"] == st["kept"] and bst["candidates"] == st["candidates"]
+                assert int(hist["dN_dphipdy"].sum()) == st["kept"]
+                bt = float(np.median(bms)) * 1e-3
+                out.update(binned_ms=round(bt * 1e3, 3), binned_ms_all=[round(v, 3) for v in bms], binned_batches=bst["batches"],
+                           binned_candidates_per_s=bst["candidates"] / bt, binned_accepted_per_s=bst["kept"] / bt)
             if a.cpu_cells > 0:
                 import sampler_ref as R
                 t0 = time.perf_counter()
