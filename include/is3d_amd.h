@@ -211,7 +211,7 @@ int is3d_cell_costs(is3d_engine *e, double *cost);
  *   is3d_launch_end(e)   ...   is3d_finish(e)
  * Buffers hold is3d_chain_boundary_size(e) doubles, in device memory (or host memory: the copies are asynchronous
  * on the launch stream, so the caller synchronises it before reading a host buffer it got).
- * At the fixed point each range's solutions are the one-chain solutions bit for bit (engine.hip k_chain_pass), so
+ * At the fixed point each range's solutions are the one-chain solutions bit for bit (engine_kernels.h k_chain_pass), so
  * the per-process Newton iteration counts (is3d_get_stats) add up to the serial chain's.  is3d_launch refuses an
  * engine with a chain range. */
 int is3d_set_chain_range(is3d_engine *e, long q0, long q1);

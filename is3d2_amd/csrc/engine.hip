@@ -1,5 +1,6 @@
 // engine.hip -- MI355X (gfx950) Cooper-Frye continuous-spectra engine behind the
-// C ABI of include/is3d_amd.h.
+// C ABI of include/is3d_amd.h.  This file is the host side; the kernels named below are in engine_kernels.h (the
+// prepass, the reductions, operations 0 and 2) and kernels.h (the momentum integrals).
 //
 // Hot path (reference MomentumSpectra.cpp:32-1682, dispatched from
 // EmissionFunction.cpp:1198-1226):
@@ -64,772 +65,12 @@
 #include "group.h"
 #include "polzn.h"
 #include "sampler.h"
+#include "devbuf.h"
 
 using namespace is3d;
 using namespace is3d::kern;
 
-namespace {
-
-struct DevTables {            // device copy of the delta-f tables (pointers into one blob)
-  DfTables tb;
-};
-
-// ------------------------------------------------------------------------------------------
-// prepass kernels
-// ------------------------------------------------------------------------------------------
-struct PrepArgs {
-  PrepConsts k;
-  DfTables tb;
-  const double* surf;   // [NSURF][n]
-  double* rec;          // [n][NREC]
-  double* aux;          // PTM/PTB: [9][n]; PTMA: [9][n] Newton inputs
-  long n;               // cells held (the field stride of surf / aux)
-  long c0, c1;          // cells [c0, c1) prepared by this launch
-  int* err;
-  unsigned long long* cnt;  // [0] breakdown [1] pl<0 [2] recon fail [3] iterations
-};
-
-template <int MODE>
-__global__ __launch_bounds__(256) void k_prep(PrepArgs A) {
-  const long c = A.c0 + (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= A.c1) return;
-  double s[NSURF];
-#pragma unroll
-  for (int f = 0; f < NSURF; f++) s[f] = A.surf[(long)f * A.n + c];
-  double R[NREC];
-  int err = DF_OK;
-  if (MODE == GRAD || MODE == CE) {
-    err = prep_grad_ce(A.k, A.tb, s, R);
-  } else if (MODE == PTM || MODE == PTB) {
-    double aux[9];
-    int flags[2];
-    err = prep_feqmod(A.k, A.tb, s, R, aux, flags);
-    if (!err) {
-#pragma unroll
-      for (int f = 0; f < 9; f++) A.aux[(long)f * A.n + c] = aux[f];
-      if (flags[0] && R[R_KIND] != 0.0) atomicAdd(&A.cnt[0], 1ull);
-      if (flags[1]) atomicAdd(&A.cnt[1], 1ull);
-    }
-  } else {
-    double ain[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    prep_famod_a(A.k, s, R, ain);
-#pragma unroll
-    for (int f = 0; f < 9; f++) A.aux[(long)f * A.n + c] = ain[f];
-  }
-  if (err) { atomicMax(A.err, err); R[R_KIND] = 0.0; }
-  if (R[R_KIND] != 0.0) sep_cell_consts(MODE, R);
-  // Grad / RTA-CE: cells whose lanes may leave the fast path (|mu_B| / T beyond ~300) counted in cnt[4]: any such
-  // cell sends the launch to the F_TB kernels, the F_TS ones carry no slow loop (launch_end)
-  if (MODE <= CE && A.k.operation == 1 && R[R_KIND] != 0.0 && sep_slow_cell(R, A.k.pT_max, A.k.b_max))
-    atomicAdd(&A.cnt[4], 1ULL);
-#pragma unroll
-  for (int f = 0; f < NREC; f++) A.rec[c * NREC + f] = R[f];
-}
-
-struct WaveSum {
-  __device__ double operator()(double v) const {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-  }
-};
-
-// sum over the W wavefronts of a workgroup (W x 64 lanes share one cell's Newton terms): each wave's sums, then the
-// W partials from LDS in wave order (every lane gets the same bits), two barriers per red_all call of up to kRedN
-// values
-constexpr int kRedN = 8;
-template <int W>
-struct BlockSum {
-  double* s;   // LDS, kRedN x W doubles
-  __device__ double operator()(double v) const;
-};
-template <int W, class... T>
-__device__ __forceinline__ void red_all(const BlockSum<W>& r, T&... v) {
-  static_assert(sizeof...(T) <= kRedN, "BlockSum: at most kRedN values per call");
-  ((v = WaveSum()(v)), ...);
-  if constexpr (W > 1) {
-    const int wave = threadIdx.x >> 6;
-    int k = 0;
-    if ((threadIdx.x & 63) == 0) ((r.s[(k++) * W + wave] = v), ...);
-    __syncthreads();
-    k = 0;
-    auto sum = [&](int kk) {
-      double a = r.s[kk * W];
-#pragma unroll
-      for (int w = 1; w < W; w++) a += r.s[kk * W + w];
-      return a;
-    };
-    ((v = sum(k++)), ...);
-    __syncthreads();
-  }
-}
-template <int W>
-__device__ double BlockSum<W>::operator()(double v) const {
-  red_all(*this, v);
-  return v;
-}
-
-struct AnisoArgs {
-  const double* rec; const double* ain; double* sol;   // rec [n][NREC], ain [9][stride], sol [6][stride]
-  long c0, n, chains;   // cells [c0, c0 + n) in `chains` warm-start chains
-  long stride;          // cells held
-  Hadrons h;
-  double fp2;
-  unsigned long long* cnt;
-};
-
-// one wavefront per warm-start chain: cells chain, chain + C, chain + 2C, ... (MomentumSpectra.cpp:98-107)
-__global__ __launch_bounds__(64, 1) void k_aniso(AnisoArgs A) {
-  const long chain = blockIdx.x;
-  const int lane = threadIdx.x;
-  __shared__ double s_etab[kExpTabN];                       // aniso_math.h aexp
-  for (int i = lane; i < kExpTabN; i += 64) s_etab[i] = kExp2Tab[i];
-  __syncthreads();
-  Hadrons h = A.h;
-  h.etab = s_etab;
-  double state[4] = {0.0, 0.0, 0.0, 0.0};
-  long cnt[3] = {0, 0, 0};
-  for (long c = A.c0 + chain; c < A.c0 + A.n; c += A.chains) {
-    if (A.rec[c * NREC + R_KIND] == 0.0) continue;
-    double ain[4];
-#pragma unroll
-    for (int f = 0; f < 4; f++) ain[f] = A.ain[(long)f * A.stride + c];
-    double out[6];
-    aniso_cell(ain, h, lane, 64, WaveSum(), A.fp2, state, out, cnt);
-    if (lane == 0) {
-#pragma unroll
-      for (int f = 0; f < 6; f++) A.sol[(long)f * A.stride + c] = out[f];
-    }
-  }
-  if (lane == 0) {
-    if (cnt[0]) atomicAdd(&A.cnt[1], (unsigned long long)cnt[0]);
-    if (cnt[1]) atomicAdd(&A.cnt[2], (unsigned long long)cnt[1]);
-    if (cnt[2]) atomicAdd(&A.cnt[3], (unsigned long long)cnt[2]);
-  }
-}
-
-// ---- PTMA warm-start chains (MomentumSpectra.cpp:1308-1364) in parallel segments -----------------------
-// The reference warm-starts each cell's Newton solve from the chain state the previous cell of its OpenMP
-// thread left (chain c = cells c, c + C, c + 2C, ...; the shipped serial build is one chain).  That state
-// recurrence is serial, and a lone wavefront walking it is latency-bound (354 us per cell on MI355X:
-// 1e5 cells took 35 s).  The chain is instead cut into segments of L positions, one wavefront each:
-//   pass 0      every segment runs its cells from a cold start (exact for each chain's first segment);
-//   pass j >= 1 a segment whose incoming state (the end state the previous segment left in pass j - 1)
-//               differs bitwise from the start its stored run used re-runs from the new start, and stops
-//               at the first cell whose new chain state equals the stored one: from there on the stored
-//               cells were computed from that same state, so they stand.  A segment that reaches its end
-//               without re-synchronising publishes a new end state and flags pass j as changed.
-// The passes stop once a pass changes nothing; then every segment's stored run starts from its
-// predecessor's true end state, i.e. the stored states and solutions are the serial chain's, bit for bit.
-// A chain state differs from a cold-start guess for ~10 cells on average before the Newton solves forget it
-// (CPU sweep study, tests/native/cf_emulator.cpp emu_chain_sweeps), so a pass re-runs little.  After
-// kChainPasses passes a single-wavefront finisher completes any remaining ripple serially (exact).
-constexpr int kChainPasses = 24;
-
-struct ChainArgs {
-  const double* rec; const double* ain; double* sol;   // ain [9][n], sol [6][n]
-  double* sta;           // [4][n] chain state after each cell (prev_ok, lambda, aT, aL)
-  int* info;             // [n] Newton iterations | pl/pt < 0 << 16 | reconstruction failure << 17
-  double* send;          // [2][4][nseg] segment end states, by pass parity
-  double* sstart;        // [4][nseg] the start state of each segment's stored run
-  int* changed;          // [kChainPasses] pass j changed some segment's end state
-  long n, C, L, nspc;    // cells, chains, positions per segment, segments per chain
-  // positions [q0, q1) of every chain (cells [q0 C, q1 C)): the whole chain on one engine; a device group's shard
-  // solves its own range, starting each chain from the end state its predecessor shard pushes into bin
-  long q0, q1;
-  int has_pred;          // q0 > 0: chain position q0 - 1 lives on the previous shard
-  int npass;             // passes enqueued (<= kChainPasses)
-  double* bin;           // [3][4 C + 1] boundary in: end states of position q0 - 1 by pass parity, [2] = final + walk flag
-  double* bout;          // [3][4 C + 1] boundary out: this range's end states (position q1 - 1), same slots
-  Hadrons h;
-  double fp2;
-};
-constexpr int kBndSlots = 3;   // bin / bout slots: pass parity 0, 1 and the finisher's
-
-__device__ __forceinline__ bool state_eq(const double* a, const double* b) {
-  bool eq = true;
-#pragma unroll
-  for (int f = 0; f < 4; f++) eq = eq && (__double_as_longlong(a[f]) == __double_as_longlong(b[f]));
-  return eq;
-}
-
-// Run segment `seg` from `state` (its start): re-run mode (sync) stops at the first cell whose new state equals
-// the stored one and returns true (end state unchanged); otherwise the state after the last cell is in `state`.
-__device__ bool chain_segment_run(const ChainArgs& A, Hadrons h, long seg, double* state, bool sync) {
-  const int lane = threadIdx.x;
-  __shared__ double s_red[kRedN * IS3D_CHAIN_W];
-  const long c = seg / A.nspc, s = seg % A.nspc;
-  const long P = min((A.n - c + A.C - 1) / A.C, A.q1);      // positions of chain c in this range's end
-  const long p0 = A.q0 + s * A.L, p1 = min(P, p0 + A.L);
-  for (long pos = p0; pos < p1; pos++) {
-    const long cell = c + pos * A.C;
-    if (A.rec[cell * NREC + R_KIND] == 0.0) continue;       // u.dsigma <= 0: not in the chain (:1146)
-    double ain[4];
-#pragma unroll
-    for (int f = 0; f < 4; f++) ain[f] = A.ain[(long)f * A.n + cell];
-    // the stored state is read before the solve: its barriers keep lane 0's store below from racing a lagging
-    // wavefront's read
-    double old[4];
-#pragma unroll
-    for (int f = 0; f < 4; f++) old[f] = A.sta[(long)f * A.n + cell];
-    double out[6];
-    long cnt[3] = {0, 0, 0};
-    aniso_cell(ain, h, lane, 64 * IS3D_CHAIN_W, BlockSum<IS3D_CHAIN_W>{s_red}, A.fp2, state, out, cnt);
-    const bool same = sync && state_eq(state, old);
-    if (lane == 0) {
-#pragma unroll
-      for (int f = 0; f < 6; f++) A.sol[(long)f * A.n + cell] = out[f];
-#pragma unroll
-      for (int f = 0; f < 4; f++) A.sta[(long)f * A.n + cell] = state[f];
-      A.info[cell] = (int)cnt[2] | ((int)cnt[0] << 16) | ((int)cnt[1] << 17);
-    }
-    if (same) return true;
-  }
-  return false;
-}
-
-// the chain kernels' Hadrons with the LDS exp table of aniso_math.h's aexp (filled by the whole workgroup)
-__device__ __forceinline__ Hadrons chain_hadrons(const ChainArgs& A, double* s_etab) {
-  for (int i = threadIdx.x; i < kExpTabN; i += blockDim.x) s_etab[i] = kExp2Tab[i];
-  __syncthreads();
-  Hadrons h = A.h;
-  h.etab = s_etab;
-  return h;
-}
-
-// one workgroup of IS3D_CHAIN_W wavefronts per segment (the lanes share each Newton evaluation's terms); every
-// branch below is uniform over the workgroup (the reductions hand all lanes the same bits)
-__global__ __launch_bounds__(64 * IS3D_CHAIN_W, 1) void k_chain_pass(ChainArgs A, int pass) {
-  const long seg = blockIdx.x, nseg = A.C * A.nspc;
-  const long c = seg / A.nspc, s = seg % A.nspc;
-  const int lane = threadIdx.x;
-  const long bw = 4 * A.C + 1;
-  // converged: the remaining passes are no-ops (a shard with a predecessor always checks its starts: the boundary
-  // pushed in may still move)
-  if (pass > 0 && A.changed[pass - 1] == 0 && !A.has_pred) return;
-  __shared__ double s_etab[kExpTabN];
-  const Hadrons h = chain_hadrons(A, s_etab);
-  const double* prev = A.send + (long)((pass + 1) & 1) * 4 * nseg;
-  double* cur = A.send + (long)(pass & 1) * 4 * nseg;
-  double state[4] = {0.0, 0.0, 0.0, 0.0};                   // cold: no previous success in this chain
-  bool done = false;
-  if (pass > 0) {
-    double st0[4], used[4];
-#pragma unroll
-    for (int f = 0; f < 4; f++) used[f] = A.sstart[f * nseg + seg];
-    if (s == 0) {
-      const double* b = A.bin + (long)((pass - 1) & 1) * bw;
-#pragma unroll
-      for (int f = 0; f < 4; f++) st0[f] = A.has_pred ? b[f * A.C + c] : 0.0;
-    } else {
-#pragma unroll
-      for (int f = 0; f < 4; f++) st0[f] = prev[f * nseg + seg - 1];
-    }
-    if (state_eq(st0, used)) {                              // same start: the stored run stands
-      done = true;
-    } else {
-#pragma unroll
-      for (int f = 0; f < 4; f++) state[f] = st0[f];
-    }
-    if (IS3D_CHAIN_W > 1) __syncthreads();   // every wavefront has read sstart before lane 0 rewrites it
-    if (done && lane == 0) for (int f = 0; f < 4; f++) cur[f * nseg + seg] = prev[f * nseg + seg];
-  }
-  if (!done) {
-    if (lane == 0) for (int f = 0; f < 4; f++) A.sstart[f * nseg + seg] = state[f];
-    const bool synced = chain_segment_run(A, h, seg, state, pass > 0);
-    if (lane == 0) {
-      if (synced) {
-        for (int f = 0; f < 4; f++) cur[f * nseg + seg] = prev[f * nseg + seg];
-      } else {
-        bool moved = pass == 0;
-        for (int f = 0; f < 4; f++) {
-          moved = moved || __double_as_longlong(state[f]) != __double_as_longlong(prev[f * nseg + seg]);
-          cur[f * nseg + seg] = state[f];
-        }
-        if (moved && pass > 0) atomicOr(&A.changed[pass], 1);
-      }
-    }
-    // pass 0 ran cold starts: exact only for the first segment of a range without a predecessor, so it flags a
-    // change whenever some segment may be wrong (a finisher after a single pass must then walk)
-    if (pass == 0 && lane == 0 && (A.nspc > 1 || A.has_pred)) atomicOr(&A.changed[0], 1);
-  }
-  // pass 0 fills both parity slots: a range without a predecessor and with one segment per chain is exact after
-  // pass 0 and flags nothing, so passes 1.. return early above and never write slot 1 -- which the finisher's
-  // no-walk copy and the successor shard's odd-pass boundary read
-  if (pass == 0 && lane == 0) {
-    double* other = A.send + 4 * nseg;
-    for (int f = 0; f < 4; f++) other[f * nseg + seg] = cur[f * nseg + seg];
-  }
-  // the range's last segment of chain c: its end state is the next shard's boundary in
-  if (s == A.nspc - 1 && lane == 0) {
-    for (int slot = pass & 1; slot <= (pass == 0 ? 1 : (pass & 1)); slot++) {
-      double* b = A.bout + (long)slot * bw;
-      for (int f = 0; f < 4; f++) b[f * A.C + c] = cur[f * nseg + seg];
-    }
-  }
-}
-
-// Serial completion after the passes (one wavefront; normally returns at once): segments in chain order, each
-// from its predecessor's current end state -- exact by induction.  It walks when this range's last pass changed
-// something or the predecessor shard walked (bin[2] flag); either way it leaves the range's final end states and
-// its walk flag in bout[2] for the next shard.
-__global__ __launch_bounds__(64 * IS3D_CHAIN_W) void k_chain_finish(ChainArgs A) {
-  const long nseg = A.C * A.nspc, bw = 4 * A.C + 1;
-  double* cur = A.send + (long)((A.npass - 1) & 1) * 4 * nseg;
-  const double* bfin = A.bin + 2 * bw;
-  double* bo = A.bout + 2 * bw;
-  const int lane = threadIdx.x;
-  const bool walk = A.changed[A.npass - 1] != 0 || (A.has_pred && bfin[4 * A.C] != 0.0);
-  if (!walk) {
-    if (lane == 0) {
-      for (long c = 0; c < A.C; c++)
-        for (int f = 0; f < 4; f++) bo[f * A.C + c] = cur[f * nseg + c * A.nspc + A.nspc - 1];
-      bo[4 * A.C] = 0.0;
-    }
-    return;
-  }
-  __shared__ double s_etab[kExpTabN];
-  const Hadrons h = chain_hadrons(A, s_etab);
-  // the running end state stays in registers (uniform over the wavefront): no memory round trip between
-  // segments, and every array element this kernel reads was written by an earlier launch or not at all
-  double carry[4] = {0.0, 0.0, 0.0, 0.0};
-  for (long seg = 0; seg < nseg; seg++) {
-    const long c = seg / A.nspc, s = seg % A.nspc;
-    if (s == 0) {
-#pragma unroll
-      for (int f = 0; f < 4; f++) carry[f] = A.has_pred ? bfin[f * A.C + c] : 0.0;
-    }
-    double used[4];
-#pragma unroll
-    for (int f = 0; f < 4; f++) used[f] = A.sstart[f * nseg + seg];
-    const bool same = state_eq(carry, used);
-    if (IS3D_CHAIN_W > 1) __syncthreads();   // every wavefront has read sstart before lane 0 rewrites it
-    if (same) {
-#pragma unroll
-      for (int f = 0; f < 4; f++) carry[f] = cur[f * nseg + seg];
-    } else {
-      if (lane == 0) for (int f = 0; f < 4; f++) A.sstart[f * nseg + seg] = carry[f];
-      double state[4] = {carry[0], carry[1], carry[2], carry[3]};
-      if (chain_segment_run(A, h, seg, state, true)) {
-#pragma unroll
-        for (int f = 0; f < 4; f++) carry[f] = cur[f * nseg + seg];
-      } else {
-#pragma unroll
-        for (int f = 0; f < 4; f++) carry[f] = state[f];
-        if (lane == 0) for (int f = 0; f < 4; f++) cur[f * nseg + seg] = state[f];
-      }
-    }
-    if (s == A.nspc - 1 && lane == 0) for (int f = 0; f < 4; f++) bo[f * A.C + c] = carry[f];
-  }
-  if (lane == 0) bo[4 * A.C] = 1.0;
-}
-
-// the serial chain's counters from the per-cell records: [1] pl/pt < 0, [2] reconstruction failures,
-// [3] Newton iterations
-__global__ __launch_bounds__(256) void k_chain_count(const double* rec, const int* info, long c_lo, long c_hi,
-                                                     unsigned long long* cnt) {
-  __shared__ unsigned long long s[3][256];
-  unsigned long long a = 0, b = 0, it = 0;
-  for (long c = c_lo + (long)blockIdx.x * 256 + threadIdx.x; c < c_hi; c += (long)gridDim.x * 256) {
-    if (rec[c * NREC + R_KIND] == 0.0) continue;
-    const int v = info[c];
-    it += (unsigned)(v & 0xffff); a += (v >> 16) & 1; b += (v >> 17) & 1;
-  }
-  s[0][threadIdx.x] = a; s[1][threadIdx.x] = b; s[2][threadIdx.x] = it;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o)
-      for (int k = 0; k < 3; k++) s[k][threadIdx.x] += s[k][threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    if (s[0][0]) atomicAdd(&cnt[1], s[0][0]);
-    if (s[1][0]) atomicAdd(&cnt[2], s[1][0]);
-    if (s[2][0]) atomicAdd(&cnt[3], s[2][0]);
-  }
-}
-
-__global__ __launch_bounds__(256) void k_famod_b(PrepArgs A, const double* sol) {
-  const long c = A.c0 + (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= A.c1) return;
-  if (A.rec[c * NREC + R_KIND] == 0.0) return;
-  double R[NREC], ain[9], so[6];
-#pragma unroll
-  for (int f = 0; f < NREC; f++) R[f] = A.rec[c * NREC + f];
-#pragma unroll
-  for (int f = 0; f < 9; f++) ain[f] = A.aux[(long)f * A.n + c];
-#pragma unroll
-  for (int f = 0; f < 6; f++) so[f] = sol[(long)f * A.n + c];
-  int broken = 0;
-  prep_famod_b(A.k, R, ain, so, &broken);
-  if (broken) atomicAdd(&A.cnt[0], 1ull);
-#pragma unroll
-  for (int f = 0; f < NREC; f++) A.rec[c * NREC + f] = R[f];
-}
-
-struct RenormArgs {
-  PrepConsts k;
-  const double* rec; const double* aux; double* renorm;   // renorm[c - c0][class]
-  const double *mass, *sign, *degen, *baryon;              // sorted species
-  const int* rrep;                                         // representative sorted species of each class
-  long c0, n, stride; int npart;                           // cells [c0, c0 + n) of stride held; npart = classes
-};
-
-__global__ __launch_bounds__(256) void k_renorm(RenormArgs A) {
-  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= A.n * A.npart) return;
-  const long c = A.c0 + idx / A.npart;
-  const int s = A.rrep[(int)(idx % A.npart)];
-  if (A.rec[c * NREC + R_KIND] == 0.0) { A.renorm[idx] = 0.0; return; }
-  double aux[9];
-#pragma unroll
-  for (int f = 0; f < 9; f++) aux[f] = A.aux[(long)f * A.stride + c];
-  A.renorm[idx] = ptm_renorm(A.k, aux, A.mass[s], A.sign[s], A.degen[s], A.baryon[s]);
-}
-
-// per-cell cost estimate (is3d_cell_costs) from the prepared records
-__global__ __launch_bounds__(256) void k_cell_cost(const double* rec, long n, double fb_cost, double* cost) {
-  const long c = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= n) return;
-  const double* R = rec + c * NREC;
-  const bool fb = R[R_KIND] == 1.0 || (R[R_KIND] == 2.0 && R[R_NARROW] != 0.0);
-  cost[c] = R[R_KIND] == 0.0 ? kSkipCost : (fb_cost > 0.0 && fb) ? fb_cost : 1.0;
-}
-
-// Modified modes: the cells whose lanes may take the separable fallback (breakdown: R_KIND == 1; narrow
-// rapidity windows: R_NARROW != 0, MomentumSpectra.cpp:863-871), listed in ascending order for the F_FB
-// launch.  kFbBlocks workgroups each own a contiguous cell range: k_fbcount counts each range's cells, k_fbwrite
-// writes them in order after the counts of the ranges before it (wave ballots + an LDS prefix per 256 cells) --
-// deterministic, and no host round trip (the count stays on the device).  (One workgroup walking per-thread chunks
-// took 44 ms per config-5 pass, 5e6 cells.)
-constexpr int kFbBlocks = 1024;
-
-__device__ __forceinline__ bool fb_cell(const double* rec, long c) {
-  const double* R = rec + c * NREC;
-  return R[R_KIND] == 1.0 || (R[R_KIND] == 2.0 && R[R_NARROW] != 0.0);
-}
-
-__global__ __launch_bounds__(256) void k_fbcount(const double* rec, long n, int* bcnt) {
-  const long ch = (n + kFbBlocks - 1) / kFbBlocks, lo = min(n, (long)blockIdx.x * ch), hi = min(n, lo + ch);
-  int cnt = 0;
-  for (long c = lo + threadIdx.x; c < hi; c += 256) cnt += fb_cell(rec, c) ? 1 : 0;
-  __shared__ int s[256];
-  s[threadIdx.x] = cnt;
-  __syncthreads();
-  for (int d = 128; d > 0; d >>= 1) {
-    if (threadIdx.x < d) s[threadIdx.x] += s[threadIdx.x + d];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) bcnt[blockIdx.x] = s[0];
-}
-
-__global__ __launch_bounds__(256) void k_fbwrite(const double* rec, long n, const int* bcnt, int* cells, int* count) {
-  const long ch = (n + kFbBlocks - 1) / kFbBlocks, lo = min(n, (long)blockIdx.x * ch), hi = min(n, lo + ch);
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  __shared__ int s_base, s_w[4];
-  if (t == 0) {
-    int o = 0;
-    for (int b = 0; b < (int)blockIdx.x; b++) o += bcnt[b];
-    s_base = o;
-    if (blockIdx.x == kFbBlocks - 1) *count = o + bcnt[blockIdx.x];
-  }
-  __syncthreads();
-  for (long c0 = lo; c0 < hi; c0 += 256) {
-    const long c = c0 + t;
-    const bool f = c < hi && fb_cell(rec, c);
-    const unsigned long long m = __ballot(f);
-    if (lane == 0) s_w[wave] = __popcll(m);
-    __syncthreads();
-    int o = s_base;
-    for (int w = 0; w < wave; w++) o += s_w[w];
-    if (f) cells[o + __popcll(m & ((1ull << lane) - 1ull))] = (int)c;
-    __syncthreads();
-    if (t == 0) s_base += s_w[0] + s_w[1] + s_w[2] + s_w[3];
-    __syncthreads();
-  }
-}
-
-// the ascending fallback-cell list of nw records into list[1 ..], its length into list[0]; list holds nw + 1 +
-// kFbBlocks ints (the per-range counts after the list)
-static void enqueue_fbscan(const double* rec, long nw, int* list, hipStream_t st) {
-  int* bcnt = list + 1 + nw;
-  hipLaunchKernelGGL(k_fbcount, dim3(kFbBlocks), dim3(256), 0, st, rec, nw, bcnt);
-  hipLaunchKernelGGL(k_fbwrite, dim3(kFbBlocks), dim3(256), 0, st, rec, nw, (const int*)bcnt, list + 1, list);
-}
-
-struct ReduceArgs {
-  const double* slab; long sstride; int nsplit;
-  int nbx, npart, npT, nphi, nk, nl, ny_out, kj; long ntask;   // npart: lane species (integrand classes)
-  const int* sorig; const double* degen_orig; double prefactor;
-  const int *cmem_off, *cmem;   // member sorted species of each class
-  double* out;
-  const unsigned long long* gate; int gate_want;   // launch_end's device-side plan choice (kernels.h SpecArgs)
-};
-
-// every member species of class c gets (2 pi hbarc)^-3 g_s x the class's sum
-__device__ __forceinline__ void write_members(const ReduceArgs& A, int c, long off, double acc, int m0, int dm) {
-  for (int m = A.cmem_off[c] + m0; m < A.cmem_off[c + 1]; m += dm) {
-    const int so = A.sorig[A.cmem[m]];
-    A.out[(long)so * A.npT * A.nphi * A.ny_out + off] = A.prefactor * A.degen_orig[so] * acc;
-  }
-}
-
-// dN[s][pT][phi][y] = (2 pi hbarc)^-3 g_s * sum over eta nodes (2+1D) and cell splits, in fixed order.
-// One thread per slab entry of an l = 0 lane; the lanes of the other eta nodes of the same (class, y,
-// phi block) are task + l * npart.
-__global__ __launch_bounds__(256) void k_reduce(ReduceArgs A) {
-  if (gate_closed(A.gate, A.gate_want)) return;
-  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= A.sstride) return;
-  const int KJ = A.kj;
-  const int lane = (int)(e % kBlock);
-  const int jj = (int)((e / kBlock) % KJ);
-  const long rest = e / ((long)kBlock * KJ);
-  const int lane_group = (int)(rest % A.nbx), ipt = (int)(rest / A.nbx);
-  const long task = (long)lane_group * kBlock + lane;
-  if (task >= A.ntask) return;
-  const int s = (int)(task % A.npart);
-  const long r = task / A.npart;
-  const long nq = (long)A.nk * A.nl;
-  const int q = (int)(r % nq);
-  if (q % A.nl != 0) return;
-  const int k = q / A.nl, j = (int)(r / nq) * KJ + jj;
-  if (j >= A.nphi) return;
-  double acc = 0.0;
-  for (int l = 0; l < A.nl; l++) {
-    const long tl = task + (long)l * A.npart;
-    const long el = ((long)ipt * A.nbx + tl / kBlock) * ((long)KJ * kBlock) + (long)jj * kBlock + tl % kBlock;
-    for (int z = 0; z < A.nsplit; z++) acc += A.slab[(long)z * A.sstride + el];
-  }
-  write_members(A, s, ((long)ipt * A.nphi + j) * A.ny_out + k, acc, 0, 1);
-}
-
-// The same sum with one wavefront per output entry, for slabs with many (eta node, cell split) terms per
-// output (2+1D: 24 eta nodes x hundreds of splits -- the per-thread loop above ran 8k dependent loads per
-// output and took 2.4 ms for pikp 1e5 cells): lane i adds terms i, i + 64, ... of the (l, split) list,
-// then a fixed xor-shuffle tree combines the lanes, so the order stays fixed (bit-reproducible).
-__global__ __launch_bounds__(256) void k_reduce_wave(ReduceArgs A) {
-  if (gate_closed(A.gate, A.gate_want)) return;
-  const long o = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int lane = threadIdx.x & 63;
-  const long nout = (long)A.npart * A.npT * A.nphi * A.ny_out;
-  if (o >= nout) return;                                   // whole wavefronts exit together
-  const int k = (int)(o % A.ny_out);
-  const long r1 = o / A.ny_out;
-  const int j = (int)(r1 % A.nphi);
-  const long r2 = r1 / A.nphi;
-  const int ipt = (int)(r2 % A.npT), s = (int)(r2 / A.npT);
-  const int KJ = A.kj, jb = j / KJ, jj = j % KJ;
-  const long nq = (long)A.nk * A.nl;
-  const long task0 = s + (long)A.npart * (k * A.nl + nq * jb);
-  const long nterm = (long)A.nl * A.nsplit;
-  double acc = 0.0;
-  for (long m = lane; m < nterm; m += 64) {
-    const int l = (int)(m / A.nsplit), z = (int)(m % A.nsplit);
-    const long tl = task0 + (long)l * A.npart;
-    const long el = ((long)ipt * A.nbx + tl / kBlock) * ((long)KJ * kBlock) + (long)jj * kBlock + tl % kBlock;
-    acc += A.slab[(long)z * A.sstride + el];
-  }
-#pragma unroll
-  for (int w = 32; w >= 1; w >>= 1) acc += __shfl_xor(acc, w, 64);
-  write_members(A, s, ((long)ipt * A.nphi + j) * A.ny_out + k, acc, lane, 64);
-}
-
-// Chunk-wise slab fold (folded F_TS launches, enqueue_spectra): acc[i] = (init ? 0 : acc[i]) + src[0][i] + ... +
-// src[ns - 1][i], added in split order, so the folded accumulator equals k_reduce's sequential sum over all splits
-// bit for bit (3+1D: one term per split and output).  Memory-bound: ns + 2 doubles per entry.
-__global__ __launch_bounds__(256) void k_fold(double* acc, const double* src, long sstride, int ns, int init,
-                                              const unsigned long long* gate, int gate_want) {
-  if (gate_closed(gate, gate_want)) return;      // the other plan of a gated pair runs (launch_end)
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < sstride; i += (long)gridDim.x * blockDim.x) {
-    double a = init ? 0.0 : acc[i];
-    for (int z = 0; z < ns; z++) a += src[(long)z * sstride + i];
-    acc[i] = a;
-  }
-}
-
-// per-cell spacetime bin indices (SpacetimeDistribution.cpp:380-392): keys[0..2][c] = itau, ir, iphi (-1 outside)
-struct KeyArgs {
-  const double *tau, *x, *y; long n;
-  double tau_min, tau_width, r_min, r_width, phip_width;
-  int tau_bins, r_bins, phip_bins;
-  int* keys;
-};
-
-__global__ __launch_bounds__(256) void k_stkeys(KeyArgs A) {
-  const long c = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= A.n) return;
-  const double two_pi = 2.0 * M_PI;
-  const double x = A.x[c], y = A.y[c], tau = A.tau[c];
-  const double r = sqrt(x * x + y * y);
-  double phi = atan2(y, x);
-  if (phi < 0.0) phi += two_pi;
-  const long itau = (int)floor((tau - A.tau_min) / A.tau_width);
-  const long ir = (int)floor((r - A.r_min) / A.r_width);
-  const long iphi = (int)floor(phi / A.phip_width);
-  A.keys[c] = (itau >= 0 && itau < A.tau_bins) ? (int)itau : -1;
-  A.keys[A.n + c] = (ir >= 0 && ir < A.r_bins) ? (int)ir : -1;
-  A.keys[2 * A.n + c] = (iphi >= 0 && iphi < A.phip_bins) ? (int)iphi : -1;
-}
-
-// part[s_orig][e] = prefactor g_s x sum over the cells of entry e = (distribution, thread slice n, bin),
-// cells in ascending order (the reference's per-thread order); perm/offs: CSR built on the host
-struct BinArgs {
-  const double* ycell; long n; int npart;          // ycell: [class][n]; npart sorted species
-  const int *perm; const long* offs; long nent;
-  const int* sorig; const double* sdegen; double prefactor;
-  const int* scls;                                  // sorted species -> integrand class
-  double* part;
-};
-
-__global__ __launch_bounds__(256) void k_stbin(BinArgs A) {
-  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= A.nent * A.npart) return;
-  const int s = (int)(idx / A.nent);
-  const long e = idx % A.nent;
-  const double f = A.prefactor * A.sdegen[s];
-  double acc = 0.0;
-  for (long i = A.offs[e]; i < A.offs[e + 1]; i++) {
-    acc += f * A.ycell[(long)A.scls[s] * A.n + A.perm[i]];
-  }
-  A.part[(long)A.sorig[s] * A.nent + e] = acc;
-}
-
-// ------------------------------------------------------------------------------------------
-// operation = 2 oversampling estimate (ParticleSampler.cpp:447-636, DeltafData.cpp:555-690)
-// ------------------------------------------------------------------------------------------
-struct DensArgs {
-  DfTables tb;
-  const double *gla;              // [alpha][pts] roots then [alpha][pts] weights
-  int gla_alpha, gla_pts;
-  double T, E, P, muB, nB;        // Plasma averages
-  const double *smass, *ssign, *sdegen, *sbaryon; const int* sorig;
-  int npart, df_mode;
-  double two_pi2_hbarC3;
-  double* dens;                   // [3][npart] original species order
-  int* err;
-};
-
-// one wavefront per (mass-sorted) species: lane k holds Gauss-Laguerre node k of each alpha
-__global__ __launch_bounds__(64) void k_densities(DensArgs A) {
-  const int s = blockIdx.x, lane = threadIdx.x;
-  DfCoef df;
-  const int err = df_eval(A.tb, A.T, A.muB, A.E, A.P, 0.0, df);     // DeltafData.cpp:574
-  if (err) { if (lane == 0) atomicMax(A.err, err); return; }
-  const double mass = A.smass[s], sign = A.ssign[s], baryon = A.sbaryon[s];
-  const double mbar = mass / A.T, chem = baryon * (A.muB / A.T);
-  const double* W = A.gla + (long)A.gla_alpha * A.gla_pts;
-  static constexpr int kAlpha[6] = {1, 1, 1, 2, 3, 3};
-  double J[6];
-  WaveSum ws;
-#pragma unroll
-  for (int q = 0; q < 6; q++) {
-    double v = 0.0;
-    for (int k = lane; k < A.gla_pts; k += 64) {
-      const long o = (long)kAlpha[q] * A.gla_pts + k;
-      v += W[o] * gt_term(q, A.gla[o], mbar, chem, sign);
-    }
-    J[q] = ws(v);
-  }
-  if (lane == 0) {
-    double d3[3];
-    species_densities(A.df_mode, df, A.T, A.nB / (A.E + A.P), mass, A.sdegen[s], baryon, J, A.two_pi2_hbarC3, d3);
-    const int so = A.sorig[s];
-    for (int i = 0; i < 3; i++) A.dens[(long)i * A.npart + so] = d3[i];
-  }
-}
-
-struct YieldArgs {
-  PrepConsts k;
-  DfTables tb;
-  const double* surf; long n;
-  const double* dens; int npart;
-  double* partial;                // [gridDim.x] per-block sums
-  int* err;
-};
-
-// one thread per cell, fixed-order tree sum per block (bit-reproducible); the host adds the blocks in order
-__global__ __launch_bounds__(256) void k_yield(YieldArgs A) {
-  __shared__ double red[256];
-  __shared__ double dsum[3];
-  const int tid = threadIdx.x;
-  if (tid < 3) {                  // species sums in species order
-    double a = 0.0;
-    for (int i = 0; i < A.npart; i++) a += A.dens[(long)tid * A.npart + i];
-    dsum[tid] = a;
-  }
-  __syncthreads();
-  const long c = (long)blockIdx.x * 256 + tid;
-  double v = 0.0;
-  if (c < A.n) {
-    double sv[NSURF];
-#pragma unroll
-    for (int f = 0; f < NSURF; f++) sv[f] = A.surf[(long)f * A.n + c];
-    const int err = yield_cell(A.k, A.tb, sv, dsum, &v);
-    if (err) { atomicMax(A.err, err); v = 0.0; }
-  }
-  red[tid] = v;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) red[tid] += red[tid + o];
-    __syncthreads();
-  }
-  if (tid == 0) A.partial[blockIdx.x] = red[0];
-}
-
-// ------------------------------------------------------------------------------------------
-// PTB "Jonah" table (DeltafData.cpp:220-295): thread (row, hadron) evaluates the two Gauss sums, one
-// thread per row then adds the hadrons in PDG order (the reference's order), so the table is
-// bit-reproducible; row kJonahN holds the lambda = 0 terms.
-// ------------------------------------------------------------------------------------------
-struct JonahArgs {
-  double T; int npdg, pts;
-  const double *mass, *degen, *sign, *r2, *w2;
-  double* terms;                  // [kJonahN + 1][2][npdg]
-  double *l2, *z, *bp;            // [kJonahN] each
-};
-
-__global__ __launch_bounds__(256) void k_jonah_terms(JonahArgs A) {
-  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= (long)(kJonahN + 1) * A.npdg) return;
-  const int i = (int)(idx / A.npdg), n = (int)(idx % A.npdg);
-  const double lambda = (i < kJonahN) ? jonah_lambda(i) : 0.0;
-  double* t = A.terms + (long)i * 2 * A.npdg;
-  jonah_terms(A.T, A.mass[n], A.degen[n], A.sign[n], A.r2, A.w2, A.pts, lambda, t + n, t + A.npdg + n);
-}
-
-__global__ __launch_bounds__(64) void k_jonah_sum(JonahArgs A) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= kJonahN) return;
-  const double* e0 = A.terms + (long)kJonahN * 2 * A.npdg;
-  const double* p0 = e0 + A.npdg;
-  const double* em = A.terms + (long)i * 2 * A.npdg;
-  const double* pm = em + A.npdg;
-  double E = 0.0, P = 0.0, Em = 0.0, Pm = 0.0;
-  for (int n = 0; n < A.npdg; n++) {
-    if (A.mass[n] == 0.0) continue;
-    E += e0[n]; P += p0[n]; Em += em[n]; Pm += pm[n];
-  }
-  jonah_row(i, E, P, Em, Pm, A.l2, A.z, A.bp);
-}
-
-__global__ void k_df_eval(DfTables tb, double T, double muB, double E, double P, double bulkPi, double* out, int* err) {
-  DfCoef df;
-  *err = df_eval(tb, T, muB, E, P, bulkPi, df);
-  const double o[15] = {df.c0, df.c1, df.c2, df.c3, df.c4, df.shear14, df.F, df.G, df.betabulk, df.betaV, df.betapi,
-                        df.lambda, df.z, df.dlambda, df.dz};
-  for (int i = 0; i < 15; i++) out[i] = o[i];
-}
-
-template <class T>
-T* dalloc(size_t count) {
-  void* p = nullptr;
-  if (count == 0) count = 1;
-  if (hipMalloc(&p, count * sizeof(T)) != hipSuccess) return nullptr;
-  return (T*)p;
-}
-
-}  // namespace
+#include "engine_kernels.h"   // this unit's device code (k_prep ... k_df_eval)
 
 // ------------------------------------------------------------------------------------------
 // engine
@@ -874,10 +115,10 @@ struct is3d_engine {
   std::vector<double> jl2, jz, jx, jl2c, jzc;
   double bp_max = -1.0;
   bool tables_dirty = true;
-  // device
-  double* d_tables = nullptr; size_t tables_len = 0;
+  // device: every allocation is a DevBuf member (devbuf.h); the raw pointers below are views into d_tables / d_const
+  DevBuf<double> d_tables;
   DfTables dtb{};
-  double* d_const = nullptr; size_t const_len = 0;    // species, grids, gla, pdg
+  DevBuf<double> d_const;    // species, grids, gla, pdg
   const double *d_smass = nullptr, *d_ssign = nullptr, *d_sbaryon = nullptr, *d_sdegen = nullptr, *d_degen_orig = nullptr;
   const double* d_csg = nullptr;   // [npT][nphp] {pT cos, pT sin}
   const double *d_pT = nullptr, *d_cphi = nullptr, *d_sphi = nullptr, *d_y = nullptr, *d_eta = nullptr, *d_etaw = nullptr;
@@ -904,16 +145,15 @@ struct is3d_engine {
   std::vector<int> scls;   // host copy of d_scls
   const double *d_cmass = nullptr, *d_csign = nullptr, *d_cbaryon = nullptr;
   int *d_crcls = nullptr, *d_cmem_off = nullptr, *d_cmem = nullptr, *d_scls = nullptr;
-  double* d_surf = nullptr; bool surf_owned = false; long ncell = 0; long surf_cap = 0;
-  double* d_chain = nullptr; long chain_cap = 0;   // PTMA warm-start chain segments (k_chain_pass)
-  double *d_rec = nullptr, *d_aux = nullptr, *d_sol = nullptr, *d_renorm = nullptr, *d_slab = nullptr, *d_out = nullptr;
-  long rec_cap = 0, aux_cap = 0, sol_cap = 0, renorm_cap = 0, slab_cap = 0, out_cap = 0;
-  int* d_fb = nullptr;        // modified modes: [0] fallback cell count, [1..] k_fbwrite's cell list
-  long fb_cap = 0;
-  double* d_phtab = nullptr;  // F_TS launches: k_phitab's per-(cell, pT, phi) rows of one chunk of cells
-  long phtab_cap = 0;
-  double* d_phtab2 = nullptr; // ... and of the next chunk, integrated on the side stream meanwhile
-  long phtab2_cap = 0;
+  // the surface [NSURF][ncell]: a view of surf_own (an uploaded or copied surface) or of the caller's device memory
+  // (is3d_set_surface_device; surf_own is then empty)
+  double* d_surf = nullptr; long ncell = 0;
+  DevBuf<double> surf_own;
+  DevBuf<double> d_chain;     // PTMA warm-start chain segments (k_chain_pass)
+  DevBuf<double> d_rec, d_aux, d_sol, d_renorm, d_slab, d_out;
+  DevBuf<int> d_fb;           // modified modes: [0] fallback cell count, [1..] k_fbwrite's cell list
+  DevBuf<double> d_phtab;     // F_TS launches: k_phitab's per-(cell, pT, phi) rows of one chunk of cells
+  DevBuf<double> d_phtab2;    // ... and of the next chunk, integrated on the side stream meanwhile
   hipStream_t side = nullptr; // F_TS chunks alternate between the launch stream and this one
   hipEvent_t fork = nullptr, join = nullptr;
   // folded F_TS chunks: k_fold runs on its own stream, in chunk order, after each chunk's k_spectra
@@ -929,17 +169,17 @@ struct is3d_engine {
   long last_nsplit = 0;       // cell splits of the last launch's main plan
   long last_nslab = 0;        // ... and the output-sized partial slabs it held (folded F_TS chunks: 1 + 2 spc)
   // operation 0
-  double *d_ycell = nullptr, *d_part = nullptr; long ycell_cap = 0, part_cap = 0;
-  int *d_keys = nullptr, *d_perm = nullptr; long keys_cap = 0, perm_cap = 0;
-  long* d_offs = nullptr; long offs_cap = 0;
+  DevBuf<double> d_ycell, d_part;
+  DevBuf<int> d_keys, d_perm;
+  DevBuf<long> d_offs;
   long ycell_n = -1;
-  int* d_err = nullptr;
-  unsigned long long* d_cnt = nullptr;
+  DevBuf<int> d_err;                  // the device error word (cf_math.h DF_*)
+  DevBuf<unsigned long long> d_cnt;   // [8] counters (PrepArgs::cnt)
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   LaunchCtx lc;               // the launch in flight (staged launches)
   // spin polarization (mode 5, polzn.hip): thermal vorticity [6][ncell] of the surface set last (a new surface
   // clears it) and the kernels' constants, rebuilt after a species / classes / grid / params change
-  double* d_vort = nullptr; long vort_cap = 0; bool have_vort = false;
+  DevBuf<double> d_vort; bool have_vort = false;
   bool have_surf = false;    // a surface was set (an empty one set from device memory has no d_surf)
   is3d::polzn::Tables pz;
   bool pz_dirty = true;
@@ -956,7 +196,7 @@ struct is3d_engine {
   // integer form (hist_nc counts, then hist_nv fixed-point vn sums)
   is3d_sample_bins sbins{};
   bool have_sbins = false;
-  unsigned long long* d_hist = nullptr; long hist_cap = 0;
+  DevBuf<unsigned long long> d_hist;
   std::vector<long long> hist;
   long hist_nc = 0, hist_nv = 0;
   bool binned = false;
@@ -975,7 +215,18 @@ static int hip_fail(is3d_engine* e, hipError_t h, const char* what) {
     if (h_ != hipSuccess) return hip_fail((e), h_, #x);        \
   } while (0)
 
-static void dfree(void* p) { if (p) (void)hipFree(p); }
+// The device error word (cf_math.h DfErr) as the IS3D_ERR_* code and message of every entry point that reads one; the
+// table errors carry the reference's printed messages.  other: the caller's message for any other nonzero word
+static int df_error(is3d_engine* e, int derr, const char* other) {
+  switch (derr) {
+    case DF_OK: return IS3D_OK;
+    case DF_SPLINE_RANGE: return e->fail(IS3D_ERR_DF_RANGE, "gsl: interp.c: interpolation error (df coefficient spline evaluated outside its table)");
+    case DF_TABLE_RANGE: return e->fail(IS3D_ERR_DF_RANGE, "Error: (T,muB) outside df coefficient table. Exiting...");
+    case DF_PTB_BARYON: return e->fail(IS3D_ERR_UNSUPPORTED, "Bilinear interpolation error: Jonah df doesn't work for nonzero muB. Exiting..");
+    case DF_TS_SLOW: return e->fail(IS3D_ERR_DEVICE, "internal: a scalar-table (F_TS) lane left the fast path (sep_slow_cell bound)");
+    default: return e->fail(IS3D_ERR_ARG, other);
+  }
+}
 
 extern "C" int is3d_abi_version(void) { return IS3D_ABI_VERSION; }
 
@@ -990,7 +241,7 @@ extern "C" is3d_engine* is3d_create(int device) {
   if (hipSetDevice(device) != hipSuccess) return nullptr;
   is3d_engine* e = new is3d_engine();
   e->device = device;
-  if (hipMalloc(&e->d_err, sizeof(int)) != hipSuccess || hipMalloc(&e->d_cnt, 8 * sizeof(unsigned long long)) != hipSuccess) {
+  if (!e->d_err.reserve(1) || !e->d_cnt.reserve(8)) {
     delete e;
     return nullptr;
   }
@@ -1006,22 +257,13 @@ extern "C" void is3d_destroy(is3d_engine* e) {
     return;
   }
   (void)hipSetDevice(e->device);
-  (void)hipDeviceSynchronize();
-  dfree(e->d_tables); dfree(e->d_const);
-  if (e->surf_owned) dfree(e->d_surf);
-  dfree(e->d_chain);
-  dfree(e->d_rec); dfree(e->d_aux); dfree(e->d_sol); dfree(e->d_renorm); dfree(e->d_slab); dfree(e->d_out);
-  dfree(e->d_fb); dfree(e->d_phtab); dfree(e->d_phtab2);
+  (void)hipDeviceSynchronize();     // before the DevBuf members die with *e
   if (e->side) (void)hipStreamDestroy(e->side);
   if (e->fold_st) (void)hipStreamDestroy(e->fold_st);
   for (auto v : {e->ev_spec[0], e->ev_spec[1], e->ev_fold[0], e->ev_fold[1], e->fold_join})
     if (v) (void)hipEventDestroy(v);
   if (e->fork) (void)hipEventDestroy(e->fork);
   if (e->join) (void)hipEventDestroy(e->join);
-  dfree(e->d_ycell); dfree(e->d_part); dfree(e->d_keys); dfree(e->d_perm); dfree(e->d_offs);
-  dfree(e->d_err); dfree(e->d_cnt);
-  dfree(e->d_vort);
-  dfree(e->d_hist);
   is3d::polzn::tables_free(e->pz);
   is3d::sampler::tables_free(e->smp);
   for (auto& v : e->ev) if (v) (void)hipEventDestroy(v);
@@ -1223,24 +465,21 @@ static int device_jonah_table(is3d_engine* e, const double* r2, const double* w2
   in.insert(in.end(), r2, r2 + pts);
   in.insert(in.end(), w2, w2 + pts);
   const size_t nterms = (size_t)(kJonahN + 1) * 2 * npdg, nout = 3 * (size_t)kJonahN;
-  double* d = dalloc<double>(in.size() + nterms + nout);
-  if (!d) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(Jonah table) failed");
+  DevBuf<double> buf;
+  if (!buf.reserve((long)(in.size() + nterms + nout))) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(Jonah table) failed");
+  double* const d = buf.get();
   JonahArgs ja{};
   ja.T = e->T_avg; ja.npdg = npdg; ja.pts = pts;
   ja.mass = d; ja.degen = d + npdg; ja.sign = d + 2 * npdg; ja.r2 = d + 3 * npdg; ja.w2 = d + 3 * npdg + pts;
   ja.terms = d + in.size();
   ja.l2 = ja.terms + nterms; ja.z = ja.l2 + kJonahN; ja.bp = ja.z + kJonahN;
   std::vector<double> out(nout);
-  hipError_t er = hipMemcpy(d, in.data(), in.size() * sizeof(double), hipMemcpyHostToDevice);
-  if (er == hipSuccess) {
-    const long nthr = (long)(kJonahN + 1) * npdg;
-    hipLaunchKernelGGL(k_jonah_terms, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, 0, ja);
-    hipLaunchKernelGGL(k_jonah_sum, dim3((kJonahN + 63) / 64), dim3(64), 0, 0, ja);
-    er = hipGetLastError();
-  }
-  if (er == hipSuccess) er = hipMemcpy(out.data(), ja.l2, nout * sizeof(double), hipMemcpyDeviceToHost);
-  dfree(d);
-  if (er != hipSuccess) return e->fail(IS3D_ERR_DEVICE, std::string("Jonah table: ") + hipGetErrorString(er));
+  HIPCHK(e, hipMemcpy(d, in.data(), in.size() * sizeof(double), hipMemcpyHostToDevice));
+  const long nthr = (long)(kJonahN + 1) * npdg;
+  hipLaunchKernelGGL(k_jonah_terms, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, 0, ja);
+  hipLaunchKernelGGL(k_jonah_sum, dim3((kJonahN + 63) / 64), dim3(64), 0, 0, ja);
+  HIPCHK(e, hipGetLastError());
+  HIPCHK(e, hipMemcpy(out.data(), ja.l2, nout * sizeof(double), hipMemcpyDeviceToHost));
   e->jl2.assign(out.begin(), out.begin() + kJonahN);
   e->jz.assign(out.begin() + kJonahN, out.begin() + 2 * kJonahN);
   e->jx.assign(out.begin() + 2 * kJonahN, out.end());
@@ -1440,20 +679,20 @@ static int finalize_tables(is3d_engine* e) {
     ojx = put(e->jx.data(), 301); ojl = put(e->jl2.data(), 301); ojlc = put(e->jl2c.data(), 301);
     ojz = put(e->jz.data(), 301); ojzc = put(e->jzc.data(), 301);
   }
-  dfree(e->d_tables);
-  e->d_tables = dalloc<double>(blob.size());
-  if (!e->d_tables) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(tables) failed");
-  HIPCHK(e, hipMemcpy(e->d_tables, blob.data(), blob.size() * sizeof(double), hipMemcpyHostToDevice));
+  e->d_tables.reset();      // a new blob every time, as large as it needs to be
+  if (!e->d_tables.reserve((long)blob.size())) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(tables) failed");
+  const double* const dt = e->d_tables.get();
+  HIPCHK(e, hipMemcpy(e->d_tables.get(), blob.data(), blob.size() * sizeof(double), hipMemcpyHostToDevice));
   DfTables& tb = e->dtb;
   tb.df_mode = mode; tb.include_baryon = e->p.include_baryon;
   tb.nT = nT; tb.nmuB = nmuB_used;
-  tb.T = e->d_tables + oT; tb.muB = e->d_tables + omu; tb.tab = e->d_tables + otab;
+  tb.T = dt + oT; tb.muB = dt + omu; tb.tab = dt + otab;
   tb.T_min = e->Tarr[0]; tb.muB_min = e->muBarr[0];
   tb.dT = std::fabs(e->Tarr[1] - e->Tarr[0]);
   tb.dmuB = e->nmuB > 1 ? std::fabs(e->muBarr[1] - e->muBarr[0]) : 0.0;
-  for (int k = 0; k < NSPL; k++) { tb.sy[k] = e->d_tables + osy[k]; tb.sc[k] = e->d_tables + osc[k]; }
-  tb.nj = nj; tb.jx = e->d_tables + ojx; tb.jl2 = e->d_tables + ojl; tb.jl2c = e->d_tables + ojlc;
-  tb.jz = e->d_tables + ojz; tb.jzc = e->d_tables + ojzc;
+  for (int k = 0; k < NSPL; k++) { tb.sy[k] = dt + osy[k]; tb.sc[k] = dt + osc[k]; }
+  tb.nj = nj; tb.jx = dt + ojx; tb.jl2 = dt + ojl; tb.jl2c = dt + ojlc;
+  tb.jz = dt + ojz; tb.jzc = dt + ojzc;
   tb.bulk_over_P_max = e->bp_max;
   // tab is laid out [10][nmuB][nT]; with include_baryon = 0 only muB row 0 is used (nmuB_used = 1)
   // but the stride must stay the file's nmuB
@@ -1569,11 +808,11 @@ static int finalize_tables(is3d_engine* e) {
   ib.insert(ib.end(), cmem_off.begin(), cmem_off.end());
   ib.insert(ib.end(), cmem.begin(), cmem.end());
   ib.insert(ib.end(), scls.begin(), scls.end());
-  dfree(e->d_const);
-  e->d_const = dalloc<double>(cb.size() + (ib.size() + 1) / 2);
-  if (!e->d_const) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(constants) failed");
-  HIPCHK(e, hipMemcpy(e->d_const, cb.data(), cb.size() * sizeof(double), hipMemcpyHostToDevice));
-  int* const di = (int*)(e->d_const + cb.size());
+  e->d_const.reset();
+  if (!e->d_const.reserve((long)(cb.size() + (ib.size() + 1) / 2))) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(constants) failed");
+  double* const dc = e->d_const.get();
+  HIPCHK(e, hipMemcpy(dc, cb.data(), cb.size() * sizeof(double), hipMemcpyHostToDevice));
+  int* const di = (int*)(dc + cb.size());
   HIPCHK(e, hipMemcpy(di, ib.data(), ib.size() * sizeof(int), hipMemcpyHostToDevice));
   e->d_sorig = di;
   e->d_rcls = di + np;
@@ -1582,14 +821,31 @@ static int finalize_tables(is3d_engine* e) {
   e->d_cmem_off = e->d_crcls + nc;
   e->d_cmem = e->d_cmem_off + nc + 1;
   e->d_scls = e->d_cmem + np;
-  e->d_cmass = e->d_const + ocm; e->d_csign = e->d_const + ocs_; e->d_cbaryon = e->d_const + ocb;
-  e->d_smass = e->d_const + osm; e->d_ssign = e->d_const + oss; e->d_sbaryon = e->d_const + osb; e->d_sdegen = e->d_const + osd;
-  e->d_degen_orig = e->d_const + odg; e->d_pT = e->d_const + opt; e->d_cphi = e->d_const + oc; e->d_sphi = e->d_const + os;
-  e->d_y = e->d_const + oy; e->d_eta = e->d_const + oe; e->d_etaw = e->d_const + ow;
-  e->d_gla = e->d_const + og; e->d_pdg = e->d_const + opd; e->d_aniso_h = e->d_const + oah;
-  e->d_pTw = e->d_const + opw; e->d_phiw = e->d_const + ophw;
-  e->d_csg = e->d_const + ocs;
+  e->d_cmass = dc + ocm; e->d_csign = dc + ocs_; e->d_cbaryon = dc + ocb;
+  e->d_smass = dc + osm; e->d_ssign = dc + oss; e->d_sbaryon = dc + osb; e->d_sdegen = dc + osd;
+  e->d_degen_orig = dc + odg; e->d_pT = dc + opt; e->d_cphi = dc + oc; e->d_sphi = dc + os;
+  e->d_y = dc + oy; e->d_eta = dc + oe; e->d_etaw = dc + ow;
+  e->d_gla = dc + og; e->d_pdg = dc + opd; e->d_aniso_h = dc + oah;
+  e->d_pTw = dc + opw; e->d_phiw = dc + ophw;
+  e->d_csg = dc + ocs;
   e->tables_dirty = false;
+  return IS3D_OK;
+}
+
+// What every surface setter does on taking a surface of n cells.  owned: d_surf becomes the engine's own buffer --
+// reallocated when too small, or more than twice the size (a device group's cost prepass uploads the whole surface
+// to shard 0 before its own window); otherwise that buffer is dropped and the caller points d_surf at its memory.
+// The vorticity, the cell window and the chain range belonged to the previous surface.
+static int adopt_surface(is3d_engine* e, long n, bool owned) {
+  if (!owned || e->surf_own.capacity() > (long)NSURF * (2 * n + 4096)) e->surf_own.reset();
+  const bool ok = !owned || e->surf_own.reserve((long)NSURF * std::max(n, 1L));
+  e->d_surf = e->surf_own.get();
+  if (!ok) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(surface) failed");
+  e->ncell = n;
+  e->have_surf = true;
+  e->have_vort = false;
+  e->win_lo = e->win_hi = -1;
+  e->chain_q0 = e->chain_q1 = -1;
   return IS3D_OK;
 }
 
@@ -1602,21 +858,8 @@ extern "C" int is3d_set_surface(is3d_engine* e, long n, const is3d_surface* s) {
                                  s->muB, s->nB, s->Vx, s->Vy, s->Vn};
   for (int f = 0; f < S_MUB; f++)
     if (!fields[f] && n > 0) return e->fail(IS3D_ERR_ARG, "surface field missing");
-  // (reallocated when too small, or more than twice the size: a device group's cost prepass uploads the whole
-  // surface to shard 0 before its own window)
-  if (!e->surf_owned || e->surf_cap < n || e->surf_cap > 2 * n + 4096) {
-    if (e->surf_owned) dfree(e->d_surf);
-    e->d_surf = dalloc<double>((size_t)NSURF * std::max(n, 1L));
-    if (!e->d_surf) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(surface) failed");
-    e->surf_owned = true;
-    e->surf_cap = n;
-  }
-  e->ncell = n;
-  e->have_surf = true;
-  e->have_vort = false;
-  e->win_lo = e->win_hi = -1;
-  e->chain_q0 = e->chain_q1 = -1;
-  if (n == 0) return IS3D_OK;
+  const int rc = adopt_surface(e, n, true);
+  if (rc || n == 0) return rc;
   for (int f = 0; f < NSURF; f++) {
     double* dst = e->d_surf + (size_t)f * n;
     if (fields[f]) HIPCHK(e, hipMemcpy(dst, fields[f], n * sizeof(double), hipMemcpyHostToDevice));
@@ -1628,35 +871,16 @@ extern "C" int is3d_set_surface(is3d_engine* e, long n, const is3d_surface* s) {
 extern "C" int is3d_set_surface_device(is3d_engine* e, long n, const double* dev_fields) {
   if (e && e->grp) return is3d::group_set_surface_device(e->grp, n, dev_fields);
   if (!e || n < 0 || (!dev_fields && n > 0)) return e ? e->fail(IS3D_ERR_ARG, "bad device surface") : IS3D_ERR_ARG;
-  if (e->surf_owned) dfree(e->d_surf);
-  e->surf_owned = false;
-  e->surf_cap = 0;
+  (void)adopt_surface(e, n, false);
   e->d_surf = const_cast<double*>(dev_fields);
-  e->ncell = n;
-  e->have_surf = true;
-  e->have_vort = false;
-  e->win_lo = e->win_hi = -1;
-  e->chain_q0 = e->chain_q1 = -1;
   return IS3D_OK;
 }
 
 extern "C" int is3d_internal_copy_surface(is3d_engine* e, long n, const double* src, long src_n, int src_device, long lo) {
   if (!e || e->grp || n < 0 || lo < 0 || lo + n > src_n || (!src && n > 0)) return e ? e->fail(IS3D_ERR_ARG, "bad surface copy") : IS3D_ERR_ARG;
   HIPCHK(e, hipSetDevice(e->device));
-  // (reallocated when too small, or more than twice the size: a device group's cost prepass uploads the whole
-  // surface to shard 0 before its own window)
-  if (!e->surf_owned || e->surf_cap < n || e->surf_cap > 2 * n + 4096) {
-    if (e->surf_owned) dfree(e->d_surf);
-    e->d_surf = dalloc<double>((size_t)NSURF * std::max(n, 1L));
-    if (!e->d_surf) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(surface) failed");
-    e->surf_owned = true;
-    e->surf_cap = n;
-  }
-  e->ncell = n;
-  e->have_surf = true;
-  e->have_vort = false;
-  e->win_lo = e->win_hi = -1;
-  e->chain_q0 = e->chain_q1 = -1;
+  const int rc = adopt_surface(e, n, true);
+  if (rc) return rc;
   for (int f = 0; f < NSURF && n > 0; f++)
     HIPCHK(e, hipMemcpyPeer(e->d_surf + (size_t)f * n, e->device, src + (size_t)f * src_n + lo, src_device, n * sizeof(double)));
   return IS3D_OK;
@@ -1667,15 +891,6 @@ extern "C" long is3d_output_size(const is3d_engine* e) {
   if (!e || !e->have_species || !e->have_grid || !e->have_params) return -1;
   const long ny = (e->p.dimension == 3) ? (long)e->y.size() : 1;
   return (long)e->mass.size() * (long)e->pT.size() * (long)e->phi.size() * ny;
-}
-
-template <class T>
-static bool ensure(T*& p, long& cap, long need) {
-  if (cap >= need && p) return true;
-  dfree(p);
-  p = dalloc<T>((size_t)std::max(need, 1L));
-  cap = p ? need : 0;
-  return p != nullptr;
 }
 
 static PrepConsts make_consts(const is3d_engine* e) {
@@ -1698,6 +913,89 @@ static PrepConsts make_consts(const is3d_engine* e) {
   return k;
 }
 
+// ---- host sequences the entry points share ---------------------------------------------------------------------
+// cells [lo, hi) of the held surface that a launch covers: the cell window, or every cell
+static void cell_window(const is3d_engine* e, long& lo, long& hi) {
+  lo = e->win_hi >= 0 ? e->win_lo : 0;
+  hi = e->win_hi >= 0 ? e->win_hi : e->ncell;
+}
+
+// a launch's prologue on its stream: fresh stats, the error word and the counters cleared, ev[0] recorded
+static int begin_stats(is3d_engine* e, long cells, hipStream_t st) {
+  e->st = is3d_stats{};
+  e->st.cells = cells;
+  HIPCHK(e, hipMemsetAsync(e->d_err.get(), 0, sizeof(int), st));
+  HIPCHK(e, hipMemsetAsync(e->d_cnt.get(), 0, 8 * sizeof(unsigned long long), st));
+  HIPCHK(e, hipEventRecord(e->ev[0], st));
+  return IS3D_OK;
+}
+
+// ... and the stage times between its four events, once ev[3] has completed
+static void read_timings(is3d_engine* e) {
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, e->ev[0], e->ev[1]) == hipSuccess) e->st.ms_prepass = ms;
+  if (hipEventElapsedTime(&ms, e->ev[1], e->ev[2]) == hipSuccess) e->st.ms_spectra = ms;
+  if (hipEventElapsedTime(&ms, e->ev[0], e->ev[3]) == hipSuccess) e->st.ms_total = ms;
+}
+
+// the prepass of cells [c0, c1) of the held surface into rec / aux (operation 1; a caller for another sets k.operation)
+static PrepArgs prep_args(const is3d_engine* e, double* rec, double* aux, long c0, long c1, int* err,
+                          unsigned long long* cnt) {
+  PrepArgs pa{};
+  pa.k = make_consts(e); pa.tb = e->dtb; pa.surf = e->d_surf; pa.rec = rec; pa.aux = aux; pa.n = e->ncell;
+  pa.c0 = c0; pa.c1 = c1;
+  pa.err = err; pa.cnt = cnt;
+  return pa;
+}
+static int enqueue_prep(is3d_engine* e, const PrepArgs& pa, hipStream_t st) {
+  const dim3 g1((unsigned)std::max(1L, (pa.c1 - pa.c0 + 255) / 256)), b1(256);
+  switch (e->p.df_mode) {
+    case GRAD: hipLaunchKernelGGL(k_prep<GRAD>, g1, b1, 0, st, pa); break;
+    case CE: hipLaunchKernelGGL(k_prep<CE>, g1, b1, 0, st, pa); break;
+    case PTM: hipLaunchKernelGGL(k_prep<PTM>, g1, b1, 0, st, pa); break;
+    case PTB: hipLaunchKernelGGL(k_prep<PTB>, g1, b1, 0, st, pa); break;
+    default: hipLaunchKernelGGL(k_prep<PTMA>, g1, b1, 0, st, pa); break;
+  }
+  HIPCHK(e, hipGetLastError());
+  return IS3D_OK;
+}
+
+// PTM: the renormalisation factors of cells [c0, c0 + n) (records and aux of `stride` cells), one per renorm class
+static int enqueue_renorm(is3d_engine* e, const PrepConsts& k, long c0, long n, long stride, hipStream_t st) {
+  const long tot = n * (long)e->nrcls;
+  if (!e->d_renorm.reserve(tot)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(renorm) failed");
+  RenormArgs ra{};
+  ra.k = k; ra.rec = e->d_rec.get(); ra.aux = e->d_aux.get(); ra.renorm = e->d_renorm.get();
+  ra.mass = e->d_smass; ra.sign = e->d_ssign; ra.degen = e->d_sdegen; ra.baryon = e->d_sbaryon;
+  ra.c0 = c0; ra.n = n; ra.stride = stride;
+  ra.npart = e->nrcls; ra.rrep = e->d_rrep;
+  hipLaunchKernelGGL(k_renorm, dim3((unsigned)std::max(1L, (tot + 255) / 256)), dim3(256), 0, st, ra);
+  HIPCHK(e, hipGetLastError());
+  return IS3D_OK;
+}
+
+// operation 2: the plasma-average densities (DeltafData.cpp:555-690) into dens[3 npart], synchronously.  Returns the
+// device error word (df_error maps it), or -1 after a HIP failure (the engine's error is set)
+static int plasma_densities(is3d_engine* e, const double* plasma, double* dens) {
+  const int np = (int)e->mass.size();
+  DensArgs da{};
+  da.tb = e->dtb; da.gla = e->d_gla; da.gla_alpha = e->gla_alpha; da.gla_pts = e->gla_pts;
+  da.T = plasma[0]; da.E = plasma[1]; da.P = plasma[2]; da.muB = plasma[3]; da.nB = plasma[4];
+  da.smass = e->d_smass; da.ssign = e->d_ssign; da.sdegen = e->d_sdegen; da.sbaryon = e->d_sbaryon; da.sorig = e->d_sorig;
+  da.npart = np; da.df_mode = e->p.df_mode; da.two_pi2_hbarC3 = 2.0 * std::pow(M_PI, 2) * std::pow(kHbarC, 3);
+  da.dens = dens; da.err = e->d_err.get();
+  int derr = 0;
+  hipError_t h = hipMemset(e->d_err.get(), 0, sizeof(int));
+  if (h == hipSuccess) {
+    hipLaunchKernelGGL(k_densities, dim3((unsigned)np), dim3(64), 0, 0, da);
+    h = hipGetLastError();
+  }
+  if (h == hipSuccess) h = hipDeviceSynchronize();
+  if (h == hipSuccess) h = hipMemcpy(&derr, e->d_err.get(), sizeof(int), hipMemcpyDeviceToHost);
+  if (h != hipSuccess) { hip_fail(e, h, "plasma densities"); return -1; }
+  return derr;
+}
+
 // A launch in stages: launch_begin (prepass up to PTMA's warm-start chains), chain_pass x npass + chain_end (the
 // chains), launch_end (PTMA C/B matrices, PTM renormalisation, the integral, the reduction).  is3d_launch runs them
 // back to back; a device group whose shards solve their own ranges of the chains (group.hip) interleaves the
@@ -1717,46 +1015,35 @@ static int launch_begin(is3d_engine* e, double* dev_out, void* stream, long q0, 
   // cell window (group shards holding the whole surface): k_spectra integrates [wlo, whi); the prepass covers
   // the window too, except for PTMA's warm-start chains, which walk every cell (MomentumSpectra.cpp:1308-1364) --
   // or, when a device group splits the chains (q1 >= 0), the cells of this shard's positions, which are its window
-  const long wlo = e->win_hi >= 0 ? e->win_lo : 0, whi = e->win_hi >= 0 ? e->win_hi : n, nw = whi - wlo;
+  long wlo, whi;
+  cell_window(e, wlo, whi);
+  const long nw = whi - wlo;
   const bool chained = mode == PTMA && e->p.famod_chains > 0;
   const bool split_chain = chained && q1 >= 0;
   const long p0 = chained && !split_chain ? 0 : wlo, p1 = chained && !split_chain ? n : whi;
   L.wlo = wlo; L.whi = whi; L.nw = nw; L.p0 = p0; L.p1 = p1; L.chained = chained;
-  e->st = is3d_stats{};
-  e->st.cells = nw;
-  HIPCHK(e, hipMemsetAsync(e->d_err, 0, sizeof(int), st));
-  HIPCHK(e, hipMemsetAsync(e->d_cnt, 0, 8 * sizeof(unsigned long long), st));
-  HIPCHK(e, hipEventRecord(e->ev[0], st));
+  rc = begin_stats(e, nw, st);
+  if (rc) return rc;
   if (nw == 0) {
     L.empty = true;
     HIPCHK(e, hipMemsetAsync(dev_out, 0, outsize * sizeof(double), st));
     return IS3D_OK;
   }
-  if (!ensure(e->d_rec, e->rec_cap, (long)NREC * n)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(records) failed");
-  if (!ensure(e->d_aux, e->aux_cap, 9L * n)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(aux) failed");
-  if (mode == PTMA && !ensure(e->d_sol, e->sol_cap, 6L * n)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(sol) failed");
-  PrepArgs& pa = L.pa;
-  pa.k = make_consts(e); pa.tb = e->dtb; pa.surf = e->d_surf; pa.rec = e->d_rec; pa.aux = e->d_aux; pa.n = n;
-  pa.c0 = p0; pa.c1 = p1;
-  pa.err = e->d_err; pa.cnt = e->d_cnt;
-  const dim3 g1((unsigned)std::max(1L, (p1 - p0 + 255) / 256)), b1(256);
-  switch (mode) {
-    case GRAD: hipLaunchKernelGGL(k_prep<GRAD>, g1, b1, 0, st, pa); break;
-    case CE: hipLaunchKernelGGL(k_prep<CE>, g1, b1, 0, st, pa); break;
-    case PTM: hipLaunchKernelGGL(k_prep<PTM>, g1, b1, 0, st, pa); break;
-    case PTB: hipLaunchKernelGGL(k_prep<PTB>, g1, b1, 0, st, pa); break;
-    default: hipLaunchKernelGGL(k_prep<PTMA>, g1, b1, 0, st, pa); break;
-  }
-  HIPCHK(e, hipGetLastError());
+  if (!e->d_rec.reserve((long)NREC * n)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(records) failed");
+  if (!e->d_aux.reserve(9L * n)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(aux) failed");
+  if (mode == PTMA && !e->d_sol.reserve(6L * n)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(sol) failed");
+  L.pa = prep_args(e, e->d_rec.get(), e->d_aux.get(), p0, p1, e->d_err.get(), e->d_cnt.get());
+  rc = enqueue_prep(e, L.pa, st);
+  if (rc) return rc;
   if (mode == PTMA) {
     AnisoArgs aa{};
-    aa.rec = e->d_rec; aa.ain = e->d_aux; aa.sol = e->d_sol; aa.stride = n;
+    aa.rec = e->d_rec.get(); aa.ain = e->d_aux.get(); aa.sol = e->d_sol.get(); aa.stride = n;
     aa.c0 = p0; aa.n = p1 - p0;
     aa.chains = chained ? std::min<long>(e->p.famod_chains, n) : std::max(1L, p1 - p0);
     const int nh = e->n_aniso_h;
     aa.h = Hadrons{nh, e->d_aniso_h, e->d_aniso_h + nh, e->d_aniso_h + 2 * nh};
     aa.fp2 = 4.0 * std::pow(M_PI, 2) * std::pow(kHbarC, 3);
-    aa.cnt = e->d_cnt;
+    aa.cnt = e->d_cnt.get();
     if (!chained) {
       hipLaunchKernelGGL(k_aniso, dim3((unsigned)aa.chains), dim3(64), 0, st, aa);
       HIPCHK(e, hipGetLastError());
@@ -1764,7 +1051,7 @@ static int launch_begin(is3d_engine* e, double* dev_out, void* stream, long q0, 
       // warm-start chains in parallel segments (k_chain_pass): ~16k segments of this engine's positions keep the
       // GPU full
       ChainArgs& ca = L.ca;
-      ca.rec = e->d_rec; ca.ain = e->d_aux; ca.sol = e->d_sol; ca.n = n; ca.C = aa.chains; ca.h = aa.h; ca.fp2 = aa.fp2;
+      ca.rec = e->d_rec.get(); ca.ain = e->d_aux.get(); ca.sol = e->d_sol.get(); ca.n = n; ca.C = aa.chains; ca.h = aa.h; ca.fp2 = aa.fp2;
       const long P = (n + ca.C - 1) / ca.C;
       ca.q0 = split_chain ? q0 : 0;
       ca.q1 = split_chain ? std::min(q1, P) : P;
@@ -1781,9 +1068,9 @@ static int launch_begin(is3d_engine* e, double* dev_out, void* stream, long q0, 
       if (const char* v = std::getenv("IS3D_CHAIN_PASSES")) ca.npass = std::max(1, std::min(kChainPasses, std::atoi(v)));
       const long nseg = ca.C * ca.nspc, bw = 4 * ca.C + 1;
       const long need = 4 * n + (n + 1) / 2 + 12 * nseg + kChainPasses + 2 * kBndSlots * bw;
-      if (!ensure(e->d_chain, e->chain_cap, need)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(chain state) failed");
-      ca.sta = e->d_chain; ca.info = (int*)(e->d_chain + 4 * n);
-      ca.send = e->d_chain + 4 * n + (n + 1) / 2; ca.sstart = ca.send + 8 * nseg;
+      if (!e->d_chain.reserve(need)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(chain state) failed");
+      ca.sta = e->d_chain.get(); ca.info = (int*)(e->d_chain.get() + 4 * n);
+      ca.send = e->d_chain.get() + 4 * n + (n + 1) / 2; ca.sstart = ca.send + 8 * nseg;
       ca.changed = (int*)(ca.sstart + 4 * nseg);
       ca.bin = ca.sstart + 4 * nseg + kChainPasses;
       ca.bout = ca.bin + kBndSlots * bw;
@@ -1809,7 +1096,7 @@ static int chain_end(is3d_engine* e) {
   const long c_lo = L.ca.q0 * L.ca.C, c_hi = std::min(e->ncell, L.ca.q1 * L.ca.C);
   hipLaunchKernelGGL(k_chain_finish, dim3(1), dim3(64 * IS3D_CHAIN_W), 0, L.st, L.ca);
   hipLaunchKernelGGL(k_chain_count, dim3((unsigned)std::min(1024L, std::max(1L, (c_hi - c_lo + 255) / 256))), dim3(256), 0,
-                     L.st, (const double*)e->d_rec, (const int*)L.ca.info, c_lo, c_hi, e->d_cnt);
+                     L.st, (const double*)e->d_rec.get(), (const int*)L.ca.info, c_lo, c_hi, e->d_cnt.get());
   HIPCHK(e, hipGetLastError());
   return IS3D_OK;
 }
@@ -1838,7 +1125,7 @@ static void ts_chunking(is3d_engine* e, IntegralPlan& I) {
   {
     size_t fr = 0, tot = 0;
     if (hipMemGetInfo(&fr, &tot) == hipSuccess && tot > 0) {
-      const long avail = (long)(fr / 2) + (e->phtab_cap + e->phtab2_cap) * (long)sizeof(double);
+      const long avail = (long)(fr / 2) + (e->d_phtab.capacity() + e->d_phtab2.capacity()) * (long)sizeof(double);
       one = std::min(one, avail);
       chunk = std::max(8L * per_split, std::min(chunk, avail / 2));
     }
@@ -1918,13 +1205,13 @@ static int enqueue_spectra(is3d_engine* e, const IntegralPlan& I, const double* 
   const int KJ = P.KJ, njb = P.njb, nc = e->ncls;
   const long nsplit = I.nsplit, cps = I.cps, wgs = I.wgs;
   if (mode >= PTM) {
-    if (!ensure(e->d_fb, e->fb_cap, nw + 1 + kFbBlocks)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(fallback list) failed");
-    enqueue_fbscan(rec_w, nw, e->d_fb, st);
+    if (!e->d_fb.reserve(nw + 1 + kFbBlocks)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(fallback list) failed");
+    enqueue_fbscan(rec_w, nw, e->d_fb.get(), st);
     HIPCHK(e, hipGetLastError());
   }
   SpecArgs sa{};
-  sa.err = e->d_err;
-  sa.rec = rec_w; sa.n = nw; sa.renorm = e->d_renorm; sa.rcls = e->d_crcls; sa.nrcls = e->nrcls; sa.slab = e->d_slab;
+  sa.err = e->d_err.get();
+  sa.rec = rec_w; sa.n = nw; sa.renorm = e->d_renorm.get(); sa.rcls = e->d_crcls; sa.nrcls = e->nrcls; sa.slab = e->d_slab.get();
   sa.outsize = is3d_output_size(e);
   sa.smass = e->d_cmass; sa.ssign = e->d_csign; sa.sbaryon = e->d_cbaryon; sa.sorig = e->d_sorig;
   sa.csg = e->d_csg;
@@ -1948,9 +1235,9 @@ static int enqueue_spectra(is3d_engine* e, const IntegralPlan& I, const double* 
     const long rw = I.rw, spc = I.spc, nchunk = I.nchunk;
     const long phn = spc * cps;
     e->last_nchunk = nchunk;
-    if (!ensure(e->d_phtab, e->phtab_cap, phn * npT * rw)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(phi tables) failed");
+    if (!e->d_phtab.reserve(phn * npT * rw)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(phi tables) failed");
     if (nchunk > 1) {
-      if (!ensure(e->d_phtab2, e->phtab2_cap, phn * npT * rw)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(phi tables) failed");
+      if (!e->d_phtab2.reserve(phn * npT * rw)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(phi tables) failed");
       if (!e->side) HIPCHK(e, hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking));
       if (!e->fork) HIPCHK(e, hipEventCreateWithFlags(&e->fork, hipEventDisableTiming));
       if (!e->join) HIPCHK(e, hipEventCreateWithFlags(&e->join, hipEventDisableTiming));
@@ -1969,14 +1256,14 @@ static int enqueue_spectra(is3d_engine* e, const IntegralPlan& I, const double* 
       const long s0 = ic * spc, ns = std::min(spc, nsplit - s0);
       const long c0 = s0 * cps, ncc = std::min(nw, (s0 + ns) * cps) - c0;
       hipStream_t cs = (ic & 1) ? e->side : st;
-      double* tab = (ic & 1) ? e->d_phtab2 : e->d_phtab;
+      double* tab = (ic & 1) ? e->d_phtab2.get() : e->d_phtab.get();
       PhiTabArgs ta{};
       ta.rec = rec_w; ta.c0 = c0; ta.nc = ncc; ta.pT = e->d_pT; ta.cphi = e->d_cphi; ta.sphi = e->d_sphi;
       ta.npT = npT; ta.nphi = nphi; ta.nphp = KJ; ta.tab = tab; ta.phn = phn; ta.by = P.by != 0;
       ta.gate = gate; ta.gate_want = want;
       SpecArgs sc = sa;
       sc.split0 = (int)s0; sc.nsplit = (int)ns; sc.phtab = tab; sc.phn = phn; sc.phc0 = c0; sc.phrow = (int)rw;
-      double* buf = e->d_slab + (1 + (ic & 1) * spc) * I.sstride;
+      double* buf = e->d_slab.get() + (1 + (ic & 1) * spc) * I.sstride;
       if (I.fold) { sc.slab = buf; sc.slab0 = (int)s0; }
       const dim3 grid((unsigned)(wgs * ns));
       if (mode == GRAD) launch_phitab<GRAD>(cs, ta);
@@ -1989,7 +1276,7 @@ static int enqueue_spectra(is3d_engine* e, const IntegralPlan& I, const double* 
       if (I.fold) {
         HIPCHK(e, hipEventRecord(e->ev_spec[ic & 1], cs));
         HIPCHK(e, hipStreamWaitEvent(e->fold_st, e->ev_spec[ic & 1], 0));
-        hipLaunchKernelGGL(k_fold, dim3((unsigned)fgrid), dim3(256), 0, e->fold_st, e->d_slab, (const double*)buf,
+        hipLaunchKernelGGL(k_fold, dim3((unsigned)fgrid), dim3(256), 0, e->fold_st, e->d_slab.get(), (const double*)buf,
                            I.sstride, (int)ns, ic == 0 ? 1 : 0, gate, want);
         HIPCHK(e, hipGetLastError());
         HIPCHK(e, hipEventRecord(e->ev_fold[ic & 1], e->fold_st));
@@ -2016,8 +1303,8 @@ static int enqueue_spectra(is3d_engine* e, const IntegralPlan& I, const double* 
   HIPCHK(e, hipGetLastError());
   if (mode >= PTM) {
     SpecArgs fa = sa;
-    fa.slab = e->d_slab + nsplit * I.sstride; fa.nsplit = (int)I.nsplit_fb; fa.cells_per_split = 0;
-    fa.fbcells = e->d_fb + 1; fa.fbcount = e->d_fb;
+    fa.slab = e->d_slab.get() + nsplit * I.sstride; fa.nsplit = (int)I.nsplit_fb; fa.cells_per_split = 0;
+    fa.fbcells = e->d_fb.get() + 1; fa.fbcount = e->d_fb.get();
     const int fflags = (e->p.regulate_deltaf ? F_REG : 0) | (e->p.outflow ? F_OUT : 0) | F_FB;
     const dim3 gfb((unsigned)(I.bx * npT * I.nsplit_fb));
     switch (mode) {
@@ -2039,7 +1326,7 @@ static int enqueue_reduce(is3d_engine* e, const IntegralPlan& I, double* dev_out
   const int nk = ny_out, nl = (dim == 3) ? 1 : (int)e->eta.size();
   const int nc = e->ncls;
   ReduceArgs ra{};
-  ra.slab = e->d_slab; ra.sstride = I.sstride; ra.nsplit = I.fold ? 1 : (int)(I.nsplit + I.nsplit_fb);
+  ra.slab = e->d_slab.get(); ra.sstride = I.sstride; ra.nsplit = I.fold ? 1 : (int)(I.nsplit + I.nsplit_fb);
   ra.nbx = (int)I.bx; ra.npart = nc; ra.npT = npT; ra.nphi = nphi; ra.nk = nk; ra.nl = nl; ra.ny_out = ny_out; ra.kj = I.P.KJ;
   ra.ntask = I.ntask;
   ra.sorig = e->d_sorig; ra.degen_orig = e->d_degen_orig; ra.prefactor = std::pow(2.0 * M_PI * kHbarC, -3);
@@ -2075,23 +1362,14 @@ static int launch_end(is3d_engine* e) {
   const PrepArgs& pa = L.pa;
   const dim3 g1((unsigned)std::max(1L, (L.p1 - L.p0 + 255) / 256)), b1(256);
   if (mode == PTMA) {
-    hipLaunchKernelGGL(k_famod_b, g1, b1, 0, st, pa, (const double*)e->d_sol);
+    hipLaunchKernelGGL(k_famod_b, g1, b1, 0, st, pa, (const double*)e->d_sol.get());
     HIPCHK(e, hipGetLastError());
   }
-  if (mode == PTM) {
-    if (!ensure(e->d_renorm, e->renorm_cap, nw * (long)e->nrcls)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(renorm) failed");
-    RenormArgs ra{};
-    ra.k = pa.k; ra.rec = e->d_rec; ra.aux = e->d_aux; ra.renorm = e->d_renorm;
-    ra.mass = e->d_smass; ra.sign = e->d_ssign; ra.degen = e->d_sdegen; ra.baryon = e->d_sbaryon;
-    ra.c0 = wlo; ra.n = nw; ra.stride = n;
-    ra.npart = e->nrcls; ra.rrep = e->d_rrep;
-    const long tot = nw * (long)e->nrcls;
-    hipLaunchKernelGGL(k_renorm, dim3((unsigned)std::max(1L, (tot + 255) / 256)), dim3(256), 0, st, ra);
-    HIPCHK(e, hipGetLastError());
-  }
+  int rc = mode == PTM ? enqueue_renorm(e, pa.k, wlo, nw, n, st) : IS3D_OK;
+  if (rc) return rc;
   HIPCHK(e, hipEventRecord(e->ev[1], st));
   // the integral and the reduction see the window only: records from wlo on, nw cells
-  const double* rec_w = e->d_rec + wlo * (long)NREC;
+  const double* rec_w = e->d_rec.get() + wlo * (long)NREC;
   // --- main integral
   // Grad / RTA-CE F_TS: a surface with cells whose lanes may leave the fast path (k_prep counts them in cnt[4]; none
   // in any tabulated delta-f range) needs the kernels that carry the slow loop, which the F_TS ones do not.  The
@@ -2100,7 +1378,7 @@ static int launch_end(is3d_engine* e) {
   const SpectraPlan P = spectra_plan(e, true);
   e->last_nchunk = 0;
   IntegralPlan I{}, J{};
-  int rc = integral_plan(e, P, nw, I);
+  rc = integral_plan(e, P, nw, I);
   if (rc) return rc;
   e->last_nsplit = I.nsplit;
   e->last_nslab = I.slabs();
@@ -2111,8 +1389,8 @@ static int launch_end(is3d_engine* e) {
     if (rc) return rc;
   }
   const long slab_need = std::max(I.slabs() * I.sstride, gated ? J.slabs() * J.sstride : 0L);
-  if (!ensure(e->d_slab, e->slab_cap, slab_need)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(slabs) failed");
-  const unsigned long long* gate = gated ? e->d_cnt + 4 : nullptr;
+  if (!e->d_slab.reserve(slab_need)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(slabs) failed");
+  const unsigned long long* gate = gated ? e->d_cnt.get() + 4 : nullptr;
   rc = enqueue_spectra(e, I, rec_w, nw, st, gate, 0);
   if (!rc && gated) rc = enqueue_spectra(e, J, rec_w, nw, st, gate, 1);
   if (rc) return rc;
@@ -2226,35 +1504,22 @@ extern "C" int is3d_cell_costs(is3d_engine* e, double* cost) {
   // private scratch (records, aux, cost, error word, counters), freed on return: a launch in flight keeps its
   // buffers and the error word is3d_finish reports, and a device group's cost prepass over the whole surface
   // (group_set_surface on shard 0) leaves no full-surface-sized buffers behind on that shard
-  double* scratch = nullptr;
-  const size_t nd = (size_t)(NREC + 9 + 1) * n + 9;
-  HIPCHK(e, hipMalloc(&scratch, nd * sizeof(double)));
-  double* d_rec = scratch;
+  DevBuf<double> scratch;
+  if (!scratch.reserve((long)(NREC + 9 + 1) * n + 9)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(cell cost scratch) failed");
+  double* d_rec = scratch.get();
   double* d_aux = d_rec + (size_t)NREC * n;
   double* d_cost = d_aux + 9 * (size_t)n;
   int* d_err = (int*)(d_cost + n);
   unsigned long long* d_cnt = (unsigned long long*)(d_cost + n + 1);
-  PrepArgs pa{};
-  pa.k = make_consts(e); pa.tb = e->dtb; pa.surf = e->d_surf; pa.rec = d_rec; pa.aux = d_aux; pa.n = n;
-  pa.c0 = 0; pa.c1 = n;
-  pa.err = d_err; pa.cnt = d_cnt;
-  const dim3 g1((unsigned)((n + 255) / 256)), b1(256);
-  hipError_t er = hipMemsetAsync(d_err, 0, 9 * sizeof(double), nullptr);
-  switch (mode) {
-    case GRAD: hipLaunchKernelGGL(k_prep<GRAD>, g1, b1, 0, nullptr, pa); break;
-    case CE: hipLaunchKernelGGL(k_prep<CE>, g1, b1, 0, nullptr, pa); break;
-    case PTM: hipLaunchKernelGGL(k_prep<PTM>, g1, b1, 0, nullptr, pa); break;
-    case PTB: hipLaunchKernelGGL(k_prep<PTB>, g1, b1, 0, nullptr, pa); break;
-    default: hipLaunchKernelGGL(k_prep<PTMA>, g1, b1, 0, nullptr, pa); break;
-  }
+  HIPCHK(e, hipMemsetAsync(d_err, 0, 9 * sizeof(double), nullptr));
+  rc = enqueue_prep(e, prep_args(e, d_rec, d_aux, 0, n, d_err, d_cnt), nullptr);
+  if (rc) return rc;
   // separable-fallback cells of PTM / PTB relative to a modified cell (config-2 shape, MI355X,
   // tools/fb_cost_probe.py: PTM 1.37-1.43, PTB 1.58-1.80)
   const double fb_cost = mode == PTM ? 1.4 : mode == PTB ? 1.8 : 0.0;
-  hipLaunchKernelGGL(k_cell_cost, g1, b1, 0, nullptr, (const double*)d_rec, n, fb_cost, d_cost);
-  if (er == hipSuccess) er = hipGetLastError();
-  if (er == hipSuccess) er = hipMemcpy(cost, d_cost, n * sizeof(double), hipMemcpyDeviceToHost);
-  (void)hipFree(scratch);
-  if (er != hipSuccess) return e->fail(IS3D_ERR_DEVICE, std::string("is3d_cell_costs: ") + hipGetErrorString(er));
+  hipLaunchKernelGGL(k_cell_cost, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, (const double*)d_rec, n, fb_cost, d_cost);
+  HIPCHK(e, hipGetLastError());
+  HIPCHK(e, hipMemcpy(cost, d_cost, n * sizeof(double), hipMemcpyDeviceToHost));
   return IS3D_OK;
 }
 
@@ -2267,21 +1532,11 @@ extern "C" int is3d_finish(is3d_engine* e) {
   e->launched = false;
   int derr = 0;
   unsigned long long cnt[8];
-  HIPCHK(e, hipMemcpy(&derr, e->d_err, sizeof(int), hipMemcpyDeviceToHost));
-  HIPCHK(e, hipMemcpy(cnt, e->d_cnt, sizeof(cnt), hipMemcpyDeviceToHost));
+  HIPCHK(e, hipMemcpy(&derr, e->d_err.get(), sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(e, hipMemcpy(cnt, e->d_cnt.get(), sizeof(cnt), hipMemcpyDeviceToHost));
   e->st.breakdown = (long)cnt[0]; e->st.pl_negative = (long)cnt[1]; e->st.recon_fail = (long)cnt[2]; e->st.iterations = (long)cnt[3];
-  float ms = 0.f;
-  if (hipEventElapsedTime(&ms, e->ev[0], e->ev[1]) == hipSuccess) e->st.ms_prepass = ms;
-  if (hipEventElapsedTime(&ms, e->ev[1], e->ev[2]) == hipSuccess) e->st.ms_spectra = ms;
-  if (hipEventElapsedTime(&ms, e->ev[0], e->ev[3]) == hipSuccess) e->st.ms_total = ms;
-  switch (derr) {
-    case DF_OK: return IS3D_OK;
-    case DF_SPLINE_RANGE: return e->fail(IS3D_ERR_DF_RANGE, "gsl: interp.c: interpolation error (df coefficient spline evaluated outside its table)");
-    case DF_TABLE_RANGE: return e->fail(IS3D_ERR_DF_RANGE, "Error: (T,muB) outside df coefficient table. Exiting...");
-    case DF_PTB_BARYON: return e->fail(IS3D_ERR_UNSUPPORTED, "Bilinear interpolation error: Jonah df doesn't work for nonzero muB. Exiting..");
-    case DF_TS_SLOW: return e->fail(IS3D_ERR_DEVICE, "internal: a scalar-table (F_TS) lane left the fast path (sep_slow_cell bound)");
-    default: return e->fail(IS3D_ERR_ARG, "Error: choose df_mode = (1,2,3,4,5)");
-  }
+  read_timings(e);
+  return df_error(e, derr, "Error: choose df_mode = (1,2,3,4,5)");
 }
 
 extern "C" int is3d_calculate_spectra(is3d_engine* e, double* dN_out) {
@@ -2290,12 +1545,12 @@ extern "C" int is3d_calculate_spectra(is3d_engine* e, double* dN_out) {
   int rc = finalize_tables(e);
   if (rc) return rc;
   const long outsize = is3d_output_size(e);
-  if (!ensure(e->d_out, e->out_cap, outsize)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(output) failed");
-  rc = is3d_launch(e, e->d_out, nullptr);
+  if (!e->d_out.reserve(outsize)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(output) failed");
+  rc = is3d_launch(e, e->d_out.get(), nullptr);
   if (rc) return rc;
   rc = is3d_finish(e);
   if (rc) return rc;
-  HIPCHK(e, hipMemcpy(dN_out, e->d_out, outsize * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(e, hipMemcpy(dN_out, e->d_out.get(), outsize * sizeof(double), hipMemcpyDeviceToHost));
   return IS3D_OK;
 }
 
@@ -2323,39 +1578,17 @@ extern "C" int is3d_calculate_dN_dX(is3d_engine* e, double* dN_taudtaudy, double
   const int carry = B.threads >= 1;
   const long nb[3] = {B.tau_bins, B.r_bins, B.phip_bins};
   const long nent = C * (nb[0] + nb[1] + nb[2]);
-  e->st = is3d_stats{};
-  e->st.cells = n;
   std::vector<double> part((size_t)np * nent, 0.0);
-  HIPCHK(e, hipMemsetAsync(e->d_err, 0, sizeof(int), st));
-  HIPCHK(e, hipMemsetAsync(e->d_cnt, 0, 8 * sizeof(unsigned long long), st));
-  HIPCHK(e, hipEventRecord(e->ev[0], st));
+  rc = begin_stats(e, n, st);
+  if (rc) return rc;
   if (n > 0) {
-    if (!ensure(e->d_rec, e->rec_cap, (long)NREC * n)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(records) failed");
-    if (!ensure(e->d_aux, e->aux_cap, 9L * n)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(aux) failed");
-    PrepArgs pa{};
-    pa.k = make_consts(e); pa.k.operation = 0;
-    pa.tb = e->dtb; pa.surf = e->d_surf; pa.rec = e->d_rec; pa.aux = e->d_aux; pa.n = n;
-    pa.c0 = 0; pa.c1 = n;
-    pa.err = e->d_err; pa.cnt = e->d_cnt;
-    const dim3 g1((unsigned)((n + 255) / 256)), b1(256);
-    switch (mode) {
-      case GRAD: hipLaunchKernelGGL(k_prep<GRAD>, g1, b1, 0, st, pa); break;
-      case CE: hipLaunchKernelGGL(k_prep<CE>, g1, b1, 0, st, pa); break;
-      case PTM: hipLaunchKernelGGL(k_prep<PTM>, g1, b1, 0, st, pa); break;
-      default: hipLaunchKernelGGL(k_prep<PTB>, g1, b1, 0, st, pa); break;
-    }
-    HIPCHK(e, hipGetLastError());
-    if (mode == PTM) {
-      if (!ensure(e->d_renorm, e->renorm_cap, n * (long)e->nrcls)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(renorm) failed");
-      RenormArgs ra{};
-      ra.k = pa.k; ra.rec = e->d_rec; ra.aux = e->d_aux; ra.renorm = e->d_renorm;
-      ra.mass = e->d_smass; ra.sign = e->d_ssign; ra.degen = e->d_sdegen; ra.baryon = e->d_sbaryon;
-      ra.c0 = 0; ra.n = n; ra.stride = n;
-      ra.npart = e->nrcls; ra.rrep = e->d_rrep;
-      const long tot = n * (long)e->nrcls;
-      hipLaunchKernelGGL(k_renorm, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, ra);
-      HIPCHK(e, hipGetLastError());
-    }
+    if (!e->d_rec.reserve((long)NREC * n)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(records) failed");
+    if (!e->d_aux.reserve(9L * n)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(aux) failed");
+    PrepArgs pa = prep_args(e, e->d_rec.get(), e->d_aux.get(), 0, n, e->d_err.get(), e->d_cnt.get());
+    pa.k.operation = 0;
+    rc = enqueue_prep(e, pa, st);
+    if (!rc && mode == PTM) rc = enqueue_renorm(e, pa.k, 0, n, n, st);
+    if (rc) return rc;
   }
   HIPCHK(e, hipEventRecord(e->ev[1], st));
   if (n > 0) {
@@ -2374,8 +1607,8 @@ extern "C" int is3d_calculate_dN_dX(is3d_engine* e, double* dN_taudtaudy, double
     if ((long)da.nbx * ((n + cpw - 1) / cpw) < 4096) cpw = kTile;
     da.cells_per_wg = cpw;
     da.nchunk = (n + cpw - 1) / cpw;
-    if (!ensure(e->d_ycell, e->ycell_cap, (long)nc * n)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(cell yields) failed");
-    da.rec = e->d_rec; da.n = n; da.renorm = e->d_renorm; da.rcls = e->d_crcls; da.nrcls = e->nrcls; da.ycell = e->d_ycell;
+    if (!e->d_ycell.reserve((long)nc * n)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(cell yields) failed");
+    da.rec = e->d_rec.get(); da.n = n; da.renorm = e->d_renorm.get(); da.rcls = e->d_crcls; da.nrcls = e->nrcls; da.ycell = e->d_ycell.get();
     da.smass = e->d_cmass; da.ssign = e->d_csign; da.sbaryon = e->d_cbaryon;
     da.pT = e->d_pT; da.pTw = e->d_pTw; da.cphi = e->d_cphi; da.sphi = e->d_sphi; da.phiw = e->d_phiw;
     da.yv = e->d_y; da.etav = e->d_eta; da.etaw = e->d_etaw;
@@ -2409,10 +1642,10 @@ extern "C" int is3d_calculate_dN_dX(is3d_engine* e, double* dN_taudtaudy, double
       // the separable-fallback lanes of the cells k_fbwrite lists (breakdown, narrow rapidity windows) in their own
       // launch (kernels.h k_dndx F_FB), added to ycell; the list's length stays on the device, so the grid is sized
       // for the whole surface and the workgroups split whatever the list holds
-      if (!ensure(e->d_fb, e->fb_cap, n + 1 + kFbBlocks)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(fallback list) failed");
-      enqueue_fbscan((const double*)e->d_rec, n, e->d_fb, st);
+      if (!e->d_fb.reserve(n + 1 + kFbBlocks)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(fallback list) failed");
+      enqueue_fbscan((const double*)e->d_rec.get(), n, e->d_fb.get(), st);
       DndxArgs fa = da;
-      fa.fbcells = e->d_fb + 1; fa.fbcount = e->d_fb;
+      fa.fbcells = e->d_fb.get() + 1; fa.fbcount = e->d_fb.get();
       fa.nchunk = std::max(1L, std::min(da.nchunk, (4096L + da.nbx - 1) / da.nbx));
       const long nfw = (long)da.nbx * fa.nchunk;
       if (mode == PTM) launch_dndx<PTM>(dim3((unsigned)nfw), shmem_fb, st, fa, kflags | F_FB, KJ);
@@ -2426,17 +1659,17 @@ extern "C" int is3d_calculate_dN_dX(is3d_engine* e, double* dN_taudtaudy, double
   HIPCHK(e, hipEventRecord(e->ev[2], st));
   if (n > 0) {
     // --- bin keys on the device, CSR (thread slice, bin) -> cells on the host, sums on the device
-    if (!ensure(e->d_keys, e->keys_cap, 3 * n)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(keys) failed");
+    if (!e->d_keys.reserve(3 * n)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(keys) failed");
     KeyArgs ka{};
     ka.tau = e->d_surf; ka.x = e->d_surf + n; ka.y = e->d_surf + 2 * n; ka.n = n;
     ka.tau_min = B.tau_min; ka.tau_width = (B.tau_max - B.tau_min) / (double)B.tau_bins;
     ka.r_min = B.r_min; ka.r_width = (B.r_max - B.r_min) / (double)B.r_bins;
     ka.phip_width = 2.0 * M_PI / (double)B.phip_bins;
-    ka.tau_bins = B.tau_bins; ka.r_bins = B.r_bins; ka.phip_bins = B.phip_bins; ka.keys = e->d_keys;
+    ka.tau_bins = B.tau_bins; ka.r_bins = B.r_bins; ka.phip_bins = B.phip_bins; ka.keys = e->d_keys.get();
     hipLaunchKernelGGL(k_stkeys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ka);
     HIPCHK(e, hipGetLastError());
     std::vector<int> keys((size_t)3 * n);
-    HIPCHK(e, hipMemcpy(keys.data(), e->d_keys, keys.size() * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(e, hipMemcpy(keys.data(), e->d_keys.get(), keys.size() * sizeof(int), hipMemcpyDeviceToHost));
     std::vector<long> offs((size_t)nent + 1, 0);
     long off_d[3] = {0, C * nb[0], C * (nb[0] + nb[1])};
     for (int d = 0; d < 3; d++)
@@ -2452,17 +1685,17 @@ extern "C" int is3d_calculate_dN_dX(is3d_engine* e, double* dN_taudtaudy, double
         const int kb = keys[(size_t)d * n + c];
         if (kb >= 0) perm[fill[off_d[d] + (c % C) * nb[d] + kb]++] = (int)c;
       }
-    if (!ensure(e->d_perm, e->perm_cap, (long)perm.size())) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(perm) failed");
-    if (!ensure(e->d_offs, e->offs_cap, nent + 1)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(offsets) failed");
-    if (!ensure(e->d_part, e->part_cap, (long)np * nent)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(bins) failed");
-    HIPCHK(e, hipMemcpy(e->d_perm, perm.data(), perm.size() * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(e, hipMemcpy(e->d_offs, offs.data(), offs.size() * sizeof(long), hipMemcpyHostToDevice));
+    if (!e->d_perm.reserve((long)perm.size())) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(perm) failed");
+    if (!e->d_offs.reserve(nent + 1)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(offsets) failed");
+    if (!e->d_part.reserve((long)np * nent)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(bins) failed");
+    HIPCHK(e, hipMemcpy(e->d_perm.get(), perm.data(), perm.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(e, hipMemcpy(e->d_offs.get(), offs.data(), offs.size() * sizeof(long), hipMemcpyHostToDevice));
     BinArgs ba{};
-    ba.ycell = e->d_ycell; ba.n = n; ba.npart = np;
-    ba.perm = e->d_perm; ba.offs = e->d_offs; ba.nent = nent;
+    ba.ycell = e->d_ycell.get(); ba.n = n; ba.npart = np;
+    ba.perm = e->d_perm.get(); ba.offs = e->d_offs.get(); ba.nent = nent;
     ba.sorig = e->d_sorig; ba.sdegen = e->d_sdegen; ba.prefactor = std::pow(2.0 * M_PI * kHbarC, -3);
     ba.scls = e->d_scls;
-    ba.part = e->d_part;
+    ba.part = e->d_part.get();
     const long nthr = nent * np;
     hipLaunchKernelGGL(k_stbin, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, st, ba);
     HIPCHK(e, hipGetLastError());
@@ -2470,19 +1703,10 @@ extern "C" int is3d_calculate_dN_dX(is3d_engine* e, double* dN_taudtaudy, double
   HIPCHK(e, hipEventRecord(e->ev[3], st));
   HIPCHK(e, hipEventSynchronize(e->ev[3]));
   int derr = 0;
-  HIPCHK(e, hipMemcpy(&derr, e->d_err, sizeof(int), hipMemcpyDeviceToHost));
-  if (n > 0) HIPCHK(e, hipMemcpy(part.data(), e->d_part, part.size() * sizeof(double), hipMemcpyDeviceToHost));
-  float ms = 0.f;
-  if (hipEventElapsedTime(&ms, e->ev[0], e->ev[1]) == hipSuccess) e->st.ms_prepass = ms;
-  if (hipEventElapsedTime(&ms, e->ev[1], e->ev[2]) == hipSuccess) e->st.ms_spectra = ms;
-  if (hipEventElapsedTime(&ms, e->ev[0], e->ev[3]) == hipSuccess) e->st.ms_total = ms;
-  switch (derr) {
-    case DF_OK: break;
-    case DF_SPLINE_RANGE: return e->fail(IS3D_ERR_DF_RANGE, "gsl: interp.c: interpolation error (df coefficient spline evaluated outside its table)");
-    case DF_TABLE_RANGE: return e->fail(IS3D_ERR_DF_RANGE, "Error: (T,muB) outside df coefficient table. Exiting...");
-    case DF_PTB_BARYON: return e->fail(IS3D_ERR_UNSUPPORTED, "Bilinear interpolation error: Jonah df doesn't work for nonzero muB. Exiting..");
-    default: return e->fail(IS3D_ERR_ARG, "Error: set df_mode = (1,2) in parameters.dat");
-  }
+  HIPCHK(e, hipMemcpy(&derr, e->d_err.get(), sizeof(int), hipMemcpyDeviceToHost));
+  if (n > 0) HIPCHK(e, hipMemcpy(part.data(), e->d_part.get(), part.size() * sizeof(double), hipMemcpyDeviceToHost));
+  read_timings(e);
+  if (derr) return df_error(e, derr, "Error: set df_mode = (1,2) in parameters.dat");
   // --- the reference's per-species thread-slice reset and bin normalisation
   const double two_pi = 2.0 * M_PI;
   const double width[3] = {(B.tau_max - B.tau_min) / (double)B.tau_bins, (B.r_max - B.r_min) / (double)B.r_bins,
@@ -2521,7 +1745,7 @@ extern "C" int is3d_get_cell_yields(const is3d_engine* e, double* dN_dy_cell) {
   if (n == 0) return IS3D_OK;
   std::vector<double> y((size_t)e->ncls * n);
   if (hipSetDevice(e->device) != hipSuccess) return IS3D_ERR_DEVICE;
-  if (hipMemcpy(y.data(), e->d_ycell, y.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return IS3D_ERR_DEVICE;
+  if (hipMemcpy(y.data(), e->d_ycell.get(), y.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return IS3D_ERR_DEVICE;
   const double pref = std::pow(2.0 * M_PI * kHbarC, -3);
   for (int s = 0; s < np; s++) {
     const int so = e->order[s];
@@ -2542,9 +1766,9 @@ extern "C" int is3d_set_vorticity(is3d_engine* e, long n, const is3d_vorticity* 
   for (int k = 0; k < 6; k++)
     if (!f[k] && n > 0) return e->fail(IS3D_ERR_ARG, "is3d_set_vorticity: vorticity component missing");
   HIPCHK(e, hipSetDevice(e->device));
-  if (!ensure(e->d_vort, e->vort_cap, 6L * n)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(vorticity) failed");
+  if (!e->d_vort.reserve(6L * n)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(vorticity) failed");
   for (int k = 0; k < 6 && n > 0; k++)
-    HIPCHK(e, hipMemcpy(e->d_vort + (size_t)k * n, f[k], n * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(e, hipMemcpy(e->d_vort.get() + (size_t)k * n, f[k], n * sizeof(double), hipMemcpyHostToDevice));
   e->have_vort = true;
   return IS3D_OK;
 }
@@ -2572,12 +1796,11 @@ extern "C" int is3d_launch_polarization(is3d_engine* e, double T_avg, double* de
   }
   hipStream_t st = (hipStream_t)stream;
   const long n = e->ncell;
-  const long wlo = e->win_hi >= 0 ? e->win_lo : 0, whi = e->win_hi >= 0 ? e->win_hi : n, nw = whi - wlo;
-  e->st = is3d_stats{};
-  e->st.cells = nw;
-  HIPCHK(e, hipMemsetAsync(e->d_err, 0, sizeof(int), st));
-  HIPCHK(e, hipMemsetAsync(e->d_cnt, 0, 8 * sizeof(unsigned long long), st));
-  HIPCHK(e, hipEventRecord(e->ev[0], st));
+  long wlo, whi;
+  cell_window(e, wlo, whi);
+  const long nw = whi - wlo;
+  const int rc = begin_stats(e, nw, st);
+  if (rc) return rc;
   HIPCHK(e, hipEventRecord(e->ev[1], st));     // no prepass: k_polzn reads the surface itself
   if (nw == 0) {
     HIPCHK(e, hipMemsetAsync(dev_out, 0, e->pz.out_size() * sizeof(double), st));
@@ -2585,11 +1808,11 @@ extern "C" int is3d_launch_polarization(is3d_engine* e, double T_avg, double* de
   } else {
     const is3d::polzn::Plan P = is3d::polzn::make_plan(e->pz, nw, e->max_splits, e->split_bytes, e->slab_bytes);
     if (!P.ok) return e->fail(IS3D_ERR_ARG, "polarization: the phi / y / eta tables do not fit a workgroup's LDS tile");
-    if (!ensure(e->d_slab, e->slab_cap, P.nsplit * P.sstride)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(slabs) failed");
+    if (!e->d_slab.reserve(P.nsplit * P.sstride)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(slabs) failed");
     e->last_nchunk = 0;
     e->last_nsplit = P.nsplit;
     e->last_nslab = P.nsplit;
-    HIPCHK(e, is3d::polzn::enqueue(e->pz, P, e->d_surf, e->d_vort, n, wlo, whi, T_avg, e->d_slab, dev_out, st, e->ev[2]));
+    HIPCHK(e, is3d::polzn::enqueue(e->pz, P, e->d_surf, e->d_vort.get(), n, wlo, whi, T_avg, e->d_slab.get(), dev_out, st, e->ev[2]));
   }
   HIPCHK(e, hipEventRecord(e->ev[3], st));
   e->launched = true;
@@ -2602,12 +1825,12 @@ extern "C" int is3d_calculate_polarization(is3d_engine* e, double T_avg, double*
   const long outsize = is3d_polarization_size(e);
   if (outsize < 0) return e->fail(IS3D_ERR_STATE, "polarization: params, species and momentum grid must be set");
   HIPCHK(e, hipSetDevice(e->device));
-  if (!ensure(e->d_out, e->out_cap, outsize)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(output) failed");
-  int rc = is3d_launch_polarization(e, T_avg, e->d_out, nullptr);
+  if (!e->d_out.reserve(outsize)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(output) failed");
+  int rc = is3d_launch_polarization(e, T_avg, e->d_out.get(), nullptr);
   if (rc) return rc;
   rc = is3d_finish(e);
   if (rc) return rc;
-  HIPCHK(e, hipMemcpy(S_out, e->d_out, outsize * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(e, hipMemcpy(S_out, e->d_out.get(), outsize * sizeof(double), hipMemcpyDeviceToHost));
   return IS3D_OK;
 }
 
@@ -2625,18 +1848,15 @@ extern "C" int is3d_evaluate_df_coefficients(is3d_engine* e, double T, double mu
   int rc = finalize_tables(e);
   if (rc) return rc;
   HIPCHK(e, hipSetDevice(e->device));
-  double* d = dalloc<double>(16);
-  if (!d) return e->fail(IS3D_ERR_DEVICE, "hipMalloc failed");
+  DevBuf<double> buf;
+  if (!buf.reserve(16)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc failed");
+  double* const d = buf.get();
   hipLaunchKernelGGL(k_df_eval, dim3(1), dim3(1), 0, 0, e->dtb, T, muB, E, P, bulkPi, d, (int*)(d + 15));
-  hipError_t h = hipDeviceSynchronize();
+  HIPCHK(e, hipDeviceSynchronize());
   int derr = 0;
-  if (h == hipSuccess) h = hipMemcpy(out15, d, 15 * sizeof(double), hipMemcpyDeviceToHost);
-  if (h == hipSuccess) h = hipMemcpy(&derr, d + 15, sizeof(int), hipMemcpyDeviceToHost);
-  dfree(d);
-  if (h != hipSuccess) return hip_fail(e, h, "df eval");
-  if (derr == DF_SPLINE_RANGE || derr == DF_TABLE_RANGE) return e->fail(IS3D_ERR_DF_RANGE, "df coefficient evaluated out of range");
-  if (derr) return e->fail(IS3D_ERR_ARG, "df coefficient error");
-  return IS3D_OK;
+  HIPCHK(e, hipMemcpy(out15, d, 15 * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(e, hipMemcpy(&derr, d + 15, sizeof(int), hipMemcpyDeviceToHost));
+  return df_error(e, derr, "df coefficient error");
 }
 
 extern "C" int is3d_total_yield(is3d_engine* e, const double* plasma, double y_cut, double* n_total,
@@ -2651,36 +1871,24 @@ extern "C" int is3d_total_yield(is3d_engine* e, const double* plasma, double y_c
   const int np = (int)e->mass.size();
   const long n = e->ncell;
   const long nb = (n + 255) / 256;
-  double* d = dalloc<double>(3 * (size_t)np + (size_t)std::max(nb, 1L) + 1);
-  if (!d) return e->fail(IS3D_ERR_DEVICE, "hipMalloc failed");
-  HIPCHK(e, hipMemset(e->d_err, 0, sizeof(int)));
-  DensArgs da{};
-  da.tb = e->dtb; da.gla = e->d_gla; da.gla_alpha = e->gla_alpha; da.gla_pts = e->gla_pts;
-  da.T = plasma[0]; da.E = plasma[1]; da.P = plasma[2]; da.muB = plasma[3]; da.nB = plasma[4];
-  da.smass = e->d_smass; da.ssign = e->d_ssign; da.sdegen = e->d_sdegen; da.sbaryon = e->d_sbaryon; da.sorig = e->d_sorig;
-  da.npart = np; da.df_mode = e->p.df_mode; da.two_pi2_hbarC3 = 2.0 * std::pow(M_PI, 2) * std::pow(kHbarC, 3);
-  da.dens = d; da.err = e->d_err;
-  hipLaunchKernelGGL(k_densities, dim3((unsigned)np), dim3(64), 0, 0, da);
-  hipError_t h = hipGetLastError();
+  DevBuf<double> buf;       // densities [3 np] | k_yield's partial sums [nb]
+  if (!buf.reserve(3L * np + std::max(nb, 1L) + 1)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc failed");
+  double* const d = buf.get();
+  int derr = plasma_densities(e, plasma, d);
+  if (derr < 0) return IS3D_ERR_DEVICE;
   std::vector<double> part((size_t)std::max(nb, 1L), 0.0);
-  if (h == hipSuccess && n > 0) {
+  if (!derr && n > 0) {     // k_yield reports through the same error word
     YieldArgs ya{};
     ya.k = make_consts(e); ya.tb = e->dtb; ya.surf = e->d_surf; ya.n = n; ya.dens = d; ya.npart = np;
-    ya.partial = d + 3 * (size_t)np; ya.err = e->d_err;
+    ya.partial = d + 3 * (size_t)np; ya.err = e->d_err.get();
     hipLaunchKernelGGL(k_yield, dim3((unsigned)nb), dim3(256), 0, 0, ya);
-    h = hipGetLastError();
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipDeviceSynchronize());
+    HIPCHK(e, hipMemcpy(&derr, e->d_err.get(), sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(e, hipMemcpy(part.data(), d + 3 * (size_t)np, nb * sizeof(double), hipMemcpyDeviceToHost));
   }
-  if (h == hipSuccess) h = hipDeviceSynchronize();
-  int derr = 0;
-  if (h == hipSuccess) h = hipMemcpy(&derr, e->d_err, sizeof(int), hipMemcpyDeviceToHost);
-  if (h == hipSuccess && n > 0) h = hipMemcpy(part.data(), d + 3 * (size_t)np, nb * sizeof(double), hipMemcpyDeviceToHost);
-  if (h == hipSuccess && densities) h = hipMemcpy(densities, d, 3 * (size_t)np * sizeof(double), hipMemcpyDeviceToHost);
-  dfree(d);
-  if (h != hipSuccess) return hip_fail(e, h, "total yield");
-  if (derr == DF_SPLINE_RANGE) return e->fail(IS3D_ERR_DF_RANGE, "gsl: interpolation error (df coefficient spline evaluated out of range)");
-  if (derr == DF_TABLE_RANGE) return e->fail(IS3D_ERR_DF_RANGE, "Error: (T,muB) outside df coefficient table");
-  if (derr == DF_PTB_BARYON) return e->fail(IS3D_ERR_UNSUPPORTED, "Bilinear interpolation error: Jonah df doesn't work for nonzero muB. Exiting..");
-  if (derr) return e->fail(IS3D_ERR_ARG, "df coefficient error");
+  if (densities) HIPCHK(e, hipMemcpy(densities, d, 3 * (size_t)np * sizeof(double), hipMemcpyDeviceToHost));
+  if (derr) return df_error(e, derr, "df coefficient error");
   double Ntot = 0.0;
   for (long b = 0; b < nb; b++) Ntot += part[b];
   if (e->p.dimension == 2) Ntot *= 2.0 * y_cut;     // :628-631
@@ -2693,13 +1901,6 @@ extern "C" int is3d_total_yield(is3d_engine* e, const double* plasma, double y_c
 // ------------------------------------------------------------------------------------------
 static_assert(sizeof(is3d_particle) == 96 && sizeof(is3d::sampler::Particle) == sizeof(is3d_particle),
               "is3d_particle is the sampler's 96-byte record");
-
-static int df_fail(is3d_engine* e, int derr) {
-  if (derr == DF_SPLINE_RANGE) return e->fail(IS3D_ERR_DF_RANGE, "gsl: interpolation error (df coefficient spline evaluated out of range)");
-  if (derr == DF_TABLE_RANGE) return e->fail(IS3D_ERR_DF_RANGE, "Error: (T,muB) outside df coefficient table");
-  if (derr == DF_PTB_BARYON) return e->fail(IS3D_ERR_UNSUPPORTED, "Bilinear interpolation error: Jonah df doesn't work for nonzero muB. Exiting..");
-  return e->fail(IS3D_ERR_ARG, "df coefficient error");
-}
 
 // cell_base: global index of this engine's cell 0 (a shard of a device-list engine holds only its window)
 static is3d::sampler::Bins sampler_bins(const is3d_sample_bins& b) {
@@ -2736,34 +1937,20 @@ int is3d_internal_sample(is3d_engine* e, const is3d_sample_params* sp, const dou
   c.run.y_max = e->p.dimension == 2 ? sp->y_cut : 0.5;
   c.run.Tavg = plasma[0]; c.run.F_avg = 0.0; c.run.betabulk_avg = 1.0;
   c.tb = e->dtb; c.surf = e->d_surf; c.n = e->ncell;
-  c.lo = e->win_hi >= 0 ? e->win_lo : 0; c.hi = e->win_hi >= 0 ? e->win_hi : e->ncell;
+  cell_window(e, c.lo, c.hi);
   c.cell_base = cell_base; c.seed = (uint64_t)sp->seed; c.n_events = sp->n_events; c.sample_bytes = e->sample_bytes;
-  double* d_dens = nullptr;
+  DevBuf<double> dens;
   if (sp->fast) {     // Plasma-average densities (DeltafData.cpp:555-690) and PTM's average df coefficients (:664-673)
-    d_dens = dalloc<double>(3 * (size_t)np);
-    if (!d_dens) return e->fail(IS3D_ERR_DEVICE, "hipMalloc failed");
-    HIPCHK(e, hipMemset(e->d_err, 0, sizeof(int)));
-    DensArgs da{};
-    da.tb = e->dtb; da.gla = e->d_gla; da.gla_alpha = e->gla_alpha; da.gla_pts = e->gla_pts;
-    da.T = plasma[0]; da.E = plasma[1]; da.P = plasma[2]; da.muB = plasma[3]; da.nB = plasma[4];
-    da.smass = e->d_smass; da.ssign = e->d_ssign; da.sdegen = e->d_sdegen; da.sbaryon = e->d_sbaryon; da.sorig = e->d_sorig;
-    da.npart = np; da.df_mode = e->p.df_mode; da.two_pi2_hbarC3 = 2.0 * std::pow(M_PI, 2) * std::pow(kHbarC, 3);
-    da.dens = d_dens; da.err = e->d_err;
-    hipLaunchKernelGGL(k_densities, dim3((unsigned)np), dim3(64), 0, 0, da);
-    hipError_t h = hipGetLastError();
-    if (h == hipSuccess) h = hipDeviceSynchronize();
-    int derr = 0;
-    if (h == hipSuccess) h = hipMemcpy(&derr, e->d_err, sizeof(int), hipMemcpyDeviceToHost);
-    if (h != hipSuccess || derr) dfree(d_dens);
-    if (h != hipSuccess) return hip_fail(e, h, "sampler densities");
-    if (derr) return df_fail(e, derr);
+    if (!dens.reserve(3L * np)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc failed");
+    const int derr = plasma_densities(e, plasma, dens.get());
+    if (derr) return derr < 0 ? IS3D_ERR_DEVICE : df_error(e, derr, "df coefficient error");
     if (e->p.df_mode == PTM) {
       double o[15];
       rc = is3d_evaluate_df_coefficients(e, plasma[0], plasma[3], 0.0, 0.0, 0.0, o);
-      if (rc) { dfree(d_dens); return rc; }
+      if (rc) return rc;
       c.run.F_avg = o[6]; c.run.betabulk_avg = o[8];
     }
-    c.dens = d_dens;
+    c.dens = dens.get();
   }
   is3d::sampler::Bins sb{};
   if (binned) {
@@ -2771,30 +1958,22 @@ int is3d_internal_sample(is3d_engine* e, const is3d_sample_params* sp, const dou
     e->hist_nc = is3d::sampler::hist_counts(sb, np);
     e->hist_nv = is3d::sampler::hist_vn(sb, np);
     const long words = e->hist_nc + e->hist_nv;
-    hipError_t h = hipSuccess;
-    if (words > e->hist_cap) {
-      dfree(e->d_hist);
-      e->d_hist = nullptr; e->hist_cap = 0;
-      h = hipMalloc((void**)&e->d_hist, (size_t)words * sizeof(unsigned long long));
-      if (h == hipSuccess) e->hist_cap = words;
-    }
-    if (h == hipSuccess) h = hipMemset(e->d_hist, 0, (size_t)words * sizeof(unsigned long long));
-    if (h != hipSuccess) { dfree(d_dens); return hip_fail(e, h, "sampler histogram"); }
-    c.bins = &sb; c.hist = e->d_hist; c.keep_list = binned == 2;
+    if (!e->d_hist.reserve(words)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(sampler histogram) failed");
+    HIPCHK(e, hipMemset(e->d_hist.get(), 0, (size_t)words * sizeof(unsigned long long)));
+    c.bins = &sb; c.hist = e->d_hist.get(); c.keep_list = binned == 2;
   }
   is3d::sampler::Stats st;
   int derr = 0;
   std::string msg;
   const int s = is3d::sampler::run(e->smp, c, e->particles, e->particle_offsets, st, derr, msg);
-  dfree(d_dens);
-  if (s == is3d::sampler::S_DF) return df_fail(e, derr);
+  if (s == is3d::sampler::S_DF) return df_error(e, derr, "df coefficient error");
   if (s == is3d::sampler::S_DEVICE) return e->fail(IS3D_ERR_DEVICE, "is3d_sample: " + msg);
   if (s == is3d::sampler::S_BUDGET) return e->fail(IS3D_ERR_ARG, "is3d_sample: " + msg);
   e->sst = is3d_sample_stats{st.cells, st.breakdown, st.candidates, st.kept, st.proposals, st.acceptances, st.capped,
                              st.clamped, st.batches};
   if (binned) {
     e->hist.assign((size_t)(e->hist_nc + e->hist_nv), 0);
-    HIPCHK(e, hipMemcpy(e->hist.data(), e->d_hist, e->hist.size() * sizeof(long long), hipMemcpyDeviceToHost));
+    HIPCHK(e, hipMemcpy(e->hist.data(), e->d_hist.get(), e->hist.size() * sizeof(long long), hipMemcpyDeviceToHost));
     e->binned = true;
   }
   e->sampled = true;

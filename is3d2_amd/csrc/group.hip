@@ -5,7 +5,7 @@
 // prep), any other cell costs one unit.  PTMA with the reference's warm-start chains (famod_chains = C > 0,
 // MomentumSpectra.cpp:1308-1364) is a serial recurrence over the whole surface (chain c = cells c, c + C, ...):
 // every device holds the whole surface, its window is a range of chain positions [q0, q1) (cells [q0 C, q1 C)),
-// and it solves only those positions' Newton steps -- the segmented solve of engine.hip k_chain_pass, with the
+// and it solves only those positions' Newton steps -- the segmented solve of engine_kernels.h k_chain_pass, with the
 // first segment of each chain starting from the end state the previous device pushes after every pass (a peer
 // copy of 4 C + 1 doubles) and a sequential finisher hand-off -- so the solutions are the single-device ones
 // bit for bit while each device does 1/K of the prepass (IS3D_CHAIN_DIST=0: every device walks every chain).
@@ -280,21 +280,29 @@ static void chain_windows(Group* g, long n) {
   }
 }
 
+// The shards' windows of a new surface of n cells; f: its host tau, dat, dax, day, dan, ux, uy, un.
+// PTM / PTB: the separable-fallback cells cost 1.4 / 1.8 of a modified one; the prepass on shard 0 knows which
+// cells they are once whole_to_shard0 has put the whole surface there (the tables must be set: otherwise the
+// u.dsigma model)
+template <class U>
+static void place_windows(Group* g, long n, const double* const f[8], U whole_to_shard0) {
+  g->ncell = n;
+  std::vector<double> cost;
+  if (g->sh.size() > 1 && n > 0 && cost_prepass(g) && whole_to_shard0(g->sh[0]) == IS3D_OK) {
+    cost.resize((size_t)n);
+    if (is3d_cell_costs(g->sh[0], cost.data()) != IS3D_OK) cost.clear();
+  }
+  balance(g, n, f[0], f[1], f[2], f[3], f[4], f[5], f[6], f[7], cost.empty() ? nullptr : cost.data());
+  g->full = needs_full(g);
+  if (g->full) chain_windows(g, n);
+}
+
 int group_set_surface(Group* g, long n, const is3d_surface* s) {
   if (!s || n < 0) return g->fail(IS3D_ERR_ARG, "bad surface");
   if (n > 0 && (!s->tau || !s->dat || !s->dax || !s->day || !s->dan || !s->ux || !s->uy || !s->un))
     return g->fail(IS3D_ERR_ARG, "surface field missing");
-  g->ncell = n;
-  // PTM / PTB: the separable-fallback cells cost 1.4 / 1.8 of a modified one; the prepass on shard 0 knows which
-  // cells they are (the tables must be set: otherwise the u.dsigma model)
-  std::vector<double> cost;
-  if (g->sh.size() > 1 && n > 0 && cost_prepass(g) && is3d_set_surface(g->sh[0], n, s) == IS3D_OK) {
-    cost.resize((size_t)n);
-    if (is3d_cell_costs(g->sh[0], cost.data()) != IS3D_OK) cost.clear();
-  }
-  balance(g, n, s->tau, s->dat, s->dax, s->day, s->dan, s->ux, s->uy, s->un, cost.empty() ? nullptr : cost.data());
-  g->full = needs_full(g);
-  if (g->full) chain_windows(g, n);
+  const double* const f[8] = {s->tau, s->dat, s->dax, s->day, s->dan, s->ux, s->uy, s->un};
+  place_windows(g, n, f, [&](is3d_engine* e) { return is3d_set_surface(e, n, s); });
   return each_parallel(g, [&](int k) -> int {
     is3d_engine* e = g->sh[k];
     if (g->full) {
@@ -321,17 +329,9 @@ int group_set_surface_device(Group* g, long n, const double* dev_fields) {
   for (int i = 0; i < 8 && n > 0; i++)
     if (hipMemcpy(h.data() + (size_t)i * n, dev_fields + (size_t)fidx[i] * n, n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
       return g->fail(IS3D_ERR_DEVICE, "surface read-back failed");
-  g->ncell = n;
-  std::vector<double> cost;
-  if (g->sh.size() > 1 && n > 0 && cost_prepass(g) &&
-      is3d_internal_copy_surface(g->sh[0], n, dev_fields, n, g->dev[0], 0) == IS3D_OK) {
-    cost.resize((size_t)n);
-    if (is3d_cell_costs(g->sh[0], cost.data()) != IS3D_OK) cost.clear();
-  }
-  balance(g, n, h.data(), h.data() + n, h.data() + 2 * n, h.data() + 3 * n, h.data() + 4 * n, h.data() + 5 * n,
-          h.data() + 6 * n, h.data() + 7 * n, cost.empty() ? nullptr : cost.data());
-  g->full = needs_full(g);
-  if (g->full) chain_windows(g, n);
+  const double* f[8];
+  for (int i = 0; i < 8; i++) f[i] = h.data() + (size_t)i * n;
+  place_windows(g, n, f, [&](is3d_engine* e) { return is3d_internal_copy_surface(e, n, dev_fields, n, g->dev[0], 0); });
   return each_parallel(g, [&](int k) -> int {
     is3d_engine* e = g->sh[k];
     const long o = g->full ? 0 : g->lo[k], m = g->full ? n : g->hi[k] - g->lo[k];
@@ -537,29 +537,10 @@ int group_finish(Group* g) {
   return IS3D_OK;
 }
 
-int group_calculate_spectra(Group* g, double* dN_out) {
-  if (!dN_out) return g->fail(IS3D_ERR_ARG, "null output");
-  const long n = group_output_size(g);
-  if (n <= 0) return g->fail(IS3D_ERR_STATE, "species / grids / params not set");
-  (void)hipSetDevice(g->dev[0]);
-  if (g->out_n < n) {
-    if (g->d_out) (void)hipFree(g->d_out);
-    g->d_out = nullptr;
-    if (hipMalloc(&g->d_out, n * sizeof(double)) != hipSuccess) return g->fail(IS3D_ERR_DEVICE, "hipMalloc(output) failed");
-    g->out_n = n;
-  }
-  int rc = group_launch(g, g->d_out, nullptr);
-  if (!rc) rc = group_finish(g);
-  if (rc) return rc;
-  (void)hipSetDevice(g->dev[0]);
-  if (hipMemcpy(dN_out, g->d_out, n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
-    return g->fail(IS3D_ERR_DEVICE, "spectra download failed");
-  return IS3D_OK;
-}
-
-int group_calculate_polarization(Group* g, double T_avg, double* S_out) {
-  if (!S_out) return g->fail(IS3D_ERR_ARG, "null output");
-  const long n = 5 * group_output_size(g);
+// launch_shards into the group's device-0 output buffer, finished and downloaded to `out`
+static int calculate(Group* g, bool polzn, double T_avg, double* out) {
+  if (!out) return g->fail(IS3D_ERR_ARG, "null output");
+  const long n = (polzn ? 5 : 1) * group_output_size(g);
   if (n <= 0) return g->fail(IS3D_ERR_STATE, "species / grids / params not set");
   (void)hipSetDevice(g->dev[0]);
   if (g->out_n < n) {
@@ -569,14 +550,18 @@ int group_calculate_polarization(Group* g, double T_avg, double* S_out) {
     if (hipMalloc(&g->d_out, n * sizeof(double)) != hipSuccess) return g->fail(IS3D_ERR_DEVICE, "hipMalloc(output) failed");
     g->out_n = n;
   }
-  int rc = group_launch_polarization(g, T_avg, g->d_out, nullptr);
+  int rc = launch_shards(g, g->d_out, nullptr, polzn, T_avg);
   if (!rc) rc = group_finish(g);
   if (rc) return rc;
   (void)hipSetDevice(g->dev[0]);
-  if (hipMemcpy(S_out, g->d_out, n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
-    return g->fail(IS3D_ERR_DEVICE, "polarization download failed");
+  if (hipMemcpy(out, g->d_out, n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+    return g->fail(IS3D_ERR_DEVICE, polzn ? "polarization download failed" : "spectra download failed");
   return IS3D_OK;
 }
+
+int group_calculate_spectra(Group* g, double* dN_out) { return calculate(g, false, 0.0, dN_out); }
+
+int group_calculate_polarization(Group* g, double T_avg, double* S_out) { return calculate(g, true, T_avg, S_out); }
 
 int group_calculate_dN_dX(Group* g, double* tau, double* r, double* phi) {
   if (!tau || !r || !phi) return g->fail(IS3D_ERR_ARG, "null output");

@@ -3,7 +3,7 @@
 It implements the staged-launch calls is3d2_amd.dist.launch_chained makes on an engine (launch_begin, chain_passes,
 chain_pass, chain_end, launch_end, chain_boundary_size / _get / _put) with the oracle's chain step
 (oracle.FamodChain, MomentumSpectra.cpp:1288-1368) as the worker, so the gloo tests run the protocol itself -- the
-same code bench.py drives over RCCL -- on the CPU.  It follows engine.hip's k_chain_pass / k_chain_finish at the
+same code bench.py drives over RCCL -- on the CPU.  It follows engine_kernels.h's k_chain_pass / k_chain_finish at the
 granularity of one segment per chain and rank:
 
   pass 0      every chain's positions [q0, q1) from a cold start (exact on rank 0);

@@ -1,5 +1,5 @@
 """GPU tier: PTMA warm-start chains (MomentumSpectra.cpp:1308-1364) on the segmented chain solver
-(engine.hip k_chain_pass / k_chain_finish) against the oracle's serial chains.
+(engine_kernels.h k_chain_pass / k_chain_finish) against the oracle's serial chains.
 
 The reference warm-starts every Newton solve from the state the previous cell of its OpenMP thread left; as
 shipped it is serial (one chain).  The engine cuts each chain into segments solved in parallel and

@@ -4,7 +4,7 @@ MomentumSpectra.cpp:1132-1135, 1308-1364) -- the bench's config-5 line, where th
 days.  test_gpu_configs.py::test_config5_miniature pins the same physics to the oracle on 8 cells; here the full
 path is held to size-independent properties:
 
-* the segmented chain solve (engine.hip k_chain_pass: up to 24 passes, then the serial finisher) reaches the serial
+* the segmented chain solve (engine_kernels.h k_chain_pass: up to 24 passes, then the serial finisher) reaches the serial
   chain's fixed point whatever the pass count: with IS3D_CHAIN_PASSES=2 the finisher carries whatever ripple the
   later passes of the default schedule would have resolved, and the Newton iteration /
   breakdown / p_L < 0 counts are the default schedule's exactly (one pass would leave every one of the ~16k
