@@ -30,6 +30,7 @@
  *   is3d_sample / is3d_get_particles  sample_dN_pTdpTdphidy, operation = 2      (ParticleSampler.cpp:638-1134)
  *   is3d_sample_binned                ... with test_sampler = 1: the binned     (BinSampledParticle.cpp:9-133,
  *                                     distributions of the kept particles        ParticleSampler.cpp:1112-1121)
+ *   is3d_sample_famod                 sample_dN_pTdpTdphidy_famod, df_mode 5    (ParticleSampler.cpp:1138-1627)
  *
  * Conventions: caller-owned host buffers in and out; the engine owns its HBM
  * buffers.  Errors are return codes (never exit()); is3d_last_error() gives the
@@ -318,8 +319,9 @@ int is3d_launch_polarization(is3d_engine *e, double T_avg, double *dev_out, void
  * (IS3D_ERR_ARG with the size needed), never a truncation.  is3d_get_tuning("sample_batches") is the number of
  * batches of the last call.
  *
- * Not covered: df_mode 5 (sample_dN_pTdpTdphidy_famod): IS3D_ERR_UNSUPPORTED; bit parity with the reference's serial
- * random stream.  Errors: IS3D_ERR_STATE for a missing setup step, IS3D_ERR_ARG for n_events < 1,
+ * df_mode 5 has a method of its own, as in the reference (EmissionFunction.cpp:1255-1275): is3d_sample and
+ * is3d_sample_binned return IS3D_ERR_UNSUPPORTED for it, is3d_sample_famod (below) samples it.  Not covered: bit
+ * parity with the reference's serial random stream.  Errors: IS3D_ERR_STATE for a missing setup step, IS3D_ERR_ARG for n_events < 1,
  * y_cut <= 0 or a negative seed, IS3D_ERR_DF_RANGE as elsewhere. */
 typedef struct {
   long seed;                      /* >= 0 */
@@ -391,6 +393,32 @@ int is3d_get_sample_hist(const is3d_engine *e, long *counts, double *vn);
 /* Test hook: the first n uniforms in [0, 1) of the stream (seed, purpose 0 poisson / 1 type / 2 momentum /
  * 3 rapidity, cell, event, candidate), generated on the device (tests compare them with sampler_math.h on the host). */
 int is3d_sample_uniforms(is3d_engine *e, long seed, int purpose, long cell, long event, long candidate, int n, double *out);
+
+/* df_mode 5 (PTMA): sample_dN_pTdpTdphidy_famod (ParticleSampler.cpp:1138-1627).  binned = 0: the list (as
+ * is3d_sample); 1: binned only, 2: binned with the list (as is3d_sample_binned with keep_list = 0 / 1; both need
+ * is3d_set_sample_bins).  The method uses no Plasma averages and has no fast branch: p->fast is ignored.  Results
+ * come through the getters above (is3d_sample_count / _offsets, is3d_get_particles, is3d_get_sample_stats,
+ * is3d_get_sample_hist); streams, order, batches, cell window and device list behave as for is3d_sample.
+ *
+ * Each call first reconstructs (lambda, aT, aL) of every cell along the reference's serial chain under the sampler's
+ * rule (:1330-1399: unlike the spectra's, a failed cold solve with no previous success breaks the cell down and counts
+ * a failure).  famod_chains means what it means for the spectra: C >= 1 strided chains (1: the reference's loop), each
+ * walking every cell of the surface whatever cell window is sampled; 0: every cell cold.  A device-list engine with
+ * famod_chains > 0 solves the whole chain on every shard, with 0 each shard solves its window.  A broken-down cell
+ * (pl or pt < 0, a failed reconstruction, det B <= deta_min) samples feq at the (lambda, aT, aL) it ends with, B = 1;
+ * is3d_sample_stats.breakdown counts the live ones of the window.  The species weights carry the reference's
+ * exp(Ebar + chem) (:1493).  is3d_get_sample_famod_stats: the counters of the reference's closing lines, over the
+ * cells the reconstruction covered (the surface; the cell window when famod_chains = 0).
+ *
+ * Errors: IS3D_ERR_STATE when df_mode is not 5, no PDG table is set, no bins are set for binned != 0, or a chain
+ * range (is3d_set_chain_range) is set; otherwise the argument and budget errors of is3d_sample. */
+typedef struct {
+  long plpt_negative;             /* cells with pl < 0 or pt < 0 */
+  long reconstruction_fail;       /* failed reconstructions, the sampler's rule */
+  long iterations;                /* Newton iterations */
+} is3d_sample_famod_stats;
+int is3d_sample_famod(is3d_engine *e, const is3d_sample_params *p, int binned);
+int is3d_get_sample_famod_stats(const is3d_engine *e, is3d_sample_famod_stats *out);
 
 #ifdef __cplusplus
 }

@@ -26,7 +26,7 @@ EXPORTS = ["is3d_abi_version", "is3d_build_id", "is3d_create", "is3d_create_devi
            "is3d_set_vorticity", "is3d_polarization_size", "is3d_calculate_polarization", "is3d_launch_polarization",
            "is3d_sample", "is3d_sample_count", "is3d_sample_offsets", "is3d_get_particles", "is3d_get_sample_stats",
            "is3d_sample_uniforms", "is3d_set_sample_bins", "is3d_sample_binned", "is3d_sample_hist_size",
-           "is3d_get_sample_hist"]
+           "is3d_get_sample_hist", "is3d_sample_famod", "is3d_get_sample_famod_stats"]
 
 VORTICITY_FIELDS = ["wtx", "wty", "wtn", "wxy", "wxn", "wyn"]
 
@@ -75,6 +75,11 @@ PARTICLE_DTYPE = [("species", "<i4"), ("event", "<i4"), ("cell", "<i8")] + \
 class SampleStats(C.Structure):
     _fields_ = [(k, C.c_long) for k in ("cells", "breakdown", "candidates", "kept", "proposals", "acceptances",
                                         "capped", "clamped", "batches")]
+
+
+class SampleFamodStats(C.Structure):
+    """is3d_sample_famod_stats: the reconstruction counters of the last is3d_sample_famod."""
+    _fields_ = [(k, C.c_long) for k in ("plpt_negative", "reconstruction_fail", "iterations")]
 
 
 class SampleBins(C.Structure):
@@ -165,6 +170,8 @@ def load():
     lib.is3d_sample_uniforms.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_long, C.c_long, C.c_long, C.c_int, pd]
     lib.is3d_set_sample_bins.argtypes = [C.c_void_p, P(SampleBins)]
     lib.is3d_sample_binned.argtypes = [C.c_void_p, P(SampleParams), pd, C.c_int]
+    lib.is3d_sample_famod.argtypes = [C.c_void_p, P(SampleParams), C.c_int]
+    lib.is3d_get_sample_famod_stats.argtypes = [C.c_void_p, P(SampleFamodStats)]
     lib.is3d_sample_hist_size.restype = C.c_long
     lib.is3d_sample_hist_size.argtypes = [C.c_void_p, P(C.c_long), P(C.c_long)]
     lib.is3d_get_sample_hist.argtypes = [C.c_void_p, P(C.c_long), pd]

@@ -191,7 +191,8 @@ struct is3d_engine {
   std::vector<is3d::sampler::Particle> particles;
   std::vector<long> particle_offsets;
   is3d_sample_stats sst{};
-  bool sampled = false;
+  is3d_sample_famod_stats sfst{};   // is3d_sample_famod: the reconstruction counters of the last call
+  bool sampled = false, sampled_famod = false;
   // test_sampler = 1: the bins, the device histogram of a binned call (zeroed at its start) and its host copy in
   // integer form (hist_nc counts, then hist_nv fixed-point vn sums)
   is3d_sample_bins sbins{};
@@ -1000,18 +1001,19 @@ static int plasma_densities(is3d_engine* e, const double* plasma, double* dens) 
 // chains), launch_end (PTMA C/B matrices, PTM renormalisation, the integral, the reduction).  is3d_launch runs them
 // back to back; a device group whose shards solve their own ranges of the chains (group.hip) interleaves the
 // shards' passes with the boundary hand-offs between them.
-static int launch_begin(is3d_engine* e, double* dev_out, void* stream, long q0, long q1, int has_pred) {
-  int rc = finalize_tables(e);
-  if (rc) return rc;
-  if (!dev_out) return e->fail(IS3D_ERR_ARG, "null output buffer");
+//
+// prepass_begin is launch_begin without an output buffer: it starts the launch context, enqueues the records and, for
+// PTMA, the Newton inputs and the (lambda, aT, aL) solution d_sol [6][n] -- cold (k_aniso) or the start of the chains
+// that chain_pass x npass + chain_end complete -- with the counters in d_cnt.  srule: the chain rule (aniso_math.h
+// aniso_cell), 0 for the spectra, 1 for the particle sampler (is3d_sample_famod).  L.empty: no cell in the window.
+static int prepass_begin(is3d_engine* e, void* stream, long q0, long q1, int has_pred, int srule) {
   HIPCHK(e, hipSetDevice(e->device));
   LaunchCtx& L = e->lc;
   L = LaunchCtx{};
   hipStream_t st = (hipStream_t)stream;
-  L.st = st; L.dev_out = dev_out;
+  L.st = st;
   const long n = e->ncell;
   const int mode = e->p.df_mode;
-  const long outsize = is3d_output_size(e);
   // cell window (group shards holding the whole surface): k_spectra integrates [wlo, whi); the prepass covers
   // the window too, except for PTMA's warm-start chains, which walk every cell (MomentumSpectra.cpp:1308-1364) --
   // or, when a device group splits the chains (q1 >= 0), the cells of this shard's positions, which are its window
@@ -1022,11 +1024,10 @@ static int launch_begin(is3d_engine* e, double* dev_out, void* stream, long q0, 
   const bool split_chain = chained && q1 >= 0;
   const long p0 = chained && !split_chain ? 0 : wlo, p1 = chained && !split_chain ? n : whi;
   L.wlo = wlo; L.whi = whi; L.nw = nw; L.p0 = p0; L.p1 = p1; L.chained = chained;
-  rc = begin_stats(e, nw, st);
+  int rc = begin_stats(e, nw, st);
   if (rc) return rc;
   if (nw == 0) {
     L.empty = true;
-    HIPCHK(e, hipMemsetAsync(dev_out, 0, outsize * sizeof(double), st));
     return IS3D_OK;
   }
   if (!e->d_rec.reserve((long)NREC * n)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(records) failed");
@@ -1044,6 +1045,7 @@ static int launch_begin(is3d_engine* e, double* dev_out, void* stream, long q0, 
     aa.h = Hadrons{nh, e->d_aniso_h, e->d_aniso_h + nh, e->d_aniso_h + 2 * nh};
     aa.fp2 = 4.0 * std::pow(M_PI, 2) * std::pow(kHbarC, 3);
     aa.cnt = e->d_cnt.get();
+    aa.srule = srule;
     if (!chained) {
       hipLaunchKernelGGL(k_aniso, dim3((unsigned)aa.chains), dim3(64), 0, st, aa);
       HIPCHK(e, hipGetLastError());
@@ -1052,6 +1054,7 @@ static int launch_begin(is3d_engine* e, double* dev_out, void* stream, long q0, 
       // GPU full
       ChainArgs& ca = L.ca;
       ca.rec = e->d_rec.get(); ca.ain = e->d_aux.get(); ca.sol = e->d_sol.get(); ca.n = n; ca.C = aa.chains; ca.h = aa.h; ca.fp2 = aa.fp2;
+      ca.srule = srule;
       const long P = (n + ca.C - 1) / ca.C;
       ca.q0 = split_chain ? q0 : 0;
       ca.q1 = split_chain ? std::min(q1, P) : P;
@@ -1077,6 +1080,17 @@ static int launch_begin(is3d_engine* e, double* dev_out, void* stream, long q0, 
       HIPCHK(e, hipMemsetAsync(ca.changed, 0, kChainPasses * sizeof(int), st));
     }
   }
+  return IS3D_OK;
+}
+
+static int launch_begin(is3d_engine* e, double* dev_out, void* stream, long q0, long q1, int has_pred) {
+  int rc = finalize_tables(e);
+  if (rc) return rc;
+  if (!dev_out) return e->fail(IS3D_ERR_ARG, "null output buffer");
+  rc = prepass_begin(e, stream, q0, q1, has_pred, 0);
+  if (rc) return rc;
+  e->lc.dev_out = dev_out;
+  if (e->lc.empty) HIPCHK(e, hipMemsetAsync(dev_out, 0, is3d_output_size(e) * sizeof(double), e->lc.st));
   return IS3D_OK;
 }
 
@@ -1908,13 +1922,20 @@ static is3d::sampler::Bins sampler_bins(const is3d_sample_bins& b) {
                                   b.tau_min, b.tau_max, b.tau_bins, b.r_min, b.r_max, b.r_bins);
 }
 
-int is3d_internal_sample(is3d_engine* e, const is3d_sample_params* sp, const double* plasma, long cell_base, int binned) {
+// famod: the df_mode 5 method (is3d_sample_famod; plasma unused, fast ignored): the Newton prepass under the sampler's
+// chain rule first, then the same sampler with the k_cells / k_sample famod variants reading d_sol
+static int sample_any(is3d_engine* e, const is3d_sample_params* sp, const double* plasma, long cell_base, int binned,
+                      bool famod) {
   if (!e || e->grp) return IS3D_ERR_ARG;
   e->sampled = false;
   e->binned = false;
-  if (!sp || !plasma) return e->fail(IS3D_ERR_ARG, "is3d_sample: null argument");
-  if (e->have_params && e->p.df_mode == PTMA)
-    return e->fail(IS3D_ERR_UNSUPPORTED, "is3d_sample: the df_mode 5 sampler (sample_dN_pTdpTdphidy_famod) is not built; df_mode 1-4 only");
+  if (!sp || (!famod && !plasma)) return e->fail(IS3D_ERR_ARG, "is3d_sample: null argument");
+  if (!famod && e->have_params && e->p.df_mode == PTMA)
+    return e->fail(IS3D_ERR_UNSUPPORTED, "is3d_sample: df_mode 5 has its own method (sample_dN_pTdpTdphidy_famod): call is3d_sample_famod");
+  if (famod && (!e->have_params || e->p.df_mode != PTMA))
+    return e->fail(IS3D_ERR_STATE, "is3d_sample_famod: needs params with df_mode 5 (df_mode 1-4: is3d_sample)");
+  if (famod && e->pdg_mass.empty()) return e->fail(IS3D_ERR_STATE, "is3d_sample_famod: no PDG table set (is3d_set_pdg)");
+  if (famod && e->chain_q1 >= 0) return e->fail(IS3D_ERR_STATE, "is3d_sample_famod: a chain range is set (is3d_set_chain_range); the sampler solves the whole chain");
   if (sp->n_events < 1) return e->fail(IS3D_ERR_ARG, "is3d_sample: n_events must be >= 1");
   if (!(sp->y_cut > 0.0)) return e->fail(IS3D_ERR_ARG, "is3d_sample: y_cut must be positive");
   if (sp->seed < 0) return e->fail(IS3D_ERR_ARG, "is3d_sample: the seed must be non-negative (a negative sampler_seed takes the clock on the host)");
@@ -1922,7 +1943,8 @@ int is3d_internal_sample(is3d_engine* e, const is3d_sample_params* sp, const dou
   int rc = finalize_tables(e);
   if (rc) return rc;
   if (!e->have_surf) return e->fail(IS3D_ERR_STATE, "is3d_sample: no surface set");
-  if (!e->have_gla || e->gla_alpha < (sp->fast ? 4 : 3)) return e->fail(IS3D_ERR_STATE, "is3d_set_gauss_laguerre: alpha = 1..3 tables needed");
+  const int fast = (sp->fast && !famod) ? 1 : 0;
+  if (!e->have_gla || e->gla_alpha < (fast ? 4 : 3)) return e->fail(IS3D_ERR_STATE, "is3d_set_gauss_laguerre: alpha = 1..3 tables needed");
   if (e->gla_pts > 64) return e->fail(IS3D_ERR_ARG, "Gauss-Laguerre table longer than 64 points");
   HIPCHK(e, hipSetDevice(e->device));
   if (e->smp_dirty) {
@@ -1933,14 +1955,14 @@ int is3d_internal_sample(is3d_engine* e, const is3d_sample_params* sp, const dou
   const int np = (int)e->mass.size();
   is3d::sampler::Config c;
   c.run.k = make_consts(e);
-  c.run.fast = sp->fast ? 1 : 0;
+  c.run.fast = fast;
   c.run.y_max = e->p.dimension == 2 ? sp->y_cut : 0.5;
-  c.run.Tavg = plasma[0]; c.run.F_avg = 0.0; c.run.betabulk_avg = 1.0;
+  c.run.Tavg = famod ? 0.0 : plasma[0]; c.run.F_avg = 0.0; c.run.betabulk_avg = 1.0;
   c.tb = e->dtb; c.surf = e->d_surf; c.n = e->ncell;
   cell_window(e, c.lo, c.hi);
   c.cell_base = cell_base; c.seed = (uint64_t)sp->seed; c.n_events = sp->n_events; c.sample_bytes = e->sample_bytes;
   DevBuf<double> dens;
-  if (sp->fast) {     // Plasma-average densities (DeltafData.cpp:555-690) and PTM's average df coefficients (:664-673)
+  if (fast) {     // Plasma-average densities (DeltafData.cpp:555-690) and PTM's average df coefficients (:664-673)
     if (!dens.reserve(3L * np)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc failed");
     const int derr = plasma_densities(e, plasma, dens.get());
     if (derr) return derr < 0 ? IS3D_ERR_DEVICE : df_error(e, derr, "df coefficient error");
@@ -1951,6 +1973,20 @@ int is3d_internal_sample(is3d_engine* e, const is3d_sample_params* sp, const dou
       c.run.F_avg = o[6]; c.run.betabulk_avg = o[8];
     }
     c.dens = dens.get();
+  }
+  if (famod && c.hi > c.lo) {
+    // (lambda, aT, aL) of the cells: the whole surface along the chains, or the window cold (famod_chains = 0)
+    rc = prepass_begin(e, nullptr, 0, -1, 0, 1);
+    for (int pass = 0; !rc && e->lc.chained && pass < e->lc.ca.npass; pass++) rc = chain_pass(e, pass);
+    if (!rc) rc = chain_end(e);
+    if (rc) return rc;
+    unsigned long long cnt[4] = {0, 0, 0, 0};
+    HIPCHK(e, hipStreamSynchronize(nullptr));
+    HIPCHK(e, hipMemcpy(cnt, e->d_cnt.get(), sizeof(cnt), hipMemcpyDeviceToHost));
+    e->sfst = is3d_sample_famod_stats{(long)cnt[1], (long)cnt[2], (long)cnt[3]};
+    c.sol = e->d_sol.get();
+  } else if (famod) {
+    e->sfst = is3d_sample_famod_stats{};
   }
   is3d::sampler::Bins sb{};
   if (binned) {
@@ -1977,6 +2013,28 @@ int is3d_internal_sample(is3d_engine* e, const is3d_sample_params* sp, const dou
     e->binned = true;
   }
   e->sampled = true;
+  e->sampled_famod = famod;
+  return IS3D_OK;
+}
+
+int is3d_internal_sample(is3d_engine* e, const is3d_sample_params* sp, const double* plasma, long cell_base, int binned) {
+  return sample_any(e, sp, plasma, cell_base, binned, false);
+}
+int is3d_internal_sample_famod(is3d_engine* e, const is3d_sample_params* sp, long cell_base, int binned) {
+  return sample_any(e, sp, nullptr, cell_base, binned, true);
+}
+
+extern "C" int is3d_sample_famod(is3d_engine* e, const is3d_sample_params* sp, int binned) {
+  if (e && e->grp) return is3d::group_sample_famod(e->grp, sp, binned);
+  if (e && (binned < 0 || binned > 2)) return e->fail(IS3D_ERR_ARG, "is3d_sample_famod: binned must be 0, 1 or 2");
+  return is3d_internal_sample_famod(e, sp, 0, binned);
+}
+
+extern "C" int is3d_get_sample_famod_stats(const is3d_engine* e, is3d_sample_famod_stats* out) {
+  if (e && e->grp) return out ? is3d::group_get_sample_famod_stats(e->grp, out) : IS3D_ERR_ARG;
+  if (!e || !out) return IS3D_ERR_ARG;
+  if (!e->sampled || !e->sampled_famod) return IS3D_ERR_STATE;
+  *out = e->sfst;
   return IS3D_OK;
 }
 

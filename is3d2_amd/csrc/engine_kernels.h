@@ -118,6 +118,7 @@ struct AnisoArgs {
   Hadrons h;
   double fp2;
   unsigned long long* cnt;
+  int srule;            // the particle sampler's chain rule (aniso_math.h aniso_cell)
 };
 
 // one wavefront per warm-start chain: cells chain, chain + C, chain + 2C, ... (MomentumSpectra.cpp:98-107)
@@ -137,7 +138,7 @@ __global__ __launch_bounds__(64, 1) void k_aniso(AnisoArgs A) {
 #pragma unroll
     for (int f = 0; f < 4; f++) ain[f] = A.ain[(long)f * A.stride + c];
     double out[6];
-    aniso_cell(ain, h, lane, 64, WaveSum(), A.fp2, state, out, cnt);
+    aniso_cell(ain, h, lane, 64, WaveSum(), A.fp2, state, out, cnt, A.srule);
     if (lane == 0) {
 #pragma unroll
       for (int f = 0; f < 6; f++) A.sol[(long)f * A.stride + c] = out[f];
@@ -185,6 +186,7 @@ struct ChainArgs {
   double* bout;          // [3][4 C + 1] boundary out: this range's end states (position q1 - 1), same slots
   Hadrons h;
   double fp2;
+  int srule;             // the particle sampler's chain rule (aniso_math.h aniso_cell)
 };
 constexpr int kBndSlots = 3;   // bin / bout slots: pass parity 0, 1 and the finisher's
 
@@ -216,7 +218,7 @@ __device__ bool chain_segment_run(const ChainArgs& A, Hadrons h, long seg, doubl
     for (int f = 0; f < 4; f++) old[f] = A.sta[(long)f * A.n + cell];
     double out[6];
     long cnt[3] = {0, 0, 0};
-    aniso_cell(ain, h, lane, 64 * IS3D_CHAIN_W, BlockSum<IS3D_CHAIN_W>{s_red}, A.fp2, state, out, cnt);
+    aniso_cell(ain, h, lane, 64 * IS3D_CHAIN_W, BlockSum<IS3D_CHAIN_W>{s_red}, A.fp2, state, out, cnt, A.srule);
     const bool same = sync && state_eq(state, old);
     if (lane == 0) {
 #pragma unroll

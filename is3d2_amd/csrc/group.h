@@ -58,6 +58,9 @@ int group_calculate_polarization(Group* g, double T_avg, double* S_out);
 // binned (0: the list only, 1: the binned distributions only, 2: both): the group adds the shards' integer
 // histograms, which is the one-device histogram bit for bit
 int group_sample(Group* g, const is3d_sample_params* p, const double* plasma, int binned);
+// is3d_sample_famod (df_mode 5): the same merge; each shard reconstructs (lambda, aT, aL) itself first
+int group_sample_famod(Group* g, const is3d_sample_params* p, int binned);
+int group_get_sample_famod_stats(const Group* g, is3d_sample_famod_stats* out);
 int group_set_sample_bins(Group* g, const is3d_sample_bins* b);
 long group_sample_hist_size(const Group* g, long* n_counts, long* n_vn);
 int group_get_sample_hist(const Group* g, long* counts, double* vn);
@@ -81,6 +84,7 @@ long is3d_internal_chain_bnd_bytes(const is3d_engine* e);
 // is3d_sample on a shard whose cell 0 is the surface's cell cell_base
 // (binned: as group_sample)
 int is3d_internal_sample(is3d_engine* e, const is3d_sample_params* p, const double* plasma, long cell_base, int binned);
+int is3d_internal_sample_famod(is3d_engine* e, const is3d_sample_params* p, long cell_base, int binned);
 // the histogram of the last binned call in its integer form: n_counts counts, then the n_vn fixed-point vn sums
 const long long* is3d_internal_sample_hist(const is3d_engine* e);
 extern "C" {

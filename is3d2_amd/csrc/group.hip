@@ -63,7 +63,8 @@ struct Group {
   std::vector<is3d_particle> particles;
   std::vector<long> particle_offsets;
   is3d_sample_stats sstats{};
-  bool sampled = false;
+  is3d_sample_famod_stats sfstats{};
+  bool sampled = false, sampled_famod = false;
   // ... and the sum of the shards' integer histograms of the last binned call (counts, then fixed-point vn sums)
   std::vector<long long> hist;
   long hist_nc = 0, hist_nv = 0;
@@ -656,14 +657,21 @@ int group_get_sample_hist(const Group* g, long* counts, double* vn) {
   return IS3D_OK;
 }
 
-int group_sample(Group* g, const is3d_sample_params* p, const double* plasma, int binned) {
+// famod (is3d_sample_famod): with famod_chains > 0 every shard holds the whole surface, solves the whole chain itself
+// and samples its window; with famod_chains = 0 the shards hold their windows and solve them cold
+static int sample_shards(Group* g, const is3d_sample_params* p, const double* plasma, int binned, bool famod) {
   g->sampled = false;
+  g->sampled_famod = false;
   g->binned = false;
-  if (!p || !plasma) return g->fail(IS3D_ERR_ARG, "is3d_sample: null argument");
+  if (!p || (!famod && !plasma)) return g->fail(IS3D_ERR_ARG, "is3d_sample: null argument");
+  if (famod && (binned < 0 || binned > 2)) return g->fail(IS3D_ERR_ARG, "is3d_sample_famod: binned must be 0, 1 or 2");
   if (stale_split(g)) return g->fail(IS3D_ERR_STATE, kStaleSplit);
   const int K = (int)g->sh.size();
-  // a shard holding the whole surface (PTMA chains: rejected by the shard anyway) samples its window of it
-  const int rc = each_parallel(g, [&](int k) -> int { return is3d_internal_sample(g->sh[k], p, plasma, g->full ? 0 : (k < (int)g->lo.size() ? g->lo[k] : 0), binned); });
+  // a shard holding the whole surface (PTMA chains) samples its window of it
+  const int rc = each_parallel(g, [&](int k) -> int {
+    const long base = g->full ? 0 : (k < (int)g->lo.size() ? g->lo[k] : 0);
+    return famod ? is3d_internal_sample_famod(g->sh[k], p, base, binned) : is3d_internal_sample(g->sh[k], p, plasma, base, binned);
+  });
   if (rc) return rc;
   const long nev = p->n_events;
   std::vector<std::vector<long>> off(K, std::vector<long>((size_t)nev + 1, 0));
@@ -693,6 +701,16 @@ int group_sample(Group* g, const is3d_sample_params* p, const double* plasma, in
   }
   g->particle_offsets[nev] = at;
   g->sstats = agg;
+  if (famod) {       // the whole chain on every shard: its counters once (shard 0's); windows solved cold: their sum
+    is3d_sample_famod_stats f{};
+    for (int k = 0; k < (g->full ? 1 : K); k++) {
+      is3d_sample_famod_stats s{};
+      const int r = is3d_get_sample_famod_stats(g->sh[k], &s);
+      if (r) return g->shard_fail(k, r);
+      f.plpt_negative += s.plpt_negative; f.reconstruction_fail += s.reconstruction_fail; f.iterations += s.iterations;
+    }
+    g->sfstats = f;
+  }
   if (binned) {      // integer sums: exact, so the shard order plays no part
     if (is3d_sample_hist_size(g->sh[0], &g->hist_nc, &g->hist_nv) < 0) return g->shard_fail(0, IS3D_ERR_STATE);
     g->hist.assign((size_t)(g->hist_nc + g->hist_nv), 0);
@@ -704,6 +722,18 @@ int group_sample(Group* g, const is3d_sample_params* p, const double* plasma, in
     g->binned = true;
   }
   g->sampled = true;
+  g->sampled_famod = famod;
+  return IS3D_OK;
+}
+
+int group_sample(Group* g, const is3d_sample_params* p, const double* plasma, int binned) {
+  return sample_shards(g, p, plasma, binned, false);
+}
+int group_sample_famod(Group* g, const is3d_sample_params* p, int binned) { return sample_shards(g, p, nullptr, binned, true); }
+
+int group_get_sample_famod_stats(const Group* g, is3d_sample_famod_stats* out) {
+  if (!g->sampled || !g->sampled_famod) return IS3D_ERR_STATE;
+  *out = g->sfstats;
   return IS3D_OK;
 }
 

@@ -152,18 +152,22 @@ void EmissionFunctionArray::run_sharded(const RunOptions& opt, int operation) {
       is3d_sample_params sp{};
       sp.seed = sample_seed_; sp.n_events = (int)sample_events_; sp.fast = (int)p_.get("fast", 0.0);
       sp.y_cut = p_.get("y_cut", 0.5);
+      // df_mode 5 has a method of its own (EmissionFunction.cpp:1255-1275): sample_dN_pTdpTdphidy_famod
+      const bool famod = prm.df_mode == 5;
       if (operation == 4) {      // test_sampler = 1: binned only, no list (EmissionFunction.cpp:1279-1291)
         sbins_ = read_sample_bins(p_);
         set_or_throw(e, is3d_set_sample_bins(e, &sbins_));
-        set_or_throw(e, is3d_sample_binned(e, &sp, plasma, 0));
+        set_or_throw(e, famod ? is3d_sample_famod(e, &sp, 1) : is3d_sample_binned(e, &sp, plasma, 0));
         long nc = 0, nv = 0;
         if (is3d_sample_hist_size(e, &nc, &nv) < 0) throw EngineError(IS3D_ERR_STATE, "is3d_sample_hist_size failed");
         hist_counts_.assign((size_t)nc, 0);
         hist_vn_.assign((size_t)nv, 0.0);
         set_or_throw(e, is3d_get_sample_hist(e, hist_counts_.data(), hist_vn_.data()));
       } else {
-        set_or_throw(e, is3d_sample(e, &sp, plasma));
+        set_or_throw(e, famod ? is3d_sample_famod(e, &sp, 0) : is3d_sample(e, &sp, plasma));
       }
+      famod_sampled_ = famod;
+      if (famod) set_or_throw(e, is3d_get_sample_famod_stats(e, &famod_stats_));
       records_.assign((size_t)is3d_sample_count(e), is3d_particle{});
       sample_offsets_.assign((size_t)sample_events_ + 1, 0);
       set_or_throw(e, is3d_sample_offsets(e, sample_offsets_.data()));
@@ -352,6 +356,10 @@ void IS3D::run_particlization(int fo_from_file, const RunOptions& opt) {
       if (!opt.quiet) {
         const is3d_sample_stats& st = sample_stats_;
         std::printf("\nMomentum sampling efficiency = %f %%\n", st.proposals ? 100.0 * (double)st.acceptances / (double)st.proposals : 0.0);
+        if (efa.famod_sampled()) {       // the closing lines of sample_dN_pTdpTdphidy_famod (ParticleSampler.cpp:1625-1626)
+          std::printf("pl went negative for %ld / %ld cells\n\n", efa.famod_stats().plpt_negative, (long)surf->size());
+          std::printf("Number of reconstruction failures = %ld\n", efa.famod_stats().reconstruction_fail);
+        }
         std::printf("Sampled %ld particles in %ld events (%ld candidates, %ld dropped at an iteration cap)\n", st.kept, nevents_,
                     st.candidates, st.capped);
       }

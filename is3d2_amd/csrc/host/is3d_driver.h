@@ -8,7 +8,7 @@
 // Same inputs (iS3D_parameters.dat, input/surface.dat, PDG/, deltaf_coefficients/, tables/
 // relative to a working directory) and the same outputs (results/continuous/*.dat).
 // Differences from the reference: errors are returned / thrown instead of exit(); operation = 2 gives the
-// oversampling estimate (Ntotal, Nevents) and, with RunOptions::sample, the sampled particle lists of df_mode 1-4
+// oversampling estimate (Ntotal, Nevents) and, with RunOptions::sample, the sampled particle lists of df_mode 1-5
 // (the engine's counter-based streams, not the reference's serial random engine) or, with test_sampler = 1, the
 // binned results/sampled files instead of the lists; cells may be sharded over several GPUs in one process.
 #pragma once
@@ -64,7 +64,7 @@ class EmissionFunctionArray {
   const std::vector<long>& mcid() const { return mcid_; }
   // operation = 2 oversampling estimate (ParticleSampler.cpp:447-636): the reference's Ntotal
   double estimate_total_yield(const RunOptions& opt);
-  // operation = 2, the sampler (ParticleSampler.cpp:638-1134, df_mode 1-4): n_events events with the given
+  // operation = 2, the sampler (ParticleSampler.cpp:638-1134, df_mode 1-4; :1138-1627, df_mode 5): n_events events with the given
   // non-negative seed; sampled() = the list with the chosen table's mcID and mass filled, sample_offsets() its
   // n_events + 1 event offsets, sampled_records() the engine's records (species index, event, cell)
   void sample_particles(const RunOptions& opt, long seed, long n_events);
@@ -72,6 +72,10 @@ class EmissionFunctionArray {
   const std::vector<is3d_particle>& sampled_records() const { return records_; }
   const std::vector<long>& sample_offsets() const { return sample_offsets_; }
   const is3d_sample_stats& sample_stats() const { return sample_stats_; }
+  // df_mode 5: both went through is3d_sample_famod (sample_dN_pTdpTdphidy_famod, ParticleSampler.cpp:1138-1627);
+  // famod_stats() = its reconstruction counters
+  bool famod_sampled() const { return famod_sampled_; }
+  const is3d_sample_famod_stats& famod_stats() const { return famod_stats_; }
   // ... with test_sampler = 1 (ParticleSampler.cpp:1112-1121): the same events binned on the device with the parameter
   // file's bins and no list; hist_counts() / hist_vn() = is3d_get_sample_hist's arrays, write_sampled_files the
   // results/sampled/* tree (EmissionFunction.cpp:685-975)
@@ -114,6 +118,8 @@ class EmissionFunctionArray {
   std::vector<is3d_particle> records_;
   std::vector<long> sample_offsets_;
   is3d_sample_stats sample_stats_{};
+  is3d_sample_famod_stats famod_stats_{};
+  bool famod_sampled_ = false;
   is3d_sample_bins sbins_{};
   std::vector<long> hist_counts_;
   std::vector<double> hist_vn_;

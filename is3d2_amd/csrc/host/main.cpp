@@ -1,5 +1,5 @@
 // iS3D_amd -- drop-in replacement of the reference executable (src/cpp/Main.cpp) for
-// operations 1 (continuous spectra), 0 (spacetime distributions) and 2 (the particle sampler, df_mode 1-4: writes
+// operations 1 (continuous spectra), 0 (spacetime distributions) and 2 (the particle sampler, df_mode 1-5: writes
 // results/particle_list_osc_<event>.dat; IS3D_PARTICLE_CSV=1 also results/particle_list_<event>.dat; test_sampler = 1
 // bins the particles instead and writes the results/sampled/* tree, as the reference): run in a directory laid out
 // like the reference's (iS3D_parameters.dat,

@@ -1,6 +1,7 @@
 // sampler.h -- private interface between engine.hip and the operation = 2 particle sampler (sampler.hip).
 //
-// The GPU form of EmissionFunctionArray::sample_dN_pTdpTdphidy (ParticleSampler.cpp:638-1134; df_mode 1-4).  The
+// The GPU form of EmissionFunctionArray::sample_dN_pTdpTdphidy (ParticleSampler.cpp:638-1134; df_mode 1-4) and of
+// sample_dN_pTdpTdphidy_famod (:1138-1627; df_mode 5, Config::sol).  The
 // math, the random-number streams and the iteration caps are in sampler_math.h; the engine passes its surface and
 // tables as plain pointers, sampler.hip owns the working buffers of a call and returns the list on the host.
 #pragma once
@@ -30,6 +31,9 @@ struct Config {
   Run run;
   DfTables tb;
   const double* surf = nullptr;    // [25][n] field-major
+  // df_mode 5 (sample_dN_pTdpTdphidy_famod): [6][n] rows (lambda, aT, aL, broken, beta_pi_perp, beta_W_perp) of the
+  // Newton prepass under the sampler's chain rule (device); null for df_mode 1-4
+  const double* sol = nullptr;
   long n = 0, lo = 0, hi = 0;      // cells held and the window [lo, hi) sampled
   long cell_base = 0;              // global index of held cell 0 (a shard of a device-list engine)
   uint64_t seed = 0;

@@ -1,6 +1,8 @@
-// sampler.hip -- operation = 2 particle sampler (df_mode 1-4) on gfx950.
+// sampler.hip -- operation = 2 particle sampler on gfx950.
 //
-// GPU form of EmissionFunctionArray::sample_dN_pTdpTdphidy (ParticleSampler.cpp:638-1134); the math and the
+// GPU form of EmissionFunctionArray::sample_dN_pTdpTdphidy (ParticleSampler.cpp:638-1134, df_mode 1-4) and, as
+// compile-time variants of k_cells and k_sample, of sample_dN_pTdpTdphidy_famod (:1138-1627, df_mode 5: the cells'
+// (lambda, aT, aL) come from the engine's Newton prepass, Config::sol); the math and the
 // counter-based random streams are in sampler_math.h.  Every draw is a pure function of (seed, purpose, global cell,
 // event, candidate, draw counter), so the list below is the same for every launch geometry, event batch, cell window
 // and shard count, and its order -- events contiguous, (cell, candidate) inside an event -- is the reference's loop
@@ -64,6 +66,7 @@ struct Args {
   // binned distributions
   Bins bins;
   unsigned long long* hist;
+  const double* sol;    // famod: [6][n] rows of the Newton prepass (Config::sol)
 };
 
 __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
@@ -73,10 +76,12 @@ __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
 
 // species weights of cell c into w[npart] (lanes over species), then lane 0: the plain sum (returned to every lane
 // through w's owner) and, when cumulative, the running sum of max(w, 0) in place
+template <bool FAMOD>
 __device__ double species_list(const Args& A, const Cell& c, double* w, bool cumulative) {
   const int lane = threadIdx.x;
   for (int s = lane; s < A.npart; s += kWave) {
-    w[s] = A.run.fast ? species_weight_fast(A.run, c, A.dens[s], A.dens[A.npart + s])
+    if (FAMOD) w[s] = species_weight_famod(A.run, c, A.mass[s], A.degen[s], A.sign[s], A.baryon[s]);
+    else w[s] = A.run.fast ? species_weight_fast(A.run, c, A.dens[s], A.dens[A.npart + s])
                       : species_weight(A.run, c, A.mass[s], A.degen[s], A.sign[s], A.baryon[s]);
   }
   __syncthreads();
@@ -93,6 +98,8 @@ __device__ double species_list(const Args& A, const Cell& c, double* w, bool cum
   return sum;     // lane 0 only
 }
 
+// FAMOD: the df_mode 5 prologue from the surface and the cell's row of the Newton prepass; it has no df tables to fail
+template <bool FAMOD>
 __global__ __launch_bounds__(kWave) void k_cells(Args A) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   Cell& sc = *reinterpret_cast<Cell*>(smem);
@@ -103,7 +110,14 @@ __global__ __launch_bounds__(kWave) void k_cells(Args A) {
   if (lane == 0) {
     double s[NSURF];
     for (int f = 0; f < NSURF; f++) s[f] = A.surf[(long)f * A.n + cell];
-    *serr = cell_setup(A.run, A.tb, s, sc);
+    if (FAMOD) {
+      double sol[6];
+      for (int f = 0; f < 6; f++) sol[f] = A.sol[(long)f * A.n + cell];
+      cell_setup_famod(A.run, s, sol, sc);
+      *serr = 0;
+    } else {
+      *serr = cell_setup(A.run, A.tb, s, sc);
+    }
     if (*serr) { atomicMax(A.err, *serr); sc.live = 0.0; }
   }
   __syncthreads();
@@ -111,7 +125,7 @@ __global__ __launch_bounds__(kWave) void k_cells(Args A) {
     if (lane == 0) { A.cells[ci] = sc; A.dn[ci] = 0.0; }
     return;
   }
-  const double sum = species_list(A, sc, w, false);
+  const double sum = species_list<FAMOD>(A, sc, w, false);
   if (lane == 0) {
     cell_finish(A.run, sc, sum);
     if (sc.live != 0.0 && sc.breaks != 0.0) atomicAdd(&A.tally[0], 1ull);
@@ -137,8 +151,9 @@ __global__ __launch_bounds__(256) void k_count(Args A) {
   A.counts[i] = n;
 }
 
-// LIST: kept particles and flags go to their slots; BIN: kept particles are binned into A.hist
-template <bool LIST, bool BIN>
+// LIST: kept particles and flags go to their slots; BIN: kept particles are binned into A.hist; FAMOD: the df_mode 5
+// species weights and candidate
+template <bool LIST, bool BIN, bool FAMOD = false>
 __global__ __launch_bounds__(kWave) void k_sample(Args A) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   Cell& sc = *reinterpret_cast<Cell*>(smem);
@@ -152,7 +167,7 @@ __global__ __launch_bounds__(kWave) void k_sample(Args A) {
   if (!__syncthreads_or(any)) return;
   if (lane == 0) sc = A.cells[cell - A.lo];
   __syncthreads();
-  species_list(A, sc, cum, true);
+  species_list<FAMOD>(A, sc, cum, true);
   Tally t{0, 0, 0, 0};
   unsigned long long ncand = 0, nkept = 0;     // binned-only: there is no scan to count them
   for (long evb = 0; evb < A.nev; evb += kWave) {
@@ -174,8 +189,10 @@ __global__ __launch_bounds__(kWave) void k_sample(Args A) {
       const long evl = evb + lo, nc = j - pre[lo];
       Particle p;
       double drawn = 0.0;
-      const bool kept = candidate(A.run, sc, A.seed, A.cell_base + cell, A.e0 + evl, nc, cum, A.npart, A.mass, A.sign,
-                                  A.baryon, &p, t, nullptr, drawn);
+      const bool kept = FAMOD ? candidate_famod(A.run, sc, A.seed, A.cell_base + cell, A.e0 + evl, nc, cum, A.npart, A.mass,
+                                                A.sign, A.baryon, &p, t, drawn)
+                              : candidate(A.run, sc, A.seed, A.cell_base + cell, A.e0 + evl, nc, cum, A.npart, A.mass, A.sign,
+                                          A.baryon, &p, t, nullptr, drawn);
       if (LIST) {
         const long slot = A.slots[evl * ncb + ci] + nc;
         A.flags[slot] = kept ? 1 : 0;
@@ -330,10 +347,12 @@ int run(const Tables& t, const Config& c, std::vector<Particle>& parts, std::vec
   SCHK(hipMemset(B.err, 0, sizeof(int)));
   SCHK(hipMemset(B.tally, 0, 8 * sizeof(unsigned long long)));
   Args A{};
-  A.run = c.run; A.tb = c.tb; A.surf = c.surf; A.n = c.n; A.lo = c.lo; A.hi = c.hi; A.cell_base = c.cell_base;
+  A.run = c.run; A.tb = c.tb; A.surf = c.surf; A.sol = c.sol; A.n = c.n; A.lo = c.lo; A.hi = c.hi; A.cell_base = c.cell_base;
   A.seed = c.seed; A.mass = t.mass; A.sign = t.sign; A.degen = t.degen; A.baryon = t.baryon; A.dens = c.dens;
   A.npart = t.npart; A.cells = B.cells; A.dn = B.dn; A.err = B.err; A.tally = B.tally;
-  hipLaunchKernelGGL(k_cells, dim3((unsigned)nw), dim3(kWave), lds, 0, A);
+  const bool famod = c.sol != nullptr;
+  if (famod) hipLaunchKernelGGL(k_cells<true>, dim3((unsigned)nw), dim3(kWave), lds, 0, A);
+  else hipLaunchKernelGGL(k_cells<false>, dim3((unsigned)nw), dim3(kWave), lds, 0, A);
   SCHK(hipGetLastError());
   std::vector<double> dn((size_t)nw);
   SCHK(hipMemcpy(dn.data(), B.dn, nw * sizeof(double), hipMemcpyDeviceToHost));
@@ -358,7 +377,8 @@ int run(const Tables& t, const Config& c, std::vector<Particle>& parts, std::vec
       A.e0 = e0; A.nev = nev; A.c0 = c.lo + a; A.c1 = c.lo + b; A.counts = B.counts; A.slots = B.slots;
       hipLaunchKernelGGL(k_count, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, 0, A);
       SCHK(hipGetLastError());
-      hipLaunchKernelGGL((k_sample<false, true>), dim3((unsigned)ncb), dim3(kWave), lds, 0, A);
+      if (famod) hipLaunchKernelGGL((k_sample<false, true, true>), dim3((unsigned)ncb), dim3(kWave), lds, 0, A);
+      else hipLaunchKernelGGL((k_sample<false, true>), dim3((unsigned)ncb), dim3(kWave), lds, 0, A);
       SCHK(hipGetLastError());
       st.batches++;
       if (b == nw) { e0 += nev; a = 0; } else { a = b; }
@@ -408,7 +428,9 @@ int run(const Tables& t, const Config& c, std::vector<Particle>& parts, std::vec
         SCHK(B.cands(total + 1));
         A.cand = B.cand; A.flags = B.flags;
         SCHK(hipMemsetAsync(B.flags + total, 0, sizeof(int), 0));
-        if (c.bins) hipLaunchKernelGGL((k_sample<true, true>), dim3((unsigned)ncb), dim3(kWave), lds, 0, A);
+        if (famod && c.bins) hipLaunchKernelGGL((k_sample<true, true, true>), dim3((unsigned)ncb), dim3(kWave), lds, 0, A);
+        else if (famod) hipLaunchKernelGGL((k_sample<true, false, true>), dim3((unsigned)ncb), dim3(kWave), lds, 0, A);
+        else if (c.bins) hipLaunchKernelGGL((k_sample<true, true>), dim3((unsigned)ncb), dim3(kWave), lds, 0, A);
         else hipLaunchKernelGGL((k_sample<true, false>), dim3((unsigned)ncb), dim3(kWave), lds, 0, A);
         SCHK(hipGetLastError());
         SCHK(scan(B.flags, B.pos, total + 1, B.tmp, B.tmp_cap));

@@ -1,4 +1,4 @@
-// sampler_math.h -- host/device math of the operation = 2 particle sampler (df_mode 1-4), shared by the sampling
+// sampler_math.h -- host/device math of the operation = 2 particle sampler (df_mode 1-4; df_mode 5 at the end), shared by the sampling
 // kernels (sampler.hip) and the CPU emulator (tests/native/sampler_emulator.cpp).
 //
 // Reference: EmissionFunctionArray::sample_dN_pTdpTdphidy (ParticleSampler.cpp:638-1134) with sample_momentum
@@ -395,6 +395,40 @@ IS3D_HD double clamp_df(double df, Tally& t) {
   return fmax(-1.0, fmin(1.0, df));
 }
 
+// the kept LRF momentum p of species sp (mass^2 = m2) as the particle record: lab boost (Momentum.cpp:14-31), the
+// rapidity draw of a 2+1D surface (:1079-1098) and the cell's position.  The tail of candidate() below, word for word,
+// for candidate_famod: candidate() keeps its own copy, because calling this from it moved k_sample<binned only> from
+// 231 to 233 VGPRs, and the df_mode 1-4 kernels are to compile to what they were.
+IS3D_HD void lab_record(const Run& R, const Cell& c, const LrfP& p, double m2, int sp, uint64_t seed, long cell, long event,
+                        long n, Particle* out, double& drawn) {
+  const Milne& b = c.b;
+  const double ptau = p.E * c.ut + p.px * b.Xt + p.pz * b.Zt;
+  const double lpx = p.E * c.ux + p.px * b.Xx + p.py * b.Yx;
+  const double lpy = p.E * c.uy + p.px * b.Xy + p.py * b.Yy;
+  const double pn = p.E * c.un + p.px * b.Xn + p.pz * b.Zn;
+  double eta = c.eta, sinheta = c.sinheta, cosheta = c.cosheta, E, pz;
+  if (R.k.dim == 2) {              // :1079-1098
+    Stream sr = stream_open(seed, P_RAPIDITY, cell, event, n);
+    const double rapidity = R.y_max * (2.0 * stream_next(sr) - 1.0);
+    drawn = rapidity;
+    const double sinhy = sinh(rapidity), coshy = sqrt(1.0 + sinhy * sinhy);
+    const double tau_pn = c.tau * pn;
+    const double mT = sqrt(m2 + lpx * lpx + lpy * lpy);   // = sqrt(ptau^2 - (tau pn)^2) of :1088, without its cancellation
+    sinheta = (ptau * sinhy - tau_pn * coshy) / mT;
+    eta = asinh(sinheta);
+    cosheta = sqrt(1.0 + sinheta * sinheta);
+    pz = mT * sinhy;
+    E = mT * coshy;
+  } else {
+    pz = c.tau * pn * cosheta + ptau * sinheta;
+    E = sqrt(m2 + lpx * lpx + lpy * lpy + pz * pz);
+  }
+  out->species = sp; out->event = (int32_t)event; out->cell = cell;
+  out->tau = c.tau; out->x = c.x; out->y = c.y; out->eta = eta;
+  out->t = c.tau * cosheta; out->z = c.tau * sinheta;
+  out->E = E; out->px = lpx; out->py = lpy; out->pz = pz;
+}
+
 // Draws species, momentum and the keep decision of candidate n of (cell, event); true = kept, *out filled.
 // cum[npart]: the cell's running species weights; mass / sign / baryon: the chosen species in their original order.
 // drawn: the drawn rapidity of a kept 2+1D particle (the binned distributions take it as drawn; untouched in 3+1D).
@@ -481,6 +515,120 @@ IS3D_HD bool candidate(const Run& R, const Cell& c, uint64_t seed, long cell, lo
                        int* branch_out) {
   double drawn = 0.0;
   return candidate(R, c, seed, cell, event, n, cum, npart, mass, sign, baryon_, out, t, branch_out, drawn);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// df_mode 5 (PTMA): sample_dN_pTdpTdphidy_famod (ParticleSampler.cpp:1138-1627)
+// ---------------------------------------------------------------------------------------------------------
+// The method has no delta-f, no diffusion and no fast branch, so its Cell reuses fields it would leave empty:
+//   pi = the symmetric momentum transformation B (the identity on breakdown), T_mod = lambda, iso_scale = det A,
+//   shear_mod = det B = det C det A (as computed, breakdown or not), alphaB_mod = alphaB (upsilonB, :1328);
+// df, V*, diff_mod and ber stay zero.  The df_mode 1-4 record is unchanged.
+//
+// The prologue (:1181-1461) of one cell; s = the 25 surface fields, sol = the cell's row of the Newton prepass
+// (lambda, aT, aL, broken, beta_pi_perp, beta_W_perp; aniso_math.h aniso_cell with the sampler's rule), read only for
+// a cell with u.dsigma > 0.  pi and Pi enter pl / pt whatever the delta-f flags say, and muB is read under
+// include_baryon alone (:1215-1248).  Breakdown: pl / pt < 0 or a failed reconstruction (sol[3]) or det B <= deta_min;
+// lambda and det A stay what the cell ends with -- (T, 1, 1) for the first two causes, the solution for the third.
+IS3D_HD void cell_setup_famod(const Run& R, const double* s, const double* sol, Cell& c) {
+  const PrepConsts& k = R.k;
+  c = Cell{};
+  const double tau = s[S_TAU], tau2 = tau * tau;
+  const double dat = s[S_DAT], dax = s[S_DAX], day = s[S_DAY], dan = s[S_DAN];
+  const double ux = s[S_UX], uy = s[S_UY], un = s[S_UN];
+  const double ut = sqrt(1.0 + ux * ux + uy * uy + tau2 * un * un);
+  if (ut * dat + ux * dax + uy * day + un * dan <= 0.0) return;
+  const double ut2 = ut * ut, ux2 = ux * ux, uy2 = uy * uy;
+  const double uperp = sqrt(ux2 + uy2), utperp = sqrt(1.0 + ux2 + uy2);
+  const double T = s[S_T];
+  const double pixx = s[S_PIXX], pixy = s[S_PIXY], pixn = s[S_PIXN], piyy = s[S_PIYY], piyn = s[S_PIYN];
+  const double pinn = (pixx * (ux2 - ut2) + piyy * (uy2 - ut2) + 2.0 * (pixy * ux * uy + tau2 * un * (pixn * ux + piyn * uy))) / (tau2 * utperp * utperp);
+  const double pitn = (pixn * ux + piyn * uy + tau2 * pinn * un) / ut;
+  const double pity = (pixy * ux + piyy * uy + tau2 * piyn * un) / ut;
+  const double pitx = (pixx * ux + pixy * uy + tau2 * pixn * un) / ut;
+  const double pitt = (pitx * ux + pity * uy + tau2 * pitn * un) / ut;
+  const double muB = k.include_baryon ? s[S_MUB] : 0.0;
+  c.b = milne_basis(ut, ux, uy, un, uperp, utperp, tau);
+  const Milne& b = c.b;
+  c.dst = dat * ut + dax * ux + day * uy + dan * un;
+  c.dsx = -(dat * b.Xt + dax * b.Xx + day * b.Xy + dan * b.Xn);
+  c.dsy = -(dax * b.Yx + day * b.Yy);
+  c.dsz = -(dat * b.Zt + dan * b.Zn);
+  c.ds_max = fabs(c.dst) + sqrt(c.dsx * c.dsx + c.dsy * c.dsy + c.dsz * c.dsz);
+  const PiLRF pl_ = boost_pi(b, tau2, pitt, pitx, pity, pitn, pixx, pixy, pixn, piyy, piyn, pinn);
+  double piTxx = 0, piTxy = 0, piTyy = 0, WTzx = 0, WTzy = 0;
+  if (k.include_shear) {
+    piTxx = (pl_.xx - pl_.yy) / 2.; piTxy = pl_.xy; piTyy = -(piTxx);
+    WTzx = pl_.xz; WTzy = pl_.yz;
+  }
+  const double lambda = sol[0], aT = sol[1], aL = sol[2];
+  bool breaks = sol[3] != 0.0;
+  const double shear_coeff = 0.5 / sol[4], diff_coeff = 1. / sol[5];
+  const double detA = aT * aT * aL;
+  const double Cxx = 1. + shear_coeff * piTxx, Cxy = shear_coeff * piTxy, Cxz = diff_coeff * WTzx * aT / (aT + aL);
+  const double Cyx = Cxy, Cyy = 1. + shear_coeff * piTyy, Cyz = diff_coeff * WTzy * aT / (aT + aL);
+  const double Czx = diff_coeff * WTzx * aL / (aT + aL), Czy = diff_coeff * WTzy * aL / (aT + aL), Czz = 1.;
+  const double detC = Cxx * (Cyy * Czz - Cyz * Czy) - Cxy * (Cyx * Czz - Cyz * Czx) + Cxz * (Cyx * Czy - Cyy * Czx);
+  const double detB = detC * detA;
+  if (detB <= k.deta_min) breaks = true;
+  c.pi = PiLRF{1.0, 0.0, 0.0, 1.0, 0.0, 1.0};
+  if (!breaks) {
+    c.pi.xx = aT + aT * shear_coeff * piTxx; c.pi.xy = aT * shear_coeff * piTxy; c.pi.xz = diff_coeff * WTzx * aT * aL / (aT + aL);
+    c.pi.yy = aT + aT * shear_coeff * piTyy; c.pi.yz = diff_coeff * WTzy * aT * aL / (aT + aL); c.pi.zz = aL;
+  }
+  c.T = T; c.alphaB = muB / T; c.T_mod = lambda; c.alphaB_mod = c.alphaB; c.bulkPi = s[S_BULKPI];
+  c.iso_scale = detA; c.shear_mod = detB;
+  c.breaks = breaks ? 1.0 : 0.0;
+  c.tau = tau; c.x = s[S_X]; c.y = s[S_Y]; c.eta = s[S_ETA];
+  c.sinheta = sinh(c.eta);
+  c.cosheta = sqrt(1.0 + c.sinheta * c.sinheta);
+  c.ut = ut; c.ux = ux; c.uy = uy; c.un = un;
+  c.live = 1.0;
+}
+
+// species weight (:1467-1499): the anisotropic density n_a = g lambda^3 det A / (2 pi^2 hbarc^3) I_100 from the
+// alpha = 1 Gauss-Laguerre row.  The reference adds the chemical term to Ebar (exp(Ebar + chem), :1493, "should be
+// zero atm") where every other density subtracts it; that is reproduced.
+IS3D_HD double species_weight_famod(const Run& R, const Cell& c, double mass, double degeneracy, double sign, double baryon) {
+  const PrepConsts& k = R.k;
+  const double lambda = c.T_mod, mbar = mass / lambda, mbar2 = mbar * mbar, chem = baryon * c.alphaB_mod;
+  const double na_fact = lambda * lambda * lambda * c.iso_scale / k.two_pi2_hbarC3;
+  double I_100 = 0.0;
+  for (int i = 0; i < k.gla_pts; i++) {
+    const double pbar = k.gla_r1[i], Ebar = sqrt(pbar * pbar + mbar2);
+    I_100 += pbar * k.gla_w1[i] * exp(pbar) / (exp(Ebar + chem) + sign);
+  }
+  return degeneracy * na_fact * I_100;
+}
+
+// rescale_momentum_famod (:428-444): p = B p', E from the mass
+IS3D_HD LrfP rescale_momentum_famod(const Cell& c, const LrfP& q, double mass2) {
+  LrfP r;
+  r.px = c.pi.xx * q.px + c.pi.xy * q.py + c.pi.xz * q.pz;
+  r.py = c.pi.xy * q.px + c.pi.yy * q.py + c.pi.yz * q.pz;
+  r.pz = c.pi.xz * q.px + c.pi.yz * q.py + c.pi.zz * q.pz;
+  r.E = sqrt(mass2 + r.px * r.px + r.py * r.py + r.pz * r.pz);
+  r.feq = q.feq;
+  return r;
+}
+
+// one candidate (:1519-1618): the streams and purposes of candidate(); kept with the flux weight alone
+IS3D_HD bool candidate_famod(const Run& R, const Cell& c, uint64_t seed, long cell, long event, long n, const double* cum,
+                             int npart, const double* mass, const double* sign, const double* baryon_, Particle* out,
+                             Tally& t, double& drawn) {
+  Stream st = stream_open(seed, P_TYPE, cell, event, n);
+  const int sp = species_draw(cum, npart, stream_next(st));
+  const double m = mass[sp], m2 = m * m;
+  Stream sm = stream_open(seed, P_MOMENTUM, cell, event, n);
+  LrfP p;
+  int branch = 0;
+  if (!sample_momentum(sm, m, sign[sp], c.T_mod, baryon_[sp] * c.alphaB_mod, &p, &t.proposals, &branch)) { t.capped++; return false; }
+  t.acceptances++;
+  p = rescale_momentum_famod(c, p, m2);
+  const double w_flux = fmax(0.0, p.E * c.dst - p.px * c.dsx - p.py * c.dsy - p.pz * c.dsz) / (p.E * c.ds_max);
+  if (!(stream_next(sm) < w_flux)) return false;
+  lab_record(R, c, p, m2, sp, seed, cell, event, n, out, drawn);
+  return true;
 }
 
 }  // namespace sampler

@@ -347,6 +347,40 @@ class Engine:
             self._chk(self.lib.is3d_get_particles(self._e, 0, n, C.c_void_p(parts.ctypes.data)))
         return hist, stats, parts, offsets
 
+    # --- df_mode 5: sample_dN_pTdpTdphidy_famod (ParticleSampler.cpp:1138-1627) -----------------------------
+    def _sampled_list(self, n_events):
+        n = self.lib.is3d_sample_count(self._e)
+        parts = np.zeros(max(n, 0), dtype=_lib.PARTICLE_DTYPE)
+        offsets = np.zeros(int(n_events) + 1, dtype=np.int64)
+        self._chk(self.lib.is3d_sample_offsets(self._e, offsets.ctypes.data_as(C.POINTER(C.c_long))))
+        if n > 0:
+            self._chk(self.lib.is3d_get_particles(self._e, 0, n, C.c_void_p(parts.ctypes.data)))
+        return parts, offsets
+
+    def sample_famod(self, seed, n_events, y_cut=0.5):
+        """sample() for df_mode 5 (PTMA): (particles, offsets, stats) in sample()'s shapes.  The method takes no
+        plasma averages and has no fast branch; each call first reconstructs (lambda, aT, aL) along the reference's
+        chain (famod_chains as for the spectra, the sampler's rule); sample_famod_stats() has its counters."""
+        sp = _lib.SampleParams(int(seed), int(n_events), 0, float(y_cut))
+        self._chk(self.lib.is3d_sample_famod(self._e, C.byref(sp), 0))
+        parts, offsets = self._sampled_list(n_events)
+        return parts, offsets, self.sample_stats()
+
+    def sample_famod_binned(self, seed, n_events, y_cut=0.5, keep_list=False):
+        """sample_binned() for df_mode 5: (hist, stats), or (hist, stats, particles, offsets) with keep_list."""
+        sp = _lib.SampleParams(int(seed), int(n_events), 0, float(y_cut))
+        self._chk(self.lib.is3d_sample_famod(self._e, C.byref(sp), 2 if keep_list else 1))
+        hist, stats = self.sample_hist(), self.sample_stats()
+        if not keep_list:
+            return hist, stats
+        return (hist, stats) + self._sampled_list(n_events)
+
+    def sample_famod_stats(self):
+        """The last sample_famod's reconstruction counters: plpt_negative, reconstruction_fail, iterations."""
+        s = _lib.SampleFamodStats()
+        self._chk(self.lib.is3d_get_sample_famod_stats(self._e, C.byref(s)))
+        return {k: getattr(s, k) for k, _ in s._fields_}
+
     def sample_stats(self):
         s = _lib.SampleStats()
         self._chk(self.lib.is3d_get_sample_stats(self._e, C.byref(s)))

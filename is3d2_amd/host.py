@@ -139,7 +139,8 @@ def total_yield(workdir, device=0, num_devices=1):
 
 
 def sample(workdir, devices=(0,), write_files=True, write_csv=False):
-    """operation = 2 run directory (df_mode 1-4): the estimate, then the GPU sampler over Nevents events.  Writes
+    """operation = 2 run directory (df_mode 1-4; df_mode 5 through is3d_sample_famod): the estimate, then the GPU
+    sampler over Nevents events.  Writes
     results/particle_list_osc_<event>.dat (and particle_list_<event>.dat with write_csv).  Returns a dict: particles
     (structured array, _lib.PARTICLE_DTYPE), mcid (per particle), offsets (Nevents + 1), n_total, n_events, seed.
     The list is sized by a first call that writes nothing, so a clock seed (sampler_seed < 0) is refused here:
