@@ -19,6 +19,8 @@
  *   is3d_set_momentum_weights         pT/phi Table weight columns              (SpacetimeDistribution.cpp:57-79)
  *   is3d_set_spacetime_bins           tau/r/phip bin parameters                (EmissionFunction.cpp:232-247)
  *   is3d_calculate_dN_dX              calculate_spectra, operation = 0         (EmissionFunction.cpp:1165-1196)
+ *   is3d_calculate_dN_dX_famod        operation = 0 for df_mode 5: no reference routine; the per-cell decomposition of
+ *                                     calculate_dN_pTdpTdphidy_famod           (MomentumSpectra.cpp:1517-1621)
  *   is3d_get_cell_yields              dN_dy_cell of each freeze-out cell       (SpacetimeDistribution.cpp:374)
  *   is3d_evaluate_df_coefficients     Deltaf_Data::evaluate_df_coefficients    (DeltafData.cpp:501-519)
  *   is3d_surface_averages             ds_max-weighted averages (Plasma)        (readindata.cpp:316-366, iS3D.cpp:184-219)
@@ -245,7 +247,21 @@ long is3d_output_size(const is3d_engine *e);
 int is3d_set_momentum_weights(is3d_engine *e, const double *pT_weight, const double *phi_weight);
 int is3d_set_spacetime_bins(is3d_engine *e, const is3d_spacetime_bins *bins);
 int is3d_calculate_dN_dX(is3d_engine *e, double *dN_taudtaudy, double *dN_2pirdrdy, double *dN_dphidy);
-/* dN_dy_cell[species][cell] of the last is3d_calculate_dN_dX call (SpacetimeDistribution.cpp:374). */
+/* operation = 0 for df_mode 5 (PTMA).  The reference has no routine (it prints "no spacetime distribution routine for
+ * famod yet" and exits, EmissionFunction.cpp:1184-1189; is3d_calculate_dN_dX returns that sentence as
+ * IS3D_ERR_UNSUPPORTED), so this entry defines one: dN_dy_cell[s][c] is cell c's term of
+ * calculate_dN_pTdpTdphidy_famod (MomentumSpectra.cpp:1517-1621) folded with the pT / phi weights and summed over the
+ * y table (3+1D) or taken at y = 0 over the eta nodes with their weights (2+1D), so that
+ *   sum_c dN_dy_cell[s][c] = sum_ipT,iphi,iy w_pT w_phi dN_pTdpTdphidy[s][ipT][iphi][iy]
+ * holds to rounding against is3d_calculate_spectra; the (lambda, aT, aL) of a cell are the spectra's (their chain rule,
+ * famod_chains as for the spectra).  Bins, thread slices, the per-species reset and the normalisation are
+ * is3d_calculate_dN_dX's.  is3d_get_cell_yields works after it; is3d_get_stats carries the breakdown cells and the
+ * Newton iterations.  Every call solves the chains again.  Honours is3d_set_cell_window as the spectra do (the chains
+ * walk every cell, the arrays and is3d_get_cell_yields' [species][hi - lo] cover the window); a chain range
+ * (is3d_set_chain_range) is refused.  df_mode 1-4: IS3D_ERR_UNSUPPORTED (is3d_calculate_dN_dX). */
+int is3d_calculate_dN_dX_famod(is3d_engine *e, double *dN_taudtaudy, double *dN_2pirdrdy, double *dN_dphidy);
+/* dN_dy_cell[species][cell] of the last is3d_calculate_dN_dX / is3d_calculate_dN_dX_famod call
+ * (SpacetimeDistribution.cpp:374). */
 int is3d_get_cell_yields(const is3d_engine *e, double *dN_dy_cell);
 
 /* Test hooks mirroring reference services. out[15] = c0 c1 c2 c3 c4 shear14 F G

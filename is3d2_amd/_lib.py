@@ -26,7 +26,8 @@ EXPORTS = ["is3d_abi_version", "is3d_build_id", "is3d_create", "is3d_create_devi
            "is3d_set_vorticity", "is3d_polarization_size", "is3d_calculate_polarization", "is3d_launch_polarization",
            "is3d_sample", "is3d_sample_count", "is3d_sample_offsets", "is3d_get_particles", "is3d_get_sample_stats",
            "is3d_sample_uniforms", "is3d_set_sample_bins", "is3d_sample_binned", "is3d_sample_hist_size",
-           "is3d_get_sample_hist", "is3d_sample_famod", "is3d_get_sample_famod_stats"]
+           "is3d_get_sample_hist", "is3d_sample_famod", "is3d_get_sample_famod_stats",
+           "is3d_calculate_dN_dX_famod"]
 
 VORTICITY_FIELDS = ["wtx", "wty", "wtn", "wxy", "wxn", "wyn"]
 
@@ -144,6 +145,7 @@ def load():
     lib.is3d_set_momentum_weights.argtypes = [C.c_void_p, pd, pd]
     lib.is3d_set_spacetime_bins.argtypes = [C.c_void_p, P(SpacetimeBins)]
     lib.is3d_calculate_dN_dX.argtypes = [C.c_void_p, pd, pd, pd]
+    lib.is3d_calculate_dN_dX_famod.argtypes = [C.c_void_p, pd, pd, pd]
     lib.is3d_get_cell_yields.argtypes = [C.c_void_p, pd]
     lib.is3d_total_yield.argtypes = [C.c_void_p, pd, d, pd, pd]
     lib.is3d_set_chain_range.argtypes = [C.c_void_p, C.c_long, C.c_long]

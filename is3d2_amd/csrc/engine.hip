@@ -1005,8 +1005,9 @@ static int plasma_densities(is3d_engine* e, const double* plasma, double* dens) 
 // prepass_begin is launch_begin without an output buffer: it starts the launch context, enqueues the records and, for
 // PTMA, the Newton inputs and the (lambda, aT, aL) solution d_sol [6][n] -- cold (k_aniso) or the start of the chains
 // that chain_pass x npass + chain_end complete -- with the counters in d_cnt.  srule: the chain rule (aniso_math.h
-// aniso_cell), 0 for the spectra, 1 for the particle sampler (is3d_sample_famod).  L.empty: no cell in the window.
-static int prepass_begin(is3d_engine* e, void* stream, long q0, long q1, int has_pred, int srule) {
+// aniso_cell), 0 for the spectra, 1 for the particle sampler (is3d_sample_famod).  op: the prep constants' operation
+// (1; 0 for is3d_calculate_dN_dX_famod).  L.empty: no cell in the window.
+static int prepass_begin(is3d_engine* e, void* stream, long q0, long q1, int has_pred, int srule, int op = 1) {
   HIPCHK(e, hipSetDevice(e->device));
   LaunchCtx& L = e->lc;
   L = LaunchCtx{};
@@ -1034,6 +1035,7 @@ static int prepass_begin(is3d_engine* e, void* stream, long q0, long q1, int has
   if (!e->d_aux.reserve(9L * n)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(aux) failed");
   if (mode == PTMA && !e->d_sol.reserve(6L * n)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(sol) failed");
   L.pa = prep_args(e, e->d_rec.get(), e->d_aux.get(), p0, p1, e->d_err.get(), e->d_cnt.get());
+  L.pa.k.operation = op;
   rc = enqueue_prep(e, L.pa, st);
   if (rc) return rc;
   if (mode == PTMA) {
@@ -1571,19 +1573,14 @@ extern "C" int is3d_calculate_spectra(is3d_engine* e, double* dN_out) {
 // operation = 0 (SpacetimeDistribution.cpp:31-1250): device prepass + per-(species, cell) yields + binning
 // into thread slices; the host then applies the reference's per-species reset (byte-count memset,
 // :165-167 / :628-630) and writes the bin-normalised distributions (:407-440).
-extern "C" int is3d_calculate_dN_dX(is3d_engine* e, double* dN_taudtaudy, double* dN_2pirdrdy, double* dN_dphidy) {
-  if (e && e->grp) return is3d::group_calculate_dN_dX(e->grp, dN_taudtaudy, dN_2pirdrdy, dN_dphidy);
-  if (!e) return IS3D_ERR_ARG;
-  if (!dN_taudtaudy || !dN_2pirdrdy || !dN_dphidy) return e->fail(IS3D_ERR_ARG, "null output");
-  if (!e->have_params) return e->fail(IS3D_ERR_STATE, "is3d_set_params not called");
-  if (e->p.df_mode == PTMA) return e->fail(IS3D_ERR_UNSUPPORTED, "calculate_spectra error: no spacetime distribution routine for famod yet");
-  if (!e->have_weights) return e->fail(IS3D_ERR_STATE, "is3d_set_momentum_weights not called");
-  if (!e->have_bins) return e->fail(IS3D_ERR_STATE, "is3d_set_spacetime_bins not called");
-  int rc = finalize_tables(e);
-  if (rc) return rc;
-  HIPCHK(e, hipSetDevice(e->device));
+//
+// dndx_finish is what follows the prepass, shared by is3d_calculate_dN_dX and is3d_calculate_dN_dX_famod: the k_dndx
+// launches over cells [wlo, wlo + n) of the held surface (their records in d_rec; the yields go to d_ycell [class][n]),
+// the bin keys / CSR / k_stbin and the host epilogue.  The caller has recorded ev[0] and ev[1] on the null stream.
+static int dndx_finish(is3d_engine* e, long wlo, long n, const char* df_msg, double* dN_taudtaudy, double* dN_2pirdrdy,
+                       double* dN_dphidy) {
   hipStream_t st = nullptr;
-  const long n = e->ncell;
+  const long nsurf = e->ncell;
   const int mode = e->p.df_mode, dim = e->p.dimension;
   const int np = (int)e->mass.size(), npT = (int)e->pT.size(), nphi = (int)e->phi.size();
   const int nk = (dim == 3) ? (int)e->y.size() : 1, nl = (dim == 3) ? 1 : (int)e->eta.size();
@@ -1593,18 +1590,6 @@ extern "C" int is3d_calculate_dN_dX(is3d_engine* e, double* dN_taudtaudy, double
   const long nb[3] = {B.tau_bins, B.r_bins, B.phip_bins};
   const long nent = C * (nb[0] + nb[1] + nb[2]);
   std::vector<double> part((size_t)np * nent, 0.0);
-  rc = begin_stats(e, n, st);
-  if (rc) return rc;
-  if (n > 0) {
-    if (!e->d_rec.reserve((long)NREC * n)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(records) failed");
-    if (!e->d_aux.reserve(9L * n)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(aux) failed");
-    PrepArgs pa = prep_args(e, e->d_rec.get(), e->d_aux.get(), 0, n, e->d_err.get(), e->d_cnt.get());
-    pa.k.operation = 0;
-    rc = enqueue_prep(e, pa, st);
-    if (!rc && mode == PTM) rc = enqueue_renorm(e, pa.k, 0, n, n, st);
-    if (rc) return rc;
-  }
-  HIPCHK(e, hipEventRecord(e->ev[1], st));
   if (n > 0) {
     // --- per-(species, cell) yields
     const int KJ = spectra_kj(nphi);
@@ -1622,7 +1607,7 @@ extern "C" int is3d_calculate_dN_dX(is3d_engine* e, double* dN_taudtaudy, double
     da.cells_per_wg = cpw;
     da.nchunk = (n + cpw - 1) / cpw;
     if (!e->d_ycell.reserve((long)nc * n)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(cell yields) failed");
-    da.rec = e->d_rec.get(); da.n = n; da.renorm = e->d_renorm.get(); da.rcls = e->d_crcls; da.nrcls = e->nrcls; da.ycell = e->d_ycell.get();
+    da.rec = e->d_rec.get() + wlo * (long)NREC; da.n = n; da.renorm = e->d_renorm.get(); da.rcls = e->d_crcls; da.nrcls = e->nrcls; da.ycell = e->d_ycell.get();
     da.smass = e->d_cmass; da.ssign = e->d_csign; da.sbaryon = e->d_cbaryon;
     da.pT = e->d_pT; da.pTw = e->d_pTw; da.cphi = e->d_cphi; da.sphi = e->d_sphi; da.phiw = e->d_phiw;
     da.yv = e->d_y; da.etav = e->d_eta; da.etaw = e->d_etaw;
@@ -1649,7 +1634,8 @@ extern "C" int is3d_calculate_dN_dX(is3d_engine* e, double* dN_taudtaudy, double
       case GRAD: launch_dndx<GRAD>(dim3((unsigned)nwg), shmem, st, da, kflags, KJ); break;
       case CE: launch_dndx<CE>(dim3((unsigned)nwg), shmem, st, da, kflags, KJ); break;
       case PTM: launch_dndx<PTM>(dim3((unsigned)nwg), shmem, st, da, kflags, KJ); break;
-      default: launch_dndx<PTB>(dim3((unsigned)nwg), shmem, st, da, kflags, KJ); break;
+      case PTB: launch_dndx<PTB>(dim3((unsigned)nwg), shmem, st, da, kflags, KJ); break;
+      default: launch_dndx<PTMA>(dim3((unsigned)nwg), shmem, st, da, kflags, KJ); break;
     }
     HIPCHK(e, hipGetLastError());
     if (mode >= PTM) {
@@ -1657,13 +1643,14 @@ extern "C" int is3d_calculate_dN_dX(is3d_engine* e, double* dN_taudtaudy, double
       // launch (kernels.h k_dndx F_FB), added to ycell; the list's length stays on the device, so the grid is sized
       // for the whole surface and the workgroups split whatever the list holds
       if (!e->d_fb.reserve(n + 1 + kFbBlocks)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(fallback list) failed");
-      enqueue_fbscan((const double*)e->d_rec.get(), n, e->d_fb.get(), st);
+      enqueue_fbscan(da.rec, n, e->d_fb.get(), st);
       DndxArgs fa = da;
       fa.fbcells = e->d_fb.get() + 1; fa.fbcount = e->d_fb.get();
       fa.nchunk = std::max(1L, std::min(da.nchunk, (4096L + da.nbx - 1) / da.nbx));
       const long nfw = (long)da.nbx * fa.nchunk;
       if (mode == PTM) launch_dndx<PTM>(dim3((unsigned)nfw), shmem_fb, st, fa, kflags | F_FB, KJ);
-      else launch_dndx<PTB>(dim3((unsigned)nfw), shmem_fb, st, fa, kflags | F_FB, KJ);
+      else if (mode == PTB) launch_dndx<PTB>(dim3((unsigned)nfw), shmem_fb, st, fa, kflags | F_FB, KJ);
+      else launch_dndx<PTMA>(dim3((unsigned)nfw), shmem_fb, st, fa, kflags | F_FB, KJ);
       HIPCHK(e, hipGetLastError());
     }
     e->ycell_n = n;
@@ -1675,7 +1662,7 @@ extern "C" int is3d_calculate_dN_dX(is3d_engine* e, double* dN_taudtaudy, double
     // --- bin keys on the device, CSR (thread slice, bin) -> cells on the host, sums on the device
     if (!e->d_keys.reserve(3 * n)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(keys) failed");
     KeyArgs ka{};
-    ka.tau = e->d_surf; ka.x = e->d_surf + n; ka.y = e->d_surf + 2 * n; ka.n = n;
+    ka.tau = e->d_surf + wlo; ka.x = e->d_surf + nsurf + wlo; ka.y = e->d_surf + 2 * nsurf + wlo; ka.n = n;
     ka.tau_min = B.tau_min; ka.tau_width = (B.tau_max - B.tau_min) / (double)B.tau_bins;
     ka.r_min = B.r_min; ka.r_width = (B.r_max - B.r_min) / (double)B.r_bins;
     ka.phip_width = 2.0 * M_PI / (double)B.phip_bins;
@@ -1689,7 +1676,7 @@ extern "C" int is3d_calculate_dN_dX(is3d_engine* e, double* dN_taudtaudy, double
     for (int d = 0; d < 3; d++)
       for (long c = 0; c < n; c++) {
         const int kb = keys[(size_t)d * n + c];
-        if (kb >= 0) offs[off_d[d] + (c % C) * nb[d] + kb + 1]++;
+        if (kb >= 0) offs[off_d[d] + ((wlo + c) % C) * nb[d] + kb + 1]++;
       }
     for (long i = 0; i < nent; i++) offs[i + 1] += offs[i];
     std::vector<int> perm((size_t)std::max(offs[nent], 1L));
@@ -1697,7 +1684,7 @@ extern "C" int is3d_calculate_dN_dX(is3d_engine* e, double* dN_taudtaudy, double
     for (int d = 0; d < 3; d++)
       for (long c = 0; c < n; c++) {
         const int kb = keys[(size_t)d * n + c];
-        if (kb >= 0) perm[fill[off_d[d] + (c % C) * nb[d] + kb]++] = (int)c;
+        if (kb >= 0) perm[fill[off_d[d] + ((wlo + c) % C) * nb[d] + kb]++] = (int)c;
       }
     if (!e->d_perm.reserve((long)perm.size())) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(perm) failed");
     if (!e->d_offs.reserve(nent + 1)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(offsets) failed");
@@ -1720,7 +1707,7 @@ extern "C" int is3d_calculate_dN_dX(is3d_engine* e, double* dN_taudtaudy, double
   HIPCHK(e, hipMemcpy(&derr, e->d_err.get(), sizeof(int), hipMemcpyDeviceToHost));
   if (n > 0) HIPCHK(e, hipMemcpy(part.data(), e->d_part.get(), part.size() * sizeof(double), hipMemcpyDeviceToHost));
   read_timings(e);
-  if (derr) return df_error(e, derr, "Error: set df_mode = (1,2) in parameters.dat");
+  if (derr) return df_error(e, derr, df_msg);
   // --- the reference's per-species thread-slice reset and bin normalisation
   const double two_pi = 2.0 * M_PI;
   const double width[3] = {(B.tau_max - B.tau_min) / (double)B.tau_bins, (B.r_max - B.r_min) / (double)B.r_bins,
@@ -1747,6 +1734,80 @@ extern "C" int is3d_calculate_dN_dX(is3d_engine* e, double* dN_taudtaudy, double
     }
     off += C * bins;
   }
+  return IS3D_OK;
+}
+
+// the checks the two operation-0 entries share, up to the tables
+static int dndx_begin(is3d_engine* e, const double* dN_taudtaudy, const double* dN_2pirdrdy, const double* dN_dphidy) {
+  if (!dN_taudtaudy || !dN_2pirdrdy || !dN_dphidy) return e->fail(IS3D_ERR_ARG, "null output");
+  if (!e->have_params) return e->fail(IS3D_ERR_STATE, "is3d_set_params not called");
+  return IS3D_OK;
+}
+
+extern "C" int is3d_calculate_dN_dX(is3d_engine* e, double* dN_taudtaudy, double* dN_2pirdrdy, double* dN_dphidy) {
+  if (e && e->grp) return is3d::group_calculate_dN_dX(e->grp, dN_taudtaudy, dN_2pirdrdy, dN_dphidy);
+  if (!e) return IS3D_ERR_ARG;
+  int rc = dndx_begin(e, dN_taudtaudy, dN_2pirdrdy, dN_dphidy);
+  if (rc) return rc;
+  if (e->p.df_mode == PTMA)
+    return e->fail(IS3D_ERR_UNSUPPORTED, "calculate_spectra error: no spacetime distribution routine for famod yet "
+                                         "(the per-cell decomposition of the PTMA spectra: call is3d_calculate_dN_dX_famod)");
+  if (!e->have_weights) return e->fail(IS3D_ERR_STATE, "is3d_set_momentum_weights not called");
+  if (!e->have_bins) return e->fail(IS3D_ERR_STATE, "is3d_set_spacetime_bins not called");
+  rc = finalize_tables(e);
+  if (rc) return rc;
+  HIPCHK(e, hipSetDevice(e->device));
+  hipStream_t st = nullptr;
+  const long n = e->ncell;
+  rc = begin_stats(e, n, st);
+  if (rc) return rc;
+  if (n > 0) {
+    if (!e->d_rec.reserve((long)NREC * n)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(records) failed");
+    if (!e->d_aux.reserve(9L * n)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(aux) failed");
+    PrepArgs pa = prep_args(e, e->d_rec.get(), e->d_aux.get(), 0, n, e->d_err.get(), e->d_cnt.get());
+    pa.k.operation = 0;
+    rc = enqueue_prep(e, pa, st);
+    if (!rc && e->p.df_mode == PTM) rc = enqueue_renorm(e, pa.k, 0, n, n, st);
+    if (rc) return rc;
+  }
+  HIPCHK(e, hipEventRecord(e->ev[1], st));
+  return dndx_finish(e, 0, n, "Error: set df_mode = (1,2) in parameters.dat", dN_taudtaudy, dN_2pirdrdy, dN_dphidy);
+}
+
+// operation = 0 for df_mode 5.  The reference has no routine (EmissionFunction.cpp:1184-1189); this one is the per-cell
+// decomposition of calculate_dN_pTdpTdphidy_famod (MomentumSpectra.cpp:1517-1621) binned as the other modes' (DESIGN
+// 7.1): the spectra's PTMA prepass (chain rule 0) with operation 0 in the prep constants, then dndx_finish over the
+// cell window.  Nothing is kept between calls: every call solves the chains again.
+extern "C" int is3d_calculate_dN_dX_famod(is3d_engine* e, double* dN_taudtaudy, double* dN_2pirdrdy, double* dN_dphidy) {
+  if (e && e->grp) return is3d::group_calculate_dN_dX_famod(e->grp, dN_taudtaudy, dN_2pirdrdy, dN_dphidy);
+  if (!e) return IS3D_ERR_ARG;
+  int rc = dndx_begin(e, dN_taudtaudy, dN_2pirdrdy, dN_dphidy);
+  if (rc) return rc;
+  if (e->p.df_mode != PTMA)
+    return e->fail(IS3D_ERR_UNSUPPORTED, "is3d_calculate_dN_dX_famod: needs df_mode 5 (df_mode 1-4: is3d_calculate_dN_dX)");
+  if (e->chain_q1 >= 0)
+    return e->fail(IS3D_ERR_STATE, "is3d_calculate_dN_dX_famod: a chain range is set (is3d_set_chain_range); this entry solves the whole chain");
+  if (!e->have_weights) return e->fail(IS3D_ERR_STATE, "is3d_set_momentum_weights not called");
+  if (!e->have_bins) return e->fail(IS3D_ERR_STATE, "is3d_set_spacetime_bins not called");
+  rc = finalize_tables(e);
+  if (rc) return rc;
+  rc = prepass_begin(e, nullptr, 0, -1, 0, 0, 0);
+  for (int pass = 0; !rc && e->lc.chained && pass < e->lc.ca.npass; pass++) rc = chain_pass(e, pass);
+  if (!rc) rc = chain_end(e);
+  if (rc) return rc;
+  const LaunchCtx& L = e->lc;
+  if (!L.empty) {
+    hipLaunchKernelGGL(k_famod_b, dim3((unsigned)std::max(1L, (L.p1 - L.p0 + 255) / 256)), dim3(256), 0, L.st, L.pa,
+                       (const double*)e->d_sol.get());
+    HIPCHK(e, hipGetLastError());
+  }
+  HIPCHK(e, hipEventRecord(e->ev[1], L.st));
+  rc = dndx_finish(e, L.wlo, L.nw, "Error: choose df_mode = (1,2,3,4,5)", dN_taudtaudy, dN_2pirdrdy, dN_dphidy);
+  if (rc) return rc;
+  // the prepass counters, as is3d_finish reads them (dndx_finish has waited for the stream)
+  unsigned long long cnt[4] = {0, 0, 0, 0};
+  HIPCHK(e, hipMemcpy(cnt, e->d_cnt.get(), sizeof(cnt), hipMemcpyDeviceToHost));
+  e->st.breakdown = (long)cnt[0]; e->st.pl_negative = (long)cnt[1]; e->st.recon_fail = (long)cnt[2]; e->st.iterations = (long)cnt[3];
   return IS3D_OK;
 }
 

@@ -42,6 +42,8 @@ int group_launch(Group* g, double* dev_out, void* stream);
 int group_finish(Group* g);
 int group_calculate_spectra(Group* g, double* dN_out);
 int group_calculate_dN_dX(Group* g, double* tau, double* r, double* phi);
+// is3d_calculate_dN_dX_famod (df_mode 5): each shard solves the chain (or its window cold) and integrates its window
+int group_calculate_dN_dX_famod(Group* g, double* tau, double* r, double* phi);
 int group_get_cell_yields(const Group* g, double* dN_dy_cell);
 int group_get_stats(const Group* g, is3d_stats* out);
 long group_output_size(const Group* g);

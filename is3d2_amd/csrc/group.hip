@@ -564,20 +564,24 @@ int group_calculate_spectra(Group* g, double* dN_out) { return calculate(g, fals
 
 int group_calculate_polarization(Group* g, double T_avg, double* S_out) { return calculate(g, true, T_avg, S_out); }
 
-int group_calculate_dN_dX(Group* g, double* tau, double* r, double* phi) {
+// famod (is3d_calculate_dN_dX_famod, df_mode 5): with famod_chains > 0 every shard holds the whole surface, solves the
+// whole chain itself and integrates its window; with famod_chains = 0 the shards hold their windows and solve them cold
+static int dndx_shards(Group* g, double* tau, double* r, double* phi, bool famod) {
   if (!tau || !r || !phi) return g->fail(IS3D_ERR_ARG, "null output");
   if (!g->have_bins || g->np <= 0) return g->fail(IS3D_ERR_STATE, "species / spacetime bins not set");
   const int K = (int)g->sh.size();
   if (K > 1 && g->bins.threads > 0)
     return g->fail(IS3D_ERR_UNSUPPORTED, "spacetime threads > 0 (the reference's thread-slice carry) runs on one device");
   if (stale_split(g)) return g->fail(IS3D_ERR_STATE, kStaleSplit);
-  if (g->full && K > 1)
-    return g->fail(IS3D_ERR_UNSUPPORTED, "calculate_spectra error: no spacetime distribution routine for famod yet");
+  if (!famod && g->full && K > 1)
+    return g->fail(IS3D_ERR_UNSUPPORTED, "calculate_spectra error: no spacetime distribution routine for famod yet "
+                                         "(the per-cell decomposition of the PTMA spectra: call is3d_calculate_dN_dX_famod)");
   const long nt = (long)g->np * g->bins.tau_bins, nr = (long)g->np * g->bins.r_bins, nph = (long)g->np * g->bins.phip_bins;
   std::vector<std::vector<double>> part(K, std::vector<double>((size_t)(nt + nr + nph), 0.0));
   const int rc = each_parallel(g, [&](int k) -> int {
     double* b = part[k].data();
-    return is3d_calculate_dN_dX(g->sh[k], b, b + nt, b + nt + nr);
+    return famod ? is3d_calculate_dN_dX_famod(g->sh[k], b, b + nt, b + nt + nr)
+                 : is3d_calculate_dN_dX(g->sh[k], b, b + nt, b + nt + nr);
   });
   if (rc) return rc;
   // the binned, width-normalised distributions are sums over cells: add the shards in order
@@ -594,10 +598,18 @@ int group_calculate_dN_dX(Group* g, double* tau, double* r, double* phi) {
     agg.ms_prepass = std::max(agg.ms_prepass, s.ms_prepass);
     agg.ms_spectra = std::max(agg.ms_spectra, s.ms_spectra);
     agg.ms_total = std::max(agg.ms_total, s.ms_total);
+    // the whole chain on every shard: its counters once (shard 0's); windows solved cold: their sum
+    if (famod && (k == 0 || !g->full)) {
+      agg.breakdown += s.breakdown; agg.pl_negative += s.pl_negative; agg.recon_fail += s.recon_fail;
+      agg.iterations += s.iterations;
+    }
   }
   g->stats = agg;
   return IS3D_OK;
 }
+
+int group_calculate_dN_dX(Group* g, double* tau, double* r, double* phi) { return dndx_shards(g, tau, r, phi, false); }
+int group_calculate_dN_dX_famod(Group* g, double* tau, double* r, double* phi) { return dndx_shards(g, tau, r, phi, true); }
 
 int group_get_cell_yields(const Group* g, double* out) {
   if (!out) return IS3D_ERR_ARG;

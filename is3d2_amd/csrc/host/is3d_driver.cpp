@@ -180,7 +180,9 @@ void EmissionFunctionArray::run_sharded(const RunOptions& opt, int operation) {
       dNtau_.assign((size_t)np * bins.tau_bins, 0.0);
       dNr_.assign((size_t)np * bins.r_bins, 0.0);
       dNphi_.assign((size_t)np * bins.phip_bins, 0.0);
-      set_or_throw(e, is3d_calculate_dN_dX(e, dNtau_.data(), dNr_.data(), dNphi_.data()));
+      // df_mode 5: the reference has no routine; the engine's is the per-cell decomposition of the PTMA spectra
+      set_or_throw(e, prm.df_mode == 5 ? is3d_calculate_dN_dX_famod(e, dNtau_.data(), dNr_.data(), dNphi_.data())
+                                       : is3d_calculate_dN_dX(e, dNtau_.data(), dNr_.data(), dNphi_.data()));
     }
     if (polzn_only) {   // EmissionFunction.cpp:1305-1310: T = QGP->temperature
       const is3d_vorticity w{surf_.w[0].data(), surf_.w[1].data(), surf_.w[2].data(), surf_.w[3].data(),

@@ -21,8 +21,9 @@ template void launch_phitab<CE>(hipStream_t, const PhiTabArgs&);
 #elif IS3D_TU == 3 || IS3D_TU == 4
 template void launch_spectra<IS3D_TU>(dim3, size_t, hipStream_t, const SpecArgs&, int, int);
 template void launch_dndx<IS3D_TU>(dim3, size_t, hipStream_t, const DndxArgs&, int, int);
-#elif IS3D_TU == 5      // operation 0 has no PTMA path (SpacetimeDistribution.cpp)
+#elif IS3D_TU == 5      // operation 0: the reference has no PTMA routine; is3d_calculate_dN_dX_famod defines one
 template void launch_spectra<PTMA>(dim3, size_t, hipStream_t, const SpecArgs&, int, int);
+template void launch_dndx<PTMA>(dim3, size_t, hipStream_t, const DndxArgs&, int, int);
 #else
 #error "unknown IS3D_TU"
 #endif

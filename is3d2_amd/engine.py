@@ -163,14 +163,17 @@ class Engine:
         s = _lib.Surface(*[(_dp(c) if c is not None else C.POINTER(C.c_double)()) for c in cols])
         self._chk(self.lib.is3d_set_surface(self._e, n, C.byref(s)))
         self.ncell = n
+        self._window = None
 
     def set_surface_device(self, ptr, n):
         self._chk(self.lib.is3d_set_surface_device(self._e, int(n), C.c_void_p(ptr)))
         self.ncell = n
+        self._window = None
 
     def set_cell_window(self, lo, hi):
         """Integrate only cells [lo, hi) of the surface (-1, -1: all); PTMA chains still walk every cell."""
         self._chk(self.lib.is3d_set_cell_window(self._e, int(lo), int(hi)))
+        self._window = None if lo < 0 or hi < 0 else (int(lo), int(hi))
 
     # --- compute -----------------------------------------------------------------------
     def cell_costs(self):
@@ -195,11 +198,27 @@ class Engine:
         t = np.zeros((self.npart, b["tau_bins"])); r = np.zeros((self.npart, b["r_bins"]))
         ph = np.zeros((self.npart, b["phip_bins"]))
         self._chk(self.lib.is3d_calculate_dN_dX(self._e, _dp(t), _dp(r), _dp(ph)))
+        self._yield_cells = self.ncell
+        return t, r, ph
+
+    def calculate_dN_dX_famod(self):
+        """operation = 0 for df_mode 5 (is3d_calculate_dN_dX_famod): the same three arrays from the per-cell
+        decomposition of the PTMA spectra (the reference has no routine); cell_yields() holds the decomposition and
+        stats() the breakdown cells and Newton iterations."""
+        b = getattr(self, "bins", None)
+        if b is None:       # the output shapes come from the bins: the library's own check, before the buffers exist
+            raise IS3DError(_lib.IS3D_ERR_STATE, "is3d_set_spacetime_bins not called")
+        t = np.zeros((self.npart, b["tau_bins"])); r = np.zeros((self.npart, b["r_bins"]))
+        ph = np.zeros((self.npart, b["phip_bins"]))
+        self._chk(self.lib.is3d_calculate_dN_dX_famod(self._e, _dp(t), _dp(r), _dp(ph)))
+        w = getattr(self, "_window", None)       # a cell window (set_cell_window) is honoured: its cells only
+        self._yield_cells = self.ncell if w is None else w[1] - w[0]
         return t, r, ph
 
     def cell_yields(self):
-        """dN_dy_cell [species][cell] of the last calculate_dN_dX."""
-        out = np.zeros((self.npart, self.ncell))
+        """dN_dy_cell [species][cell] of the last calculate_dN_dX / calculate_dN_dX_famod (the latter under a cell
+        window: the window's cells)."""
+        out = np.zeros((self.npart, getattr(self, "_yield_cells", self.ncell)))
         self._chk(self.lib.is3d_get_cell_yields(self._e, _dp(out)))
         return out
 

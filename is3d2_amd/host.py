@@ -89,7 +89,9 @@ class HostError(RuntimeError):
 
 
 def run_particlization(workdir, out_size, device=0, num_devices=1):
-    """IS3D::run_particlization on devices [device, device + num_devices); returns the spectra."""
+    """IS3D::run_particlization on devices [device, device + num_devices); returns the spectra (operation = 1) or,
+    per species, [tau bins | r bins | phip bins] of the spacetime distributions (operation = 0: df_mode 1-4 through
+    is3d_calculate_dN_dX, df_mode 5 through is3d_calculate_dN_dX_famod)."""
     lib = load()
     out = np.zeros(out_size)
     err = C.create_string_buffer(512)
