@@ -33,6 +33,9 @@
  *   is3d_sample_binned                ... with test_sampler = 1: the binned     (BinSampledParticle.cpp:9-133,
  *                                     distributions of the kept particles        ParticleSampler.cpp:1112-1121)
  *   is3d_sample_famod                 sample_dN_pTdpTdphidy_famod, df_mode 5    (ParticleSampler.cpp:1138-1627)
+ *   is3d_set_decays / is3d_decay_feeddown   do_resonance_decays: no live reference routine (the key is read at
+ *                                     EmissionFunction.cpp:204-205; src/cpp/jail/emissionfunction_resonance_decays.cpp
+ *                                     is dead code): the decay feed-down of the spectra, defined in DESIGN.md 7.6
  *
  * Conventions: caller-owned host buffers in and out; the engine owns its HBM
  * buffers.  Errors are return codes (never exit()); is3d_last_error() gives the
@@ -435,6 +438,43 @@ typedef struct {
 } is3d_sample_famod_stats;
 int is3d_sample_famod(is3d_engine *e, const is3d_sample_params *p, int binned);
 int is3d_get_sample_famod_stats(const is3d_engine *e, is3d_sample_famod_stats *out);
+
+/* do_resonance_decays: feed-down of the continuous spectra from resonance decays.  The reference reads the key
+ * (EmissionFunction.cpp:204-205) but has no working routine (src/cpp/jail/emissionfunction_resonance_decays.cpp is in
+ * no makefile and starts with exit(-1)); the method here is defined in is3d2_amd/csrc/decay_math.h and DESIGN.md 7.6
+ * (Sollfrank, Koch and Heinz, Z. Phys. C 52 (1991) 593; 2- and 3-body channels, 12-point Gauss-Legendre rules).
+ *
+ * is3d_set_decays takes the channel table (after the species and the momentum grid; setting either again clears it):
+ * parent and daughter[] are indices into the chosen species (-1: a daughter that is not chosen receives nothing),
+ * masses and widths in GeV (the widths only open closed 2-body channels, the jail file's rule :239-256).  1-body rows
+ * (the stability marker) are ignored; rows with >= 4 bodies and closed channels are skipped and counted.
+ * is3d_decay_feeddown updates a host array in the spectra layout [species][pT][phi][y] in place (any such array, not
+ * only the last is3d_calculate_spectra result): every species then holds thermal + feed-down; a decaying parent keeps
+ * its own spectrum.  is3d_launch_feeddown is the resident form (dev_inout on the engine's GPU, is3d_finish
+ * synchronises).  Every output element sums its terms in a fixed order: the result is bit-identical across repeats
+ * and does not depend on the order the channels were listed in.  A device-list engine runs it on devices[0].
+ * Errors: IS3D_ERR_STATE when no decays / species / grid / params are set; IS3D_ERR_ARG for a pT <= 0 or a pT table that
+ * is not ascending, a phi table that is not ascending in [0, 2 pi), an index out of range, n_body < 1, a cycle. */
+typedef struct {
+  int parent;
+  int n_body;
+  int daughter[3];                /* chosen index, -1: not a chosen species */
+  double branching, mass_parent, width_parent, mass[3], width[3];
+} is3d_decay_channel;
+typedef struct {
+  long channels;                  /* rows given */
+  long kept;                      /* open 2- and 3-body channels */
+  long skipped_many_body;         /* rows with >= 4 bodies */
+  long skipped_closed;            /* closed 3-body channels, 2-body channels the mass adjustment cannot open */
+  long adjusted;                  /* 2-body channels the mass adjustment opened (among kept) */
+  long levels;                    /* topological levels = launches */
+  double branching_skipped;       /* summed branching of the skipped rows (many-body and closed) */
+  double ms_total;                /* device time of the last feed-down (HIP events) */
+} is3d_decay_stats;
+int is3d_set_decays(is3d_engine *e, int n, const is3d_decay_channel *channels);
+int is3d_decay_feeddown(is3d_engine *e, double *dN_inout);
+int is3d_launch_feeddown(is3d_engine *e, double *dev_inout, void *stream);
+int is3d_get_decay_stats(const is3d_engine *e, is3d_decay_stats *out);
 
 #ifdef __cplusplus
 }

@@ -17,7 +17,8 @@
  *   is3d_host_polarization         calculate_spin_polzn + write_polzn_vector_toFile     (Polarization.cpp:25-263,
  *                                                                                        EmissionFunction.cpp:561-609)
  *   is3d_host_read_pdg             PDG_Data::read_resonances                            (readindata.cpp:1217-1252)
- *   is3d_host_param                ParameterReader::getVal                              (ParameterReader.cpp:142-155)
+ *   is3d_host_read_decays          ... its decay rows, with the antibaryon rule         (readindata.cpp:997-1007, 1035-1056)
+ *   is3d_host_param                ParameterReader::getVal                             (ParameterReader.cpp:142-155)
  */
 #ifndef IS3D_HOST_H
 #define IS3D_HOST_H
@@ -26,7 +27,12 @@
 extern "C" {
 #endif
 
-/* Runs the whole workflow on HIP devices [device, device + num_devices) (cells sharded);
+/* do_resonance_decays = 1 in iS3D_parameters.dat with operation = 1: the decay rows of the PDG file are applied to the
+ * spectra (is3d_set_decays + is3d_decay_feeddown, include/is3d_amd.h) between the spectra and the writers, so
+ * results/continuous and dN_out hold thermal + feed-down, and the channel counts are printed.  With the key 0 or
+ * absent, or under another operation, nothing changes.  lightest_particle is read and not used, as in the reference.
+ *
+ * Runs the whole workflow on HIP devices [device, device + num_devices) (cells sharded);
  * dN_out (optional, capacity doubles) receives dN/(pT dpT dphi dy)[species][pT][phi][y] (operation 1)
  * or, per species, [dN_taudtaudy (tau_bins) | dN_2pirdrdy (r_bins) | dN_dphidy (phip_bins)] (operation 0). */
 int is3d_host_run_particlization(const char *workdir, int device, int num_devices, double *dN_out,
@@ -88,6 +94,11 @@ int is3d_host_polarization(const char *workdir, const int *devices, int num_devi
 /* Returns the number of particles (or < 0); arrays optional (capacity entries). */
 int is3d_host_read_pdg(const char *workdir, int hrg_eos, int capacity, long *mcid, double *mass, int *gspin,
                        int *baryon, int *sign);
+/* The decay rows of a conventional PDG file (hrg_eos 1, 2) in particle order, antibaryon rows generated
+ * (readindata.cpp:997-1007, 1035-1056): returns their number (or < 0); arrays optional (capacity rows):
+ * parent mcid, n_body as written, branching, daughters[n][5]. */
+long is3d_host_read_decays(const char *workdir, int hrg_eos, long capacity, long *parent, int *n_body,
+                           double *branching, long *daughters);
 int is3d_host_param(const char *path, const char *key, double *value);
 
 #ifdef __cplusplus

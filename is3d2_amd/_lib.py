@@ -6,6 +6,8 @@ There is no fallback: if the HIP library is missing, importing the engine fails.
 import ctypes as C
 import os
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("IS3D_LIB") or os.path.join(_HERE, "libis3d_amd.so")   # IS3D_LIB: A/B builds only
 
@@ -27,7 +29,8 @@ EXPORTS = ["is3d_abi_version", "is3d_build_id", "is3d_create", "is3d_create_devi
            "is3d_sample", "is3d_sample_count", "is3d_sample_offsets", "is3d_get_particles", "is3d_get_sample_stats",
            "is3d_sample_uniforms", "is3d_set_sample_bins", "is3d_sample_binned", "is3d_sample_hist_size",
            "is3d_get_sample_hist", "is3d_sample_famod", "is3d_get_sample_famod_stats",
-           "is3d_calculate_dN_dX_famod"]
+           "is3d_calculate_dN_dX_famod",
+           "is3d_set_decays", "is3d_decay_feeddown", "is3d_launch_feeddown", "is3d_get_decay_stats"]
 
 VORTICITY_FIELDS = ["wtx", "wty", "wtn", "wxy", "wxn", "wyn"]
 
@@ -89,6 +92,23 @@ class SampleBins(C.Structure):
                 ("y_bins", C.c_int), ("phip_bins", C.c_int), ("eta_cut", C.c_double), ("eta_bins", C.c_int),
                 ("tau_min", C.c_double), ("tau_max", C.c_double), ("tau_bins", C.c_int),
                 ("r_min", C.c_double), ("r_max", C.c_double), ("r_bins", C.c_int)]
+
+
+class DecayChannel(C.Structure):
+    """is3d_decay_channel: one decay row over the chosen species (DECAY_DTYPE is its numpy form)."""
+    _fields_ = [("parent", C.c_int), ("n_body", C.c_int), ("daughter", C.c_int * 3), ("branching", C.c_double),
+                ("mass_parent", C.c_double), ("width_parent", C.c_double), ("mass", C.c_double * 3),
+                ("width", C.c_double * 3)]
+
+
+DECAY_DTYPE = np.dtype([("parent", "<i4"), ("n_body", "<i4"), ("daughter", "<i4", (3,)), ("branching", "<f8"),
+                        ("mass_parent", "<f8"), ("width_parent", "<f8"), ("mass", "<f8", (3,)), ("width", "<f8", (3,))],
+                       align=True)
+
+
+class DecayStats(C.Structure):
+    _fields_ = [(k, C.c_long) for k in ("channels", "kept", "skipped_many_body", "skipped_closed", "adjusted",
+                                        "levels")] + [("branching_skipped", C.c_double), ("ms_total", C.c_double)]
 
 
 # (name in Engine.sample_binned's dict, the bins field that sizes it)
@@ -177,6 +197,10 @@ def load():
     lib.is3d_sample_hist_size.restype = C.c_long
     lib.is3d_sample_hist_size.argtypes = [C.c_void_p, P(C.c_long), P(C.c_long)]
     lib.is3d_get_sample_hist.argtypes = [C.c_void_p, P(C.c_long), pd]
+    lib.is3d_set_decays.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    lib.is3d_decay_feeddown.argtypes = [C.c_void_p, pd]
+    lib.is3d_launch_feeddown.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.is3d_get_decay_stats.argtypes = [C.c_void_p, P(DecayStats)]
     _lib = lib
     return lib
 

@@ -65,6 +65,7 @@
 #include "group.h"
 #include "polzn.h"
 #include "sampler.h"
+#include "decay.h"
 #include "devbuf.h"
 
 using namespace is3d;
@@ -203,6 +204,17 @@ struct is3d_engine {
   bool binned = false;
   is3d_stats st{};
   bool launched = false;
+  // resonance-decay feed-down (decay.hip): the channel table as given, its plan (built by is3d_set_decays; a new
+  // species list or momentum grid clears it), the packed tables (rebuilt after a params change: ny) and the log slabs
+  std::vector<is3d_decay_channel> dk_ch;
+  bool have_decays = false, dk_dirty = true, dk_launched = false;
+  is3d::decay::Rule dk_rule{};
+  is3d::decay::Plan dk_plan;
+  is3d::decay::Packed dk_pack;
+  DevBuf<double> d_dk_d, d_dk_log, d_dk_io;
+  DevBuf<int> d_dk_i;
+  hipEvent_t dk_ev[2] = {nullptr, nullptr};
+  is3d_decay_stats dk_stats{};
 
   int fail(int code, const std::string& msg) { err = msg; return code; }
 };
@@ -247,6 +259,7 @@ extern "C" is3d_engine* is3d_create(int device) {
     return nullptr;
   }
   for (auto& v : e->ev) (void)hipEventCreate(&v);
+  for (auto& v : e->dk_ev) (void)hipEventCreate(&v);
   return e;
 }
 
@@ -268,6 +281,7 @@ extern "C" void is3d_destroy(is3d_engine* e) {
   is3d::polzn::tables_free(e->pz);
   is3d::sampler::tables_free(e->smp);
   for (auto& v : e->ev) if (v) (void)hipEventDestroy(v);
+  for (auto& v : e->dk_ev) if (v) (void)hipEventDestroy(v);
   delete e;
 }
 
@@ -339,6 +353,7 @@ extern "C" int is3d_set_params(is3d_engine* e, const is3d_params* p) {
   e->have_params = true;
   e->tables_dirty = true;
   e->pz_dirty = true;
+  e->dk_dirty = true;
   return IS3D_OK;
 }
 
@@ -357,6 +372,8 @@ extern "C" int is3d_set_species(is3d_engine* e, int n, const double* mass, const
   e->tables_dirty = true;
   e->pz_dirty = true;
   e->smp_dirty = true;
+  e->have_decays = false;     // the channels index the species
+  e->dk_ch.clear();
   return IS3D_OK;
 }
 
@@ -401,6 +418,8 @@ extern "C" int is3d_set_momentum_grid(is3d_engine* e, int npT, const double* pT,
   e->have_grid = true;
   e->tables_dirty = true;
   e->pz_dirty = true;
+  e->have_decays = false;     // is3d_set_decays checked the grid it saw
+  e->dk_ch.clear();
   return IS3D_OK;
 }
 
@@ -1542,8 +1561,15 @@ extern "C" int is3d_cell_costs(is3d_engine* e, double* cost) {
 extern "C" int is3d_finish(is3d_engine* e) {
   if (e && e->grp) return is3d::group_finish(e->grp);
   if (!e) return IS3D_ERR_ARG;
-  if (!e->launched) return e->fail(IS3D_ERR_STATE, "nothing launched");
+  if (!e->launched && !e->dk_launched) return e->fail(IS3D_ERR_STATE, "nothing launched");
   HIPCHK(e, hipSetDevice(e->device));
+  if (e->dk_launched) {       // is3d_launch_feeddown: no device error word, its own two events
+    e->dk_launched = false;
+    HIPCHK(e, hipEventSynchronize(e->dk_ev[1]));
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, e->dk_ev[0], e->dk_ev[1]) == hipSuccess) e->dk_stats.ms_total = ms;
+    if (!e->launched) return IS3D_OK;
+  }
   HIPCHK(e, hipEventSynchronize(e->ev[3]));
   e->launched = false;
   int derr = 0;
@@ -1906,6 +1932,88 @@ extern "C" int is3d_calculate_polarization(is3d_engine* e, double T_avg, double*
   rc = is3d_finish(e);
   if (rc) return rc;
   HIPCHK(e, hipMemcpy(S_out, e->d_out.get(), outsize * sizeof(double), hipMemcpyDeviceToHost));
+  return IS3D_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// resonance-decay feed-down of the continuous spectra (do_resonance_decays; method in decay_math.h, kernels in decay.hip)
+// ------------------------------------------------------------------------------------------
+extern "C" int is3d_set_decays(is3d_engine* e, int n, const is3d_decay_channel* ch) {
+  if (e && e->grp) return is3d::group_set_decays(e->grp, n, ch);
+  if (!e) return IS3D_ERR_ARG;
+  if (!e->have_species || !e->have_grid) return e->fail(IS3D_ERR_STATE, "is3d_set_decays: set the species and the momentum grid first");
+  if (n < 0 || (n > 0 && !ch)) return e->fail(IS3D_ERR_ARG, "is3d_set_decays: bad channel table");
+  e->have_decays = false;
+  e->dk_ch.clear();
+  std::string msg = is3d::decay::check_grid((int)e->pT.size(), e->pT.data(), (int)e->phi.size(), e->phi.data(), 0, nullptr);
+  if (!msg.empty()) return e->fail(IS3D_ERR_ARG, "is3d_set_decays: " + msg);
+  e->dk_rule = is3d::decay::make_rule();
+  msg = is3d::decay::build_plan(e->dk_plan, e->dk_rule, (int)e->mass.size(), e->mass.data(), n, ch);
+  if (!msg.empty()) return e->fail(IS3D_ERR_ARG, "is3d_set_decays: " + msg);
+  e->dk_ch.assign(ch, ch + n);
+  e->dk_stats = e->dk_plan.stats;
+  e->have_decays = true;
+  e->dk_dirty = true;
+  return IS3D_OK;
+}
+
+extern "C" int is3d_get_decay_stats(const is3d_engine* e, is3d_decay_stats* out) {
+  if (e && e->grp) return out ? is3d::group_get_decay_stats(e->grp, out) : IS3D_ERR_ARG;
+  if (!e || !out) return IS3D_ERR_ARG;
+  if (!e->have_decays) return IS3D_ERR_STATE;
+  *out = e->dk_stats;
+  return IS3D_OK;
+}
+
+extern "C" int is3d_launch_feeddown(is3d_engine* e, double* dev_inout, void* stream) {
+  if (e && e->grp) return is3d::group_launch_feeddown(e->grp, dev_inout, stream);
+  if (!e) return IS3D_ERR_ARG;
+  if (!e->have_params || !e->have_species || !e->have_grid)
+    return e->fail(IS3D_ERR_STATE, "feed-down: params, species and momentum grid must be set");
+  if (!e->have_decays) return e->fail(IS3D_ERR_STATE, "feed-down: no decay channels set (is3d_set_decays)");
+  if (!dev_inout) return e->fail(IS3D_ERR_ARG, "null spectra buffer");
+  HIPCHK(e, hipSetDevice(e->device));
+  const int ny = e->p.dimension == 3 ? (int)e->y.size() : 1;
+  if (e->dk_dirty) {
+    if (ny < 1) return e->fail(IS3D_ERR_ARG, "feed-down: empty y table");
+    const std::string msg = is3d::decay::check_grid((int)e->pT.size(), e->pT.data(), (int)e->phi.size(), e->phi.data(), ny, e->y.data());
+    if (!msg.empty()) return e->fail(IS3D_ERR_ARG, "feed-down: " + msg);
+    e->dk_pack = is3d::decay::pack(e->dk_plan, e->dk_rule, e->pT, e->phi, ny, e->y);
+    const is3d::decay::Packed& K = e->dk_pack;
+    if (K.nb < 1 || K.lds > 64 * 1024) return e->fail(IS3D_ERR_ARG, "feed-down: the phi table does not fit a workgroup's LDS");
+    if (!e->d_dk_d.reserve((long)K.d.size()) || !e->d_dk_i.reserve((long)K.i.size()))
+      return e->fail(IS3D_ERR_DEVICE, "hipMalloc(decay tables) failed");
+    HIPCHK(e, hipMemcpy(e->d_dk_d.get(), K.d.data(), K.d.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(e, hipMemcpy(e->d_dk_i.get(), K.i.data(), K.i.size() * sizeof(int), hipMemcpyHostToDevice));
+    e->dk_dirty = false;
+  }
+  const long per = (long)e->pT.size() * ny;
+  for (int l = 0; l < e->dk_plan.levels(); l++)
+    if ((long)(e->dk_plan.lvl_r0[l + 1] - e->dk_plan.lvl_r0[l]) * per > 0x7fffffffL)
+      return e->fail(IS3D_ERR_ARG, "feed-down: a level has more than 2^31 workgroups");
+  if (!e->d_dk_log.reserve(is3d_output_size(e))) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(decay logs) failed");
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(e, hipEventRecord(e->dk_ev[0], st));
+  HIPCHK(e, is3d::decay::enqueue(e->dk_plan, e->dk_pack, e->d_dk_d.get(), e->d_dk_i.get(), dev_inout, e->d_dk_log.get(), st));
+  HIPCHK(e, hipEventRecord(e->dk_ev[1], st));
+  e->dk_launched = true;
+  return IS3D_OK;
+}
+
+extern "C" int is3d_decay_feeddown(is3d_engine* e, double* dN) {
+  if (e && e->grp) return is3d::group_decay_feeddown(e->grp, dN);
+  if (!e || !dN) return e ? e->fail(IS3D_ERR_ARG, "null spectra array") : IS3D_ERR_ARG;
+  const long n = is3d_output_size(e);
+  if (n < 0) return e->fail(IS3D_ERR_STATE, "feed-down: params, species and momentum grid must be set");
+  if (!e->have_decays) return e->fail(IS3D_ERR_STATE, "feed-down: no decay channels set (is3d_set_decays)");
+  HIPCHK(e, hipSetDevice(e->device));
+  if (!e->d_dk_io.reserve(n)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(spectra) failed");
+  HIPCHK(e, hipMemcpy(e->d_dk_io.get(), dN, n * sizeof(double), hipMemcpyHostToDevice));
+  int rc = is3d_launch_feeddown(e, e->d_dk_io.get(), nullptr);
+  if (rc) return rc;
+  rc = is3d_finish(e);
+  if (rc) return rc;
+  HIPCHK(e, hipMemcpy(dN, e->d_dk_io.get(), n * sizeof(double), hipMemcpyDeviceToHost));
   return IS3D_OK;
 }
 

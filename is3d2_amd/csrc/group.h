@@ -70,6 +70,12 @@ long group_sample_count(const Group* g);
 int group_sample_offsets(const Group* g, long* offsets);
 int group_get_particles(const Group* g, long first, long count, is3d_particle* out);
 int group_get_sample_stats(const Group* g, is3d_sample_stats* out);
+// resonance-decay feed-down: runs on devices[0] (shard 0), on the summed spectra; group_finish after
+// group_launch_feeddown finishes that shard alone
+int group_set_decays(Group* g, int n, const is3d_decay_channel* ch);
+int group_launch_feeddown(Group* g, double* dev_inout, void* stream);
+int group_decay_feeddown(Group* g, double* dN_inout);
+int group_get_decay_stats(const Group* g, is3d_decay_stats* out);
 }  // namespace is3d
 
 // engine.hip internals the group uses on its shard engines (not part of the public ABI)

@@ -58,6 +58,7 @@ struct Group {
   hipStream_t cur0 = nullptr;         // shard 0's stream of the launch in flight
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool launched = false;
+  bool fd_launched = false;           // group_launch_feeddown: shard 0 alone has work in flight
   is3d_stats stats{};
   // particle sampler: the merged list of the last group_sample
   std::vector<is3d_particle> particles;
@@ -502,7 +503,29 @@ int group_set_vorticity(Group* g, long n, const is3d_vorticity* w) {
   });
 }
 
+int group_set_decays(Group* g, int n, const is3d_decay_channel* ch) {
+  const int rc = is3d_set_decays(g->sh[0], n, ch);
+  return rc ? g->shard_fail(0, rc) : IS3D_OK;
+}
+int group_launch_feeddown(Group* g, double* dev_inout, void* stream) {
+  const int rc = is3d_launch_feeddown(g->sh[0], dev_inout, stream);
+  if (rc) return g->shard_fail(0, rc);
+  g->fd_launched = true;
+  return IS3D_OK;
+}
+int group_decay_feeddown(Group* g, double* dN_inout) {
+  const int rc = is3d_decay_feeddown(g->sh[0], dN_inout);
+  return rc ? g->shard_fail(0, rc) : IS3D_OK;
+}
+int group_get_decay_stats(const Group* g, is3d_decay_stats* out) { return is3d_get_decay_stats(g->sh[0], out); }
+
 int group_finish(Group* g) {
+  if (g->fd_launched && !g->launched) {
+    g->fd_launched = false;
+    const int rc = is3d_finish(g->sh[0]);
+    return rc ? g->shard_fail(0, rc) : IS3D_OK;
+  }
+  g->fd_launched = false;     // with a spectra launch in flight shard 0's is3d_finish below covers both
   if (!g->launched) return g->fail(IS3D_ERR_STATE, "nothing launched");
   g->launched = false;
   const int K = (int)g->sh.size();

@@ -297,16 +297,35 @@ std::string read_pdg(const std::string& dir, int hrg_eos, std::vector<Particle>&
     const std::string path = join(dir, hrg_eos == 1 ? "PDG/pdg-urqmd_v3.3+.dat" : "PDG/pdg_smash.dat");
     std::ifstream f(path);
     if (!f) return "cannot read " + path;
+    std::vector<Particle> base;
     while (true) {
       Particle p{};
-      int strange, charm, bottom, giso, charge, ndec;
+      int charm, bottom, giso, ndec;
       if (!(f >> p.mcid)) break;
-      f >> p.name >> p.mass >> p.width >> p.gspin >> p.baryon >> strange >> charm >> bottom >> giso >> charge >> ndec;
-      for (int j = 0; j < ndec; j++) { std::string tok; for (int k = 0; k < 8; k++) f >> tok; }
+      f >> p.name >> p.mass >> p.width >> p.gspin >> p.baryon >> p.strange >> charm >> bottom >> giso >> p.charge >> ndec;
+      for (int j = 0; j < ndec; j++) {          // mcid n_body branching d1 .. d5 (readindata.cpp:997-1007)
+        DecayRow r{};
+        long parent;
+        f >> parent >> r.n_body >> r.branching;
+        for (int k = 0; k < 5; k++) f >> r.daughter[k];
+        p.decays.push_back(r);
+      }
+      base.push_back(p);
+    }
+    auto self_conjugate = [&](long mcid) {      // a neutral non-strange meson (readindata.cpp:1055)
+      for (const auto& q : base)
+        if (q.mcid == mcid) return q.baryon == 0 && q.charge == 0 && q.strange == 0;
+      return false;
+    };
+    for (const auto& p : base) {
       out.push_back(p);
-      if (p.baryon > 0) {                       // antibaryon entry (readindata.cpp:1023-1063)
+      if (p.baryon > 0) {                       // antibaryon entry (readindata.cpp:1013-1060)
         Particle a = p;
         a.mcid = -p.mcid; a.name = "Anti-baryon-" + p.name; a.baryon = -p.baryon;
+        a.strange = -p.strange; a.charge = -p.charge;
+        for (auto& r : a.decays)
+          for (long& d : r.daughter)
+            if (d != 0 && !self_conjugate(d)) d = -d;
         out.push_back(a);
       }
     }

@@ -61,7 +61,15 @@ std::string write_averages_file(const std::string& dir, const Averages& a);
 
 // PDG_Data::read_resonances (readindata.cpp:973-1252): hrg_eos 1 UrQMD, 2 SMASH
 // (conventional format, antibaryons inserted), 3 SMASH box (mcid-decoded).
-struct Particle { long mcid; std::string name; double mass, width; int gspin, baryon, sign; };
+// Conventional format: the decay rows are kept (n_body as written: the UrQMD table flags some rows with a negative
+// count), and an antibaryon's rows repeat the baryon's with every daughter negated except neutral non-strange mesons
+// (readindata.cpp:1035-1056; a daughter is looked up in the whole file).  The box format has no decay rows.
+struct DecayRow { int n_body; double branching; long daughter[5]; };
+struct Particle {
+  long mcid; std::string name; double mass, width; int gspin, baryon, sign;
+  int strange = 0, charge = 0;
+  std::vector<DecayRow> decays;
+};
 std::string read_pdg(const std::string& dir, int hrg_eos, std::vector<Particle>& out);
 void decode_mcid(long mcid, int& gspin, int& baryon, int& sign, bool& has_antiparticle);   // read_mcid
 

@@ -53,6 +53,37 @@ EmissionFunctionArray::EmissionFunctionArray(const ParameterReader& params, cons
   for (const auto& q : particles) {
     pdg_mass_.push_back(q.mass); pdg_sign_.push_back(q.sign); pdg_degen_.push_back(q.gspin); pdg_baryon_.push_back(q.baryon);
   }
+  // the decay rows of the chosen species as the engine's channel table: indices into the chosen list (first match,
+  // -1 for a daughter that is not chosen), masses and widths from the PDG list; |n_body| (the UrQMD table flags some
+  // rows with a negative count); lightest_particle is read and not used, as in the reference.  Only operation = 1
+  // uses the table: under any other operation the key changes nothing, so a row it could not resolve must not fail the run
+  if ((int)p_.get("do_resonance_decays", 0.0) == 1 && (int)p_.get("operation", 1.0) == 1) {
+    auto find = [&](long mc) {
+      for (size_t n = 0; n < particles.size(); n++) if (particles[n].mcid == mc) return (int)n;
+      return -1;
+    };
+    auto chosen_index = [&](long mc) {
+      for (size_t k = 0; k < mcid_.size(); k++) if (mcid_[k] == mc) return (int)k;
+      return -1;
+    };
+    for (size_t k = 0; k < idx.size(); k++) {
+      const Particle& par = particles[idx[k]];
+      if (chosen_index(par.mcid) != (int)k) continue;       // a repeated chosen entry: the first carries the channels
+      for (const DecayRow& r : par.decays) {
+        is3d_decay_channel c{};
+        c.parent = (int)k; c.n_body = std::abs(r.n_body); c.branching = r.branching;
+        c.mass_parent = par.mass; c.width_parent = par.width;
+        for (int d = 0; d < 3; d++) c.daughter[d] = -1;
+        for (int d = 0; d < std::min(c.n_body, 3); d++) {
+          const int at = find(r.daughter[d]);
+          check(at >= 0, "decay row of " + std::to_string(par.mcid) + ": daughter " + std::to_string(r.daughter[d]) + " is not in the PDG list");
+          c.daughter[d] = chosen_index(r.daughter[d]);
+          c.mass[d] = particles[at].mass; c.width[d] = particles[at].width;
+        }
+        decays_.push_back(c);
+      }
+    }
+  }
 }
 
 static void set_or_throw(is3d_engine* e, int rc) {
@@ -144,6 +175,18 @@ void EmissionFunctionArray::run_sharded(const RunOptions& opt, int operation) {
     if (operation == 1) {
       dN_.assign(is3d_output_size(e), 0.0);
       set_or_throw(e, is3d_calculate_spectra(e, dN_.data()));
+      if ((int)p_.get("do_resonance_decays", 0.0) == 1) {     // between the spectra and the writers
+        set_or_throw(e, is3d_set_decays(e, (int)decays_.size(), decays_.data()));
+        set_or_throw(e, is3d_decay_feeddown(e, dN_.data()));
+        set_or_throw(e, is3d_get_decay_stats(e, &decay_stats_));
+        if (!opt.quiet) {
+          const is3d_decay_stats& d = decay_stats_;
+          std::printf("\nResonance decays: %ld channels, %ld kept (%ld opened by the mass adjustment), %ld with 4 or more "
+                      "bodies and %ld closed skipped (summed branching %g), %ld levels, %g ms\n",
+                      d.channels, d.kept, d.adjusted, d.skipped_many_body, d.skipped_closed, d.branching_skipped, d.levels,
+                      d.ms_total);
+        }
+      }
     } else if (operation == 2) {
       const double plasma[5] = {plasma_.T, plasma_.E, plasma_.P, plasma_.muB, plasma_.nB};
       set_or_throw(e, is3d_total_yield(e, plasma, p_.get("y_cut", 0.5), &ntotal_, nullptr));
@@ -638,6 +681,25 @@ extern "C" int is3d_host_read_pdg(const char* workdir, int hrg_eos, int capacity
   if (mcid) {
     if (n > capacity) return -2;
     for (int i = 0; i < n; i++) { mcid[i] = p[i].mcid; mass[i] = p[i].mass; gspin[i] = p[i].gspin; baryon[i] = p[i].baryon; sign[i] = p[i].sign; }
+  }
+  return n;
+}
+
+extern "C" long is3d_host_read_decays(const char* workdir, int hrg_eos, long capacity, long* parent, int* n_body,
+                                      double* branching, long* daughters) {
+  std::vector<Particle> p;
+  if (!read_pdg(workdir ? workdir : ".", hrg_eos, p).empty()) return -1;
+  long n = 0;
+  for (const auto& q : p) n += (long)q.decays.size();
+  if (parent) {
+    if (n > capacity) return -2;
+    long i = 0;
+    for (const auto& q : p)
+      for (const auto& r : q.decays) {
+        parent[i] = q.mcid; n_body[i] = r.n_body; branching[i] = r.branching;
+        for (int k = 0; k < 5; k++) daughters[5 * i + k] = r.daughter[k];
+        i++;
+      }
   }
   return n;
 }

@@ -94,8 +94,15 @@ class EmissionFunctionArray {
   const std::vector<double>& polarization() const { return S_; }
   void write_polzn_files(const std::string& dir) const;
   double seconds() const { return seconds_; }
+  // do_resonance_decays = 1 with operation = 1: the decay rows of the PDG file over the chosen species
+  // (decay_channels()), applied to the spectra by is3d_decay_feeddown before the writers run; decay_stats() = the
+  // engine's bookkeeping (zero when the key is 0 or absent)
+  const std::vector<is3d_decay_channel>& decay_channels() const { return decays_; }
+  const is3d_decay_stats& decay_stats() const { return decay_stats_; }
 
  private:
+  std::vector<is3d_decay_channel> decays_;
+  is3d_decay_stats decay_stats_{};
   const ParameterReader& p_;
   const Table &pT_, &phi_, &y_, &eta_;
   const Surface& surf_;

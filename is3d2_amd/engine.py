@@ -57,6 +57,22 @@ def _arr(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
+def _decay_table(channels):
+    """(n, pointer, array) of a channel table given as a DECAY_DTYPE array or a list of dicts."""
+    if isinstance(channels, np.ndarray) and channels.dtype == _lib.DECAY_DTYPE:
+        a = np.ascontiguousarray(channels)
+    else:
+        a = np.zeros(len(channels), dtype=_lib.DECAY_DTYPE)
+        a["daughter"] = -1
+        for i, c in enumerate(channels):
+            for k, v in c.items():
+                if k in ("daughter", "mass", "width"):
+                    a[k][i, :len(v)] = v
+                else:
+                    a[k][i] = v
+    return len(a), C.c_void_p(a.ctypes.data), a
+
+
 class IS3DError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("is3d error %d: %s" % (code, msg))
@@ -250,6 +266,35 @@ class Engine:
         """Resident form: writes 5 x output_size doubles into the device buffer; finish() synchronises."""
         self._chk(self.lib.is3d_launch_polarization(self._e, float(T_avg), C.c_void_p(dev_out_ptr),
                                                     C.c_void_p(stream_ptr or 0)))
+
+    # --- do_resonance_decays: feed-down of the continuous spectra (csrc/decay_math.h, DESIGN.md 7.6) -------
+    def set_decays(self, channels):
+        """The decay channel table over the chosen species (after set_species and set_momentum_grid, which clear it):
+        a numpy array of _lib.DECAY_DTYPE (hrg.decay_channels builds it from PDG rows) or a list of dicts with its
+        field names."""
+        n, ptr, keep = _decay_table(channels)      # keep: the array behind ptr, alive over the call
+        self._chk(self.lib.is3d_set_decays(self._e, n, ptr))
+        del keep
+
+    def feeddown(self, dN):
+        """A new array: dN (spectra layout, any shape of output_size elements) with the decay feed-down added;
+        every species then holds thermal + feed-down, a decaying parent keeps its own spectrum."""
+        out = np.array(dN, dtype=np.float64, order="C", copy=True)
+        if out.size != self.output_size():
+            raise ValueError("feeddown: the array must hold output_size() = %d values" % self.output_size())
+        self._chk(self.lib.is3d_decay_feeddown(self._e, _dp(out)))
+        return out
+
+    def launch_feeddown(self, dev_inout_ptr, stream_ptr=None):
+        """Resident form: updates output_size doubles in device memory in place; finish() synchronises."""
+        self._chk(self.lib.is3d_launch_feeddown(self._e, C.c_void_p(dev_inout_ptr), C.c_void_p(stream_ptr or 0)))
+
+    def decay_stats(self):
+        """The channel bookkeeping of set_decays (channels, kept, skipped_many_body, skipped_closed, adjusted,
+        levels, branching_skipped) and the device time of the last feed-down (ms_total)."""
+        s = _lib.DecayStats()
+        self._chk(self.lib.is3d_get_decay_stats(self._e, C.byref(s)))
+        return {k: getattr(s, k) for k, _ in s._fields_}
 
     def launch(self, dev_out_ptr, stream_ptr=None):
         self._chk(self.lib.is3d_launch(self._e, C.c_void_p(dev_out_ptr), C.c_void_p(stream_ptr or 0)))

@@ -22,6 +22,8 @@ def load():
         lib.is3d_host_read_surface.restype = C.c_long
         lib.is3d_host_read_surface.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, PD, PD]
         lib.is3d_host_read_pdg.argtypes = [C.c_char_p, C.c_int, C.c_int, PL, PD, PI, PI, PI]
+        lib.is3d_host_read_decays.restype = C.c_long
+        lib.is3d_host_read_decays.argtypes = [C.c_char_p, C.c_int, C.c_long, PL, PI, PD, PL]
         lib.is3d_host_param.argtypes = [C.c_char_p, C.c_char_p, PD]
         lib.is3d_host_total_yield.argtypes = [C.c_char_p, C.c_int, C.c_int, PD, PL, C.c_char_p, C.c_int]
         lib.is3d_host_read_vorticity.restype = C.c_long
@@ -73,6 +75,21 @@ def read_pdg(workdir, hrg_eos):
                            m.ctypes.data_as(C.POINTER(C.c_double)), g.ctypes.data_as(C.POINTER(C.c_int)),
                            b.ctypes.data_as(C.POINTER(C.c_int)), s.ctypes.data_as(C.POINTER(C.c_int)))
     return dict(mcid=mc, mass=m, gspin=g, baryon=b, sign=s)
+
+
+def read_decays(workdir, hrg_eos):
+    """The decay rows of the run directory's PDG file, antibaryon rows generated, in hrg.decay_channels' form:
+    row_mcid, row_n_body, row_branching, row_daughters[n][5]."""
+    lib = load()
+    n = lib.is3d_host_read_decays(workdir.encode(), hrg_eos, 0, None, None, None, None)
+    if n < 0:
+        raise RuntimeError("pdg read failed")
+    mc = np.zeros(n, dtype=np.int64); nb = np.zeros(n, dtype=np.int32); br = np.zeros(n)
+    ds = np.zeros((n, 5), dtype=np.int64)
+    lib.is3d_host_read_decays(workdir.encode(), hrg_eos, n, mc.ctypes.data_as(C.POINTER(C.c_long)),
+                              nb.ctypes.data_as(C.POINTER(C.c_int)), br.ctypes.data_as(C.POINTER(C.c_double)),
+                              ds.ctypes.data_as(C.POINTER(C.c_long)))
+    return dict(row_mcid=mc, row_n_body=nb.astype(np.int64), row_branching=br, row_daughters=ds)
 
 
 def param(path, key):

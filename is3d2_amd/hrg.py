@@ -103,6 +103,82 @@ def pdg_particles(hrg):
                 sign=np.array(sign, dtype=np.float64))
 
 
+def decay_rows_with_antibaryons(rows, particles):
+    """The decay rows and particle records of a conventional PDG file with the antibaryon entries the reference's
+    reader generates (readindata.cpp:1013-1060): every baryon (baryon > 0) is followed by its antiparticle, whose
+    rows repeat the baryon's with every daughter negated -- except daughters that are neutral non-strange mesons
+    (baryon = charge = strange = 0, :1055), which are their own antiparticles.
+
+    rows: dict of row_mcid, row_n_body, row_branching, row_daughters[n][5]; particles: dict of p_mcid, p_mass,
+    p_width, p_baryon, p_strange, p_charge (file order).  Returns (rows, particles) in the same form."""
+    info = {int(m): (int(b), int(s), int(q)) for m, b, s, q in
+            zip(particles["p_mcid"], particles["p_baryon"], particles["p_strange"], particles["p_charge"])}
+    by_parent = {}
+    for m, nb, br, ds in zip(rows["row_mcid"], rows["row_n_body"], rows["row_branching"], rows["row_daughters"]):
+        by_parent.setdefault(int(m), []).append((int(nb), float(br), [int(d) for d in ds]))
+    out_rows, out_parts = [], []
+    for k, m in enumerate(int(v) for v in particles["p_mcid"]):
+        rec = [particles[f][k] for f in ("p_mass", "p_width", "p_baryon", "p_strange", "p_charge")]
+        out_parts.append([m] + rec)
+        for nb, br, ds in by_parent.get(m, []):
+            out_rows.append((m, nb, br, ds))
+        if rec[2] > 0:
+            out_parts.append([-m, rec[0], rec[1], -rec[2], -rec[3], -rec[4]])
+            for nb, br, ds in by_parent.get(m, []):
+                anti = []
+                for d in ds:
+                    if d == 0:
+                        anti.append(0)
+                        continue
+                    if d not in info:
+                        raise ValueError("can not find decay particle %d for the anti-baryon of %d" % (d, m))
+                    b, s, q = info[d]
+                    anti.append(d if (b == 0 and q == 0 and s == 0) else -d)
+                out_rows.append((-m, nb, br, anti))
+    p = np.array(out_parts, dtype=object)
+    new_parts = dict(p_mcid=p[:, 0].astype(np.int64), p_mass=p[:, 1].astype(np.float64),
+                     p_width=p[:, 2].astype(np.float64), p_baryon=p[:, 3].astype(np.int64),
+                     p_strange=p[:, 4].astype(np.int64), p_charge=p[:, 5].astype(np.int64))
+    new_rows = dict(row_mcid=np.array([r[0] for r in out_rows], dtype=np.int64),
+                    row_n_body=np.array([r[1] for r in out_rows], dtype=np.int64),
+                    row_branching=np.array([r[2] for r in out_rows], dtype=np.float64),
+                    row_daughters=np.array([r[3] for r in out_rows], dtype=np.int64).reshape(-1, 5))
+    return new_rows, new_parts
+
+
+def decay_channels(rows, particles, mcids, antibaryons=True):
+    """The engine's channel table (_lib.DECAY_DTYPE, Engine.set_decays) for the chosen list `mcids` from PDG decay
+    rows (the form above; antibaryons = True generates the antibaryon channels first).  A row whose parent is not
+    chosen is dropped; a daughter that is not chosen gets index -1 (its mass and width still enter the kinematics);
+    rows with more than three bodies keep their first three daughters (the engine skips and counts them)."""
+    from ._lib import DECAY_DTYPE
+    if antibaryons:
+        rows, particles = decay_rows_with_antibaryons(rows, particles)
+    rec = {}
+    for m, mass, width in zip(particles["p_mcid"], particles["p_mass"], particles["p_width"]):
+        rec.setdefault(int(m), (float(mass), float(width)))
+    index = {}
+    for i, m in enumerate(int(v) for v in mcids):
+        index.setdefault(m, i)
+    out = []
+    for m, nb, br, ds in zip(rows["row_mcid"], rows["row_n_body"], rows["row_branching"], rows["row_daughters"]):
+        m, nb = int(m), abs(int(nb))     # the UrQMD table flags some rows with a negative body count
+        if m not in index:
+            continue
+        c = np.zeros((), dtype=DECAY_DTYPE)
+        c["parent"], c["n_body"], c["branching"] = index[m], nb, br
+        c["mass_parent"], c["width_parent"] = rec[m]
+        c["daughter"] = -1
+        for k in range(min(nb, 3)):
+            d = int(ds[k])
+            if d not in rec:
+                raise ValueError("decay row of %d: daughter %d is not in the particle list" % (m, d))
+            c["daughter"][k] = index.get(d, -1)
+            c["mass"][k], c["width"][k] = rec[d]
+        out.append(c)
+    return np.array(out, dtype=DECAY_DTYPE) if out else np.zeros(0, dtype=DECAY_DTYPE)
+
+
 def chosen_mcids(name):
     return _load()["chosen_" + name].copy()
 

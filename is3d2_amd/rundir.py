@@ -26,17 +26,29 @@ def _table(path, v, w):
             f.write("%.17g\t%.17g\n" % (a, b))
 
 
-def write_pdg(d, hrg_eos):
+def write_pdg(d, hrg_eos, decays=None):
+    """decays (optional, conventional format only): decay rows and particle records in the form of
+    hrg.decay_rows_with_antibaryons' input (row_mcid, row_n_body, row_branching, row_daughters, p_mcid, p_strange,
+    p_charge); a particle then gets its strangeness, charge and rows.  Default: 0 channels."""
     p = np.load(os.path.join(_DATA, "pdg.npz"))
     os.makedirs(os.path.join(d, "PDG"), exist_ok=True)
     if hrg_eos in (1, 2):
         key = "urqmd" if hrg_eos == 1 else "smash"
         fn = "pdg-urqmd_v3.3+.dat" if hrg_eos == 1 else "pdg_smash.dat"
+        rows, quantum = {}, {}
+        if decays is not None:
+            for m, nb, br, ds in zip(decays["row_mcid"], decays["row_n_body"], decays["row_branching"], decays["row_daughters"]):
+                rows.setdefault(int(m), []).append((int(nb), float(br), [int(v) for v in ds]))
+            quantum = {int(m): (int(s), int(q)) for m, s, q in zip(decays["p_mcid"], decays["p_strange"], decays["p_charge"])}
         with open(os.path.join(d, "PDG", fn), "w") as f:
             for m, mass, w, g, b in zip(p[key + "_mcid"], p[key + "_mass"], p[key + "_width"], p[key + "_gspin"],
                                         p[key + "_baryon"]):
-                # decay channels are not needed on the continuous-spectra path: written as 0 channels
-                f.write("%d h%d %.17g %.17g %d %d 0 0 0 1 0 0\n" % (m, abs(m), mass, w, g, b))
+                # decay channels are not needed on the continuous-spectra path: written as 0 channels by default
+                s, q = quantum.get(int(m), (0, 0))
+                mine = rows.get(int(m), [])
+                f.write("%d h%d %.17g %.17g %d %d %d 0 0 1 %d %d\n" % (m, abs(m), mass, w, g, b, s, q, len(mine)))
+                for nb, br, ds in mine:
+                    f.write("%d %d %.17g %s\n" % (m, nb, br, " ".join(str(v) for v in ds)))
     else:
         with open(os.path.join(d, "PDG", "pdg_box.dat"), "w") as f:
             f.write("# NAME MASS[GEV] WIDTH[GEV] PARITY PDG\n")
@@ -45,8 +57,8 @@ def write_pdg(d, hrg_eos):
 
 
 def write_run_dir(d, surf, params, hrg_eos=2, chosen="pikp", pT="pT24", phi="phi24", y="y21", eta="eta24",
-                  surface_format=1):
-    """Write a complete run directory.  `params` maps iS3D_parameters.dat keys to values."""
+                  surface_format=1, decays=None):
+    """Write a complete run directory.  `params` maps iS3D_parameters.dat keys to values; `decays`: write_pdg's."""
     for sub in ("input", "PDG", "tables/momentum", "tables/spacetime_rapidity", "tables/gauss",
                 "tables/thermodynamic", "results/continuous"):
         os.makedirs(os.path.join(d, sub), exist_ok=True)
@@ -63,7 +75,7 @@ def write_run_dir(d, surf, params, hrg_eos=2, chosen="pikp", pT="pT24", phi="phi
     else:       # 1, or 5 = 1 + thermal-vorticity columns
         synth.write_mode1(os.path.join(d, "input", "surface.dat"), surf, include_baryon=baryon,
                           vorticity_seed=(5 if surface_format == 5 else None))
-    write_pdg(d, hrg_eos)
+    write_pdg(d, hrg_eos, decays)
     pp = np.load(os.path.join(_DATA, "pdg.npz"))
     mc = pp["chosen_" + chosen] if isinstance(chosen, str) else np.asarray(chosen)
     with open(os.path.join(d, "PDG", "chosen_particles.dat"), "w") as f:
