@@ -1,6 +1,7 @@
-// devbuf.h -- DevBuf<T>: the one owner of a device allocation (hipMalloc / hipFree), move-only, freed by its
-// destructor.  The engine's buffers are members of this type and its function-local scratch is a local, so an early
-// return frees what it allocated.
+// devbuf.h -- the one owner of each device resource in csrc, move-only, released by its destructor: DevBuf<T> of an
+// allocation (hipMalloc / hipFree), DevStream of a stream and DevEvent of an event.  The buffers, streams and events of
+// the engine, the device group, the sampler and the table sets are members of these types and function-local scratch
+// is a local, so an early return releases what it made.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -46,5 +47,35 @@ class DevBuf {
   T* p_ = nullptr;
   long cap_ = 0;
 };
+
+// a stream or an event: empty until create(flags) makes it on the current device (so a lazily made one stays lazy:
+// `if (!s) s.create(...)`), destroyed by reset() or the destructor
+template <class H, hipError_t (*Create)(H*, unsigned), hipError_t (*Destroy)(H)>
+class DevHandle {
+ public:
+  DevHandle() = default;
+  DevHandle(DevHandle&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+  DevHandle& operator=(DevHandle&& o) noexcept {
+    if (this != &o) { reset(); h_ = o.h_; o.h_ = nullptr; }
+    return *this;
+  }
+  ~DevHandle() { reset(); }
+
+  hipError_t create(unsigned flags) {
+    reset();
+    return Create(&h_, flags);
+  }
+  void reset() {
+    if (h_) (void)Destroy(h_);
+    h_ = nullptr;
+  }
+  H get() const { return h_; }
+  explicit operator bool() const { return h_ != nullptr; }
+
+ private:
+  H h_ = nullptr;
+};
+using DevStream = DevHandle<hipStream_t, hipStreamCreateWithFlags, hipStreamDestroy>;
+using DevEvent = DevHandle<hipEvent_t, hipEventCreateWithFlags, hipEventDestroy>;   // flags hipEventDefault: a timing event
 
 }  // namespace is3d

@@ -55,6 +55,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/is3d_amd.h"
@@ -116,7 +117,8 @@ struct is3d_engine {
   std::vector<double> jl2, jz, jx, jl2c, jzc;
   double bp_max = -1.0;
   bool tables_dirty = true;
-  // device: every allocation is a DevBuf member (devbuf.h); the raw pointers below are views into d_tables / d_const
+  // device: every allocation, stream and event is a DevBuf / DevStream / DevEvent member (devbuf.h); the raw pointers
+  // below are views into d_tables / d_const
   DevBuf<double> d_tables;
   DfTables dtb{};
   DevBuf<double> d_const;    // species, grids, gla, pdg
@@ -155,12 +157,13 @@ struct is3d_engine {
   DevBuf<int> d_fb;           // modified modes: [0] fallback cell count, [1..] k_fbwrite's cell list
   DevBuf<double> d_phtab;     // F_TS launches: k_phitab's per-(cell, pT, phi) rows of one chunk of cells
   DevBuf<double> d_phtab2;    // ... and of the next chunk, integrated on the side stream meanwhile
-  hipStream_t side = nullptr; // F_TS chunks alternate between the launch stream and this one
-  hipEvent_t fork = nullptr, join = nullptr;
+  // the streams and events of the chunked F_TS launches are made by the first launch that needs them
+  DevStream side;             // F_TS chunks alternate between the launch stream and this one
+  DevEvent fork, join;
   // folded F_TS chunks: k_fold runs on its own stream, in chunk order, after each chunk's k_spectra
   // (ev_spec); a chunk reusing a slab buffer waits for the fold that emptied it (ev_fold)
-  hipStream_t fold_st = nullptr;
-  hipEvent_t ev_spec[2] = {nullptr, nullptr}, ev_fold[2] = {nullptr, nullptr}, fold_join = nullptr;
+  DevStream fold_st;
+  DevEvent ev_spec[2], ev_fold[2], fold_join;
   // is3d_set_tuning: F_TS table chunking (defaults IS3D_PHITAB_ONE / IS3D_PHITAB_BYTES): tables of the whole window
   // up to phitab_one bytes are one chunk, larger ones chunks of whole cell splits of about phitab_chunk bytes
   long phitab_one = IS3D_PHITAB_ONE, phitab_chunk = IS3D_PHITAB_BYTES;
@@ -176,7 +179,7 @@ struct is3d_engine {
   long ycell_n = -1;
   DevBuf<int> d_err;                  // the device error word (cf_math.h DF_*)
   DevBuf<unsigned long long> d_cnt;   // [8] counters (PrepArgs::cnt)
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  DevEvent ev[4];             // timing events of a launch's stages
   LaunchCtx lc;               // the launch in flight (staged launches)
   // spin polarization (mode 5, polzn.hip): thermal vorticity [6][ncell] of the surface set last (a new surface
   // clears it) and the kernels' constants, rebuilt after a species / classes / grid / params change
@@ -213,7 +216,7 @@ struct is3d_engine {
   is3d::decay::Packed dk_pack;
   DevBuf<double> d_dk_d, d_dk_log, d_dk_io;
   DevBuf<int> d_dk_i;
-  hipEvent_t dk_ev[2] = {nullptr, nullptr};
+  DevEvent dk_ev[2];
   is3d_decay_stats dk_stats{};
 
   int fail(int code, const std::string& msg) { err = msg; return code; }
@@ -258,8 +261,8 @@ extern "C" is3d_engine* is3d_create(int device) {
     delete e;
     return nullptr;
   }
-  for (auto& v : e->ev) (void)hipEventCreate(&v);
-  for (auto& v : e->dk_ev) (void)hipEventCreate(&v);
+  for (auto& v : e->ev) (void)v.create(hipEventDefault);
+  for (auto& v : e->dk_ev) (void)v.create(hipEventDefault);
   return e;
 }
 
@@ -271,17 +274,7 @@ extern "C" void is3d_destroy(is3d_engine* e) {
     return;
   }
   (void)hipSetDevice(e->device);
-  (void)hipDeviceSynchronize();     // before the DevBuf members die with *e
-  if (e->side) (void)hipStreamDestroy(e->side);
-  if (e->fold_st) (void)hipStreamDestroy(e->fold_st);
-  for (auto v : {e->ev_spec[0], e->ev_spec[1], e->ev_fold[0], e->ev_fold[1], e->fold_join})
-    if (v) (void)hipEventDestroy(v);
-  if (e->fork) (void)hipEventDestroy(e->fork);
-  if (e->join) (void)hipEventDestroy(e->join);
-  is3d::polzn::tables_free(e->pz);
-  is3d::sampler::tables_free(e->smp);
-  for (auto& v : e->ev) if (v) (void)hipEventDestroy(v);
-  for (auto& v : e->dk_ev) if (v) (void)hipEventDestroy(v);
+  (void)hipDeviceSynchronize();     // before the buffers, streams and events die with *e
   delete e;
 }
 
@@ -946,16 +939,16 @@ static int begin_stats(is3d_engine* e, long cells, hipStream_t st) {
   e->st.cells = cells;
   HIPCHK(e, hipMemsetAsync(e->d_err.get(), 0, sizeof(int), st));
   HIPCHK(e, hipMemsetAsync(e->d_cnt.get(), 0, 8 * sizeof(unsigned long long), st));
-  HIPCHK(e, hipEventRecord(e->ev[0], st));
+  HIPCHK(e, hipEventRecord(e->ev[0].get(), st));
   return IS3D_OK;
 }
 
 // ... and the stage times between its four events, once ev[3] has completed
 static void read_timings(is3d_engine* e) {
   float ms = 0.f;
-  if (hipEventElapsedTime(&ms, e->ev[0], e->ev[1]) == hipSuccess) e->st.ms_prepass = ms;
-  if (hipEventElapsedTime(&ms, e->ev[1], e->ev[2]) == hipSuccess) e->st.ms_spectra = ms;
-  if (hipEventElapsedTime(&ms, e->ev[0], e->ev[3]) == hipSuccess) e->st.ms_total = ms;
+  if (hipEventElapsedTime(&ms, e->ev[0].get(), e->ev[1].get()) == hipSuccess) e->st.ms_prepass = ms;
+  if (hipEventElapsedTime(&ms, e->ev[1].get(), e->ev[2].get()) == hipSuccess) e->st.ms_spectra = ms;
+  if (hipEventElapsedTime(&ms, e->ev[0].get(), e->ev[3].get()) == hipSuccess) e->st.ms_total = ms;
 }
 
 // the prepass of cells [c0, c1) of the held surface into rec / aux (operation 1; a caller for another sets k.operation)
@@ -967,15 +960,20 @@ static PrepArgs prep_args(const is3d_engine* e, double* rec, double* aux, long c
   pa.err = err; pa.cnt = cnt;
   return pa;
 }
+// f(std::integral_constant<int, MODE>{}) for df_mode `mode`: the one place a templated launcher's mode is chosen.
+// FIRST: the lowest mode the site sees (an F_FB launch: PTM), so that it names no launcher for the modes below it
+template <int FIRST = GRAD, class F>
+static void with_mode(int mode, F f) {
+  if constexpr (FIRST <= GRAD) { if (mode == GRAD) return f(std::integral_constant<int, GRAD>{}); }
+  if constexpr (FIRST <= CE) { if (mode == CE) return f(std::integral_constant<int, CE>{}); }
+  if (mode == PTM) return f(std::integral_constant<int, PTM>{});
+  if (mode == PTB) return f(std::integral_constant<int, PTB>{});
+  return f(std::integral_constant<int, PTMA>{});
+}
+
 static int enqueue_prep(is3d_engine* e, const PrepArgs& pa, hipStream_t st) {
   const dim3 g1((unsigned)std::max(1L, (pa.c1 - pa.c0 + 255) / 256)), b1(256);
-  switch (e->p.df_mode) {
-    case GRAD: hipLaunchKernelGGL(k_prep<GRAD>, g1, b1, 0, st, pa); break;
-    case CE: hipLaunchKernelGGL(k_prep<CE>, g1, b1, 0, st, pa); break;
-    case PTM: hipLaunchKernelGGL(k_prep<PTM>, g1, b1, 0, st, pa); break;
-    case PTB: hipLaunchKernelGGL(k_prep<PTB>, g1, b1, 0, st, pa); break;
-    default: hipLaunchKernelGGL(k_prep<PTMA>, g1, b1, 0, st, pa); break;
-  }
+  with_mode(e->p.df_mode, [&](auto M) { hipLaunchKernelGGL(k_prep<decltype(M)::value>, g1, b1, 0, st, pa); });
   HIPCHK(e, hipGetLastError());
   return IS3D_OK;
 }
@@ -1026,7 +1024,7 @@ static int plasma_densities(is3d_engine* e, const double* plasma, double* dens) 
 // that chain_pass x npass + chain_end complete -- with the counters in d_cnt.  srule: the chain rule (aniso_math.h
 // aniso_cell), 0 for the spectra, 1 for the particle sampler (is3d_sample_famod).  op: the prep constants' operation
 // (1; 0 for is3d_calculate_dN_dX_famod).  L.empty: no cell in the window.
-static int prepass_begin(is3d_engine* e, void* stream, long q0, long q1, int has_pred, int srule, int op = 1) {
+static int prepass_begin(is3d_engine* e, void* stream, long q0, long q1, int has_pred, int srule, int op) {
   HIPCHK(e, hipSetDevice(e->device));
   LaunchCtx& L = e->lc;
   L = LaunchCtx{};
@@ -1104,17 +1102,6 @@ static int prepass_begin(is3d_engine* e, void* stream, long q0, long q1, int has
   return IS3D_OK;
 }
 
-static int launch_begin(is3d_engine* e, double* dev_out, void* stream, long q0, long q1, int has_pred) {
-  int rc = finalize_tables(e);
-  if (rc) return rc;
-  if (!dev_out) return e->fail(IS3D_ERR_ARG, "null output buffer");
-  rc = prepass_begin(e, stream, q0, q1, has_pred, 0);
-  if (rc) return rc;
-  e->lc.dev_out = dev_out;
-  if (e->lc.empty) HIPCHK(e, hipMemsetAsync(dev_out, 0, is3d_output_size(e) * sizeof(double), e->lc.st));
-  return IS3D_OK;
-}
-
 static int chain_pass(is3d_engine* e, int pass) {
   LaunchCtx& L = e->lc;
   if (L.empty || !L.chained) return IS3D_OK;
@@ -1133,6 +1120,42 @@ static int chain_end(is3d_engine* e) {
   hipLaunchKernelGGL(k_chain_count, dim3((unsigned)std::min(1024L, std::max(1L, (c_hi - c_lo + 255) / 256))), dim3(256), 0,
                      L.st, (const double*)e->d_rec.get(), (const int*)L.ca.info, c_lo, c_hi, e->d_cnt.get());
   HIPCHK(e, hipGetLastError());
+  return IS3D_OK;
+}
+
+// the whole prepass of a launch on this engine alone: prepass_begin, every chain pass, chain_end
+static int run_prepass(is3d_engine* e, void* stream, int srule, int op) {
+  int rc = prepass_begin(e, stream, 0, -1, 0, srule, op);
+  for (int pass = 0; !rc && e->lc.chained && pass < e->lc.ca.npass; pass++) rc = chain_pass(e, pass);
+  return rc ? rc : chain_end(e);
+}
+
+// whole: the chains too (run_prepass: is3d_launch); otherwise the caller stages them (a chain range q0, q1, has_pred)
+static int launch_begin(is3d_engine* e, double* dev_out, void* stream, long q0, long q1, int has_pred, bool whole = false) {
+  int rc = finalize_tables(e);
+  if (rc) return rc;
+  if (!dev_out) return e->fail(IS3D_ERR_ARG, "null output buffer");
+  rc = whole ? run_prepass(e, stream, 0, 1) : prepass_begin(e, stream, q0, q1, has_pred, 0, 1);
+  if (rc) return rc;
+  e->lc.dev_out = dev_out;
+  if (e->lc.empty) HIPCHK(e, hipMemsetAsync(dev_out, 0, is3d_output_size(e) * sizeof(double), e->lc.st));
+  return IS3D_OK;
+}
+
+// PTMA: the C / B matrices of cells [p0, p1) of the launch in flight from their (lambda, aT, aL) in d_sol
+static int enqueue_famod_b(is3d_engine* e) {
+  const LaunchCtx& L = e->lc;
+  hipLaunchKernelGGL(k_famod_b, dim3((unsigned)std::max(1L, (L.p1 - L.p0 + 255) / 256)), dim3(256), 0, L.st, L.pa,
+                     (const double*)e->d_sol.get());
+  HIPCHK(e, hipGetLastError());
+  return IS3D_OK;
+}
+
+// the prepass counters of a launch whose stream has been waited for: d_cnt -> the stats
+static int read_counters(is3d_engine* e) {
+  unsigned long long cnt[4] = {0, 0, 0, 0};
+  HIPCHK(e, hipMemcpy(cnt, e->d_cnt.get(), sizeof(cnt), hipMemcpyDeviceToHost));
+  e->st.breakdown = (long)cnt[0]; e->st.pl_negative = (long)cnt[1]; e->st.recon_fail = (long)cnt[2]; e->st.iterations = (long)cnt[3];
   return IS3D_OK;
 }
 
@@ -1273,24 +1296,24 @@ static int enqueue_spectra(is3d_engine* e, const IntegralPlan& I, const double* 
     if (!e->d_phtab.reserve(phn * npT * rw)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(phi tables) failed");
     if (nchunk > 1) {
       if (!e->d_phtab2.reserve(phn * npT * rw)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(phi tables) failed");
-      if (!e->side) HIPCHK(e, hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking));
-      if (!e->fork) HIPCHK(e, hipEventCreateWithFlags(&e->fork, hipEventDisableTiming));
-      if (!e->join) HIPCHK(e, hipEventCreateWithFlags(&e->join, hipEventDisableTiming));
-      HIPCHK(e, hipEventRecord(e->fork, st));
-      HIPCHK(e, hipStreamWaitEvent(e->side, e->fork, 0));
+      if (!e->side) HIPCHK(e, e->side.create(hipStreamNonBlocking));
+      if (!e->fork) HIPCHK(e, e->fork.create(hipEventDisableTiming));
+      if (!e->join) HIPCHK(e, e->join.create(hipEventDisableTiming));
+      HIPCHK(e, hipEventRecord(e->fork.get(), st));
+      HIPCHK(e, hipStreamWaitEvent(e->side.get(), e->fork.get(), 0));
     }
     if (I.fold) {
-      if (!e->fold_st) HIPCHK(e, hipStreamCreateWithFlags(&e->fold_st, hipStreamNonBlocking));
+      if (!e->fold_st) HIPCHK(e, e->fold_st.create(hipStreamNonBlocking));
       for (auto* v : {&e->ev_spec[0], &e->ev_spec[1], &e->ev_fold[0], &e->ev_fold[1], &e->fold_join})
-        if (!*v) HIPCHK(e, hipEventCreateWithFlags(v, hipEventDisableTiming));
-      HIPCHK(e, hipStreamWaitEvent(e->fold_st, e->fork, 0));
+        if (!*v) HIPCHK(e, v->create(hipEventDisableTiming));
+      HIPCHK(e, hipStreamWaitEvent(e->fold_st.get(), e->fork.get(), 0));
     }
     // folded: slab 0 is the accumulator, chunk ic's splits go to buffer ic & 1 (slabs 1 + (ic & 1) spc ...)
     const int fgrid = (int)std::min(4096L, std::max(1L, (I.sstride + 255) / 256));
     for (long ic = 0; ic < nchunk; ic++) {
       const long s0 = ic * spc, ns = std::min(spc, nsplit - s0);
       const long c0 = s0 * cps, ncc = std::min(nw, (s0 + ns) * cps) - c0;
-      hipStream_t cs = (ic & 1) ? e->side : st;
+      hipStream_t cs = (ic & 1) ? e->side.get() : st;
       double* tab = (ic & 1) ? e->d_phtab2.get() : e->d_phtab.get();
       PhiTabArgs ta{};
       ta.rec = rec_w; ta.c0 = c0; ta.nc = ncc; ta.pT = e->d_pT; ta.cphi = e->d_cphi; ta.sphi = e->d_sphi;
@@ -1304,36 +1327,30 @@ static int enqueue_spectra(is3d_engine* e, const IntegralPlan& I, const double* 
       if (mode == GRAD) launch_phitab<GRAD>(cs, ta);
       else launch_phitab<CE>(cs, ta);
       // a folded chunk reusing slab buffer ic & 1 waits for the fold of chunk ic - 2, which emptied it
-      if (I.fold && ic >= 2) HIPCHK(e, hipStreamWaitEvent(cs, e->ev_fold[ic & 1], 0));
+      if (I.fold && ic >= 2) HIPCHK(e, hipStreamWaitEvent(cs, e->ev_fold[ic & 1].get(), 0));
       if (mode == GRAD) launch_spectra<GRAD>(grid, shmem, cs, sc, kflags, KJ);
       else launch_spectra<CE>(grid, shmem, cs, sc, kflags, KJ);
       HIPCHK(e, hipGetLastError());
       if (I.fold) {
-        HIPCHK(e, hipEventRecord(e->ev_spec[ic & 1], cs));
-        HIPCHK(e, hipStreamWaitEvent(e->fold_st, e->ev_spec[ic & 1], 0));
-        hipLaunchKernelGGL(k_fold, dim3((unsigned)fgrid), dim3(256), 0, e->fold_st, e->d_slab.get(), (const double*)buf,
+        HIPCHK(e, hipEventRecord(e->ev_spec[ic & 1].get(), cs));
+        HIPCHK(e, hipStreamWaitEvent(e->fold_st.get(), e->ev_spec[ic & 1].get(), 0));
+        hipLaunchKernelGGL(k_fold, dim3((unsigned)fgrid), dim3(256), 0, e->fold_st.get(), e->d_slab.get(), (const double*)buf,
                            I.sstride, (int)ns, ic == 0 ? 1 : 0, gate, want);
         HIPCHK(e, hipGetLastError());
-        HIPCHK(e, hipEventRecord(e->ev_fold[ic & 1], e->fold_st));
+        HIPCHK(e, hipEventRecord(e->ev_fold[ic & 1].get(), e->fold_st.get()));
       }
     }
     if (nchunk > 1) {
-      HIPCHK(e, hipEventRecord(e->join, e->side));
-      HIPCHK(e, hipStreamWaitEvent(st, e->join, 0));
+      HIPCHK(e, hipEventRecord(e->join.get(), e->side.get()));
+      HIPCHK(e, hipStreamWaitEvent(st, e->join.get(), 0));
     }
     if (I.fold) {
-      HIPCHK(e, hipEventRecord(e->fold_join, e->fold_st));
-      HIPCHK(e, hipStreamWaitEvent(st, e->fold_join, 0));
+      HIPCHK(e, hipEventRecord(e->fold_join.get(), e->fold_st.get()));
+      HIPCHK(e, hipStreamWaitEvent(st, e->fold_join.get(), 0));
     }
   } else {
     const dim3 grid((unsigned)(wgs * nsplit));
-    switch (mode) {
-      case GRAD: launch_spectra<GRAD>(grid, shmem, st, sa, kflags, KJ); break;
-      case CE: launch_spectra<CE>(grid, shmem, st, sa, kflags, KJ); break;
-      case PTM: launch_spectra<PTM>(grid, shmem, st, sa, kflags, KJ); break;
-      case PTB: launch_spectra<PTB>(grid, shmem, st, sa, kflags, KJ); break;
-      default: launch_spectra<PTMA>(grid, shmem, st, sa, kflags, KJ); break;
-    }
+    with_mode(mode, [&](auto M) { launch_spectra<decltype(M)::value>(grid, shmem, st, sa, kflags, KJ); });
   }
   HIPCHK(e, hipGetLastError());
   if (mode >= PTM) {
@@ -1342,11 +1359,7 @@ static int enqueue_spectra(is3d_engine* e, const IntegralPlan& I, const double* 
     fa.fbcells = e->d_fb.get() + 1; fa.fbcount = e->d_fb.get();
     const int fflags = (e->p.regulate_deltaf ? F_REG : 0) | (e->p.outflow ? F_OUT : 0) | F_FB;
     const dim3 gfb((unsigned)(I.bx * npT * I.nsplit_fb));
-    switch (mode) {
-      case PTM: launch_spectra<PTM>(gfb, P.shmem_fb, st, fa, fflags, KJ); break;
-      case PTB: launch_spectra<PTB>(gfb, P.shmem_fb, st, fa, fflags, KJ); break;
-      default: launch_spectra<PTMA>(gfb, P.shmem_fb, st, fa, fflags, KJ); break;
-    }
+    with_mode<PTM>(mode, [&](auto M) { launch_spectra<decltype(M)::value>(gfb, P.shmem_fb, st, fa, fflags, KJ); });
     HIPCHK(e, hipGetLastError());
   }
   return IS3D_OK;
@@ -1385,24 +1398,18 @@ static int launch_end(is3d_engine* e) {
   double* dev_out = L.dev_out;
   HIPCHK(e, hipSetDevice(e->device));
   if (L.empty) {
-    HIPCHK(e, hipEventRecord(e->ev[1], st));
-    HIPCHK(e, hipEventRecord(e->ev[2], st));
-    HIPCHK(e, hipEventRecord(e->ev[3], st));
+    HIPCHK(e, hipEventRecord(e->ev[1].get(), st));
+    HIPCHK(e, hipEventRecord(e->ev[2].get(), st));
+    HIPCHK(e, hipEventRecord(e->ev[3].get(), st));
     e->launched = true;
     return IS3D_OK;
   }
   const long n = e->ncell;
   const int mode = e->p.df_mode;
   const long wlo = L.wlo, nw = L.nw;
-  const PrepArgs& pa = L.pa;
-  const dim3 g1((unsigned)std::max(1L, (L.p1 - L.p0 + 255) / 256)), b1(256);
-  if (mode == PTMA) {
-    hipLaunchKernelGGL(k_famod_b, g1, b1, 0, st, pa, (const double*)e->d_sol.get());
-    HIPCHK(e, hipGetLastError());
-  }
-  int rc = mode == PTM ? enqueue_renorm(e, pa.k, wlo, nw, n, st) : IS3D_OK;
+  int rc = mode == PTMA ? enqueue_famod_b(e) : mode == PTM ? enqueue_renorm(e, L.pa.k, wlo, nw, n, st) : IS3D_OK;
   if (rc) return rc;
-  HIPCHK(e, hipEventRecord(e->ev[1], st));
+  HIPCHK(e, hipEventRecord(e->ev[1].get(), st));
   // the integral and the reduction see the window only: records from wlo on, nw cells
   const double* rec_w = e->d_rec.get() + wlo * (long)NREC;
   // --- main integral
@@ -1429,11 +1436,11 @@ static int launch_end(is3d_engine* e) {
   rc = enqueue_spectra(e, I, rec_w, nw, st, gate, 0);
   if (!rc && gated) rc = enqueue_spectra(e, J, rec_w, nw, st, gate, 1);
   if (rc) return rc;
-  HIPCHK(e, hipEventRecord(e->ev[2], st));
+  HIPCHK(e, hipEventRecord(e->ev[2].get(), st));
   rc = enqueue_reduce(e, I, dev_out, st, gate, 0);
   if (!rc && gated) rc = enqueue_reduce(e, J, dev_out, st, gate, 1);
   if (rc) return rc;
-  HIPCHK(e, hipEventRecord(e->ev[3], st));
+  HIPCHK(e, hipEventRecord(e->ev[3].get(), st));
   e->launched = true;
   return IS3D_OK;
 }
@@ -1444,9 +1451,7 @@ extern "C" int is3d_launch(is3d_engine* e, double* dev_out, void* stream) {
   if (e->chain_q1 >= 0)
     return e->fail(IS3D_ERR_STATE, "a chain range (is3d_set_chain_range) runs through the staged launch: its first "
                                    "positions need the previous range's boundary states");
-  int rc = launch_begin(e, dev_out, stream, 0, -1, 0);
-  for (int pass = 0; !rc && e->lc.chained && pass < e->lc.ca.npass; pass++) rc = chain_pass(e, pass);
-  if (!rc) rc = chain_end(e);
+  const int rc = launch_begin(e, dev_out, stream, 0, -1, 0, true);
   return rc ? rc : launch_end(e);
 }
 
@@ -1565,35 +1570,40 @@ extern "C" int is3d_finish(is3d_engine* e) {
   HIPCHK(e, hipSetDevice(e->device));
   if (e->dk_launched) {       // is3d_launch_feeddown: no device error word, its own two events
     e->dk_launched = false;
-    HIPCHK(e, hipEventSynchronize(e->dk_ev[1]));
+    HIPCHK(e, hipEventSynchronize(e->dk_ev[1].get()));
     float ms = 0.f;
-    if (hipEventElapsedTime(&ms, e->dk_ev[0], e->dk_ev[1]) == hipSuccess) e->dk_stats.ms_total = ms;
+    if (hipEventElapsedTime(&ms, e->dk_ev[0].get(), e->dk_ev[1].get()) == hipSuccess) e->dk_stats.ms_total = ms;
     if (!e->launched) return IS3D_OK;
   }
-  HIPCHK(e, hipEventSynchronize(e->ev[3]));
+  HIPCHK(e, hipEventSynchronize(e->ev[3].get()));
   e->launched = false;
   int derr = 0;
-  unsigned long long cnt[8];
   HIPCHK(e, hipMemcpy(&derr, e->d_err.get(), sizeof(int), hipMemcpyDeviceToHost));
-  HIPCHK(e, hipMemcpy(cnt, e->d_cnt.get(), sizeof(cnt), hipMemcpyDeviceToHost));
-  e->st.breakdown = (long)cnt[0]; e->st.pl_negative = (long)cnt[1]; e->st.recon_fail = (long)cnt[2]; e->st.iterations = (long)cnt[3];
+  const int rc = read_counters(e);
+  if (rc) return rc;
   read_timings(e);
   return df_error(e, derr, "Error: choose df_mode = (1,2,3,4,5)");
+}
+
+// what is3d_calculate_spectra and is3d_calculate_polarization share: launch(d_out) into the engine's output buffer of
+// outsize doubles on the null stream, finished and downloaded to `out`
+template <class L>
+static int calculate(is3d_engine* e, long outsize, double* out, L launch) {
+  HIPCHK(e, hipSetDevice(e->device));
+  if (!e->d_out.reserve(outsize)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(output) failed");
+  int rc = launch(e->d_out.get());
+  if (!rc) rc = is3d_finish(e);
+  if (rc) return rc;
+  HIPCHK(e, hipMemcpy(out, e->d_out.get(), outsize * sizeof(double), hipMemcpyDeviceToHost));
+  return IS3D_OK;
 }
 
 extern "C" int is3d_calculate_spectra(is3d_engine* e, double* dN_out) {
   if (e && e->grp) return is3d::group_calculate_spectra(e->grp, dN_out);
   if (!e || !dN_out) return e ? e->fail(IS3D_ERR_ARG, "null output") : IS3D_ERR_ARG;
-  int rc = finalize_tables(e);
+  const int rc = finalize_tables(e);
   if (rc) return rc;
-  const long outsize = is3d_output_size(e);
-  if (!e->d_out.reserve(outsize)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(output) failed");
-  rc = is3d_launch(e, e->d_out.get(), nullptr);
-  if (rc) return rc;
-  rc = is3d_finish(e);
-  if (rc) return rc;
-  HIPCHK(e, hipMemcpy(dN_out, e->d_out.get(), outsize * sizeof(double), hipMemcpyDeviceToHost));
-  return IS3D_OK;
+  return calculate(e, is3d_output_size(e), dN_out, [&](double* d) { return is3d_launch(e, d, nullptr); });
 }
 
 // operation = 0 (SpacetimeDistribution.cpp:31-1250): device prepass + per-(species, cell) yields + binning
@@ -1656,13 +1666,7 @@ static int dndx_finish(is3d_engine* e, long wlo, long n, const char* df_msg, dou
     const long nwg = (long)da.nbx * da.nchunk;
     if (nwg > 0x7fffffffL) return e->fail(IS3D_ERR_ARG, "surface too large for one dN/dX launch");
     const int kflags = (e->p.regulate_deltaf ? F_REG : 0) | (e->p.outflow ? F_OUT : 0);
-    switch (mode) {
-      case GRAD: launch_dndx<GRAD>(dim3((unsigned)nwg), shmem, st, da, kflags, KJ); break;
-      case CE: launch_dndx<CE>(dim3((unsigned)nwg), shmem, st, da, kflags, KJ); break;
-      case PTM: launch_dndx<PTM>(dim3((unsigned)nwg), shmem, st, da, kflags, KJ); break;
-      case PTB: launch_dndx<PTB>(dim3((unsigned)nwg), shmem, st, da, kflags, KJ); break;
-      default: launch_dndx<PTMA>(dim3((unsigned)nwg), shmem, st, da, kflags, KJ); break;
-    }
+    with_mode(mode, [&](auto M) { launch_dndx<decltype(M)::value>(dim3((unsigned)nwg), shmem, st, da, kflags, KJ); });
     HIPCHK(e, hipGetLastError());
     if (mode >= PTM) {
       // the separable-fallback lanes of the cells k_fbwrite lists (breakdown, narrow rapidity windows) in their own
@@ -1674,16 +1678,14 @@ static int dndx_finish(is3d_engine* e, long wlo, long n, const char* df_msg, dou
       fa.fbcells = e->d_fb.get() + 1; fa.fbcount = e->d_fb.get();
       fa.nchunk = std::max(1L, std::min(da.nchunk, (4096L + da.nbx - 1) / da.nbx));
       const long nfw = (long)da.nbx * fa.nchunk;
-      if (mode == PTM) launch_dndx<PTM>(dim3((unsigned)nfw), shmem_fb, st, fa, kflags | F_FB, KJ);
-      else if (mode == PTB) launch_dndx<PTB>(dim3((unsigned)nfw), shmem_fb, st, fa, kflags | F_FB, KJ);
-      else launch_dndx<PTMA>(dim3((unsigned)nfw), shmem_fb, st, fa, kflags | F_FB, KJ);
+      with_mode<PTM>(mode, [&](auto M) { launch_dndx<decltype(M)::value>(dim3((unsigned)nfw), shmem_fb, st, fa, kflags | F_FB, KJ); });
       HIPCHK(e, hipGetLastError());
     }
     e->ycell_n = n;
   } else {
     e->ycell_n = 0;
   }
-  HIPCHK(e, hipEventRecord(e->ev[2], st));
+  HIPCHK(e, hipEventRecord(e->ev[2].get(), st));
   if (n > 0) {
     // --- bin keys on the device, CSR (thread slice, bin) -> cells on the host, sums on the device
     if (!e->d_keys.reserve(3 * n)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(keys) failed");
@@ -1727,8 +1729,8 @@ static int dndx_finish(is3d_engine* e, long wlo, long n, const char* df_msg, dou
     hipLaunchKernelGGL(k_stbin, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, st, ba);
     HIPCHK(e, hipGetLastError());
   }
-  HIPCHK(e, hipEventRecord(e->ev[3], st));
-  HIPCHK(e, hipEventSynchronize(e->ev[3]));
+  HIPCHK(e, hipEventRecord(e->ev[3].get(), st));
+  HIPCHK(e, hipEventSynchronize(e->ev[3].get()));
   int derr = 0;
   HIPCHK(e, hipMemcpy(&derr, e->d_err.get(), sizeof(int), hipMemcpyDeviceToHost));
   if (n > 0) HIPCHK(e, hipMemcpy(part.data(), e->d_part.get(), part.size() * sizeof(double), hipMemcpyDeviceToHost));
@@ -1796,7 +1798,7 @@ extern "C" int is3d_calculate_dN_dX(is3d_engine* e, double* dN_taudtaudy, double
     if (!rc && e->p.df_mode == PTM) rc = enqueue_renorm(e, pa.k, 0, n, n, st);
     if (rc) return rc;
   }
-  HIPCHK(e, hipEventRecord(e->ev[1], st));
+  HIPCHK(e, hipEventRecord(e->ev[1].get(), st));
   return dndx_finish(e, 0, n, "Error: set df_mode = (1,2) in parameters.dat", dN_taudtaudy, dN_2pirdrdy, dN_dphidy);
 }
 
@@ -1817,24 +1819,13 @@ extern "C" int is3d_calculate_dN_dX_famod(is3d_engine* e, double* dN_taudtaudy, 
   if (!e->have_bins) return e->fail(IS3D_ERR_STATE, "is3d_set_spacetime_bins not called");
   rc = finalize_tables(e);
   if (rc) return rc;
-  rc = prepass_begin(e, nullptr, 0, -1, 0, 0, 0);
-  for (int pass = 0; !rc && e->lc.chained && pass < e->lc.ca.npass; pass++) rc = chain_pass(e, pass);
-  if (!rc) rc = chain_end(e);
-  if (rc) return rc;
+  rc = run_prepass(e, nullptr, 0, 0);
   const LaunchCtx& L = e->lc;
-  if (!L.empty) {
-    hipLaunchKernelGGL(k_famod_b, dim3((unsigned)std::max(1L, (L.p1 - L.p0 + 255) / 256)), dim3(256), 0, L.st, L.pa,
-                       (const double*)e->d_sol.get());
-    HIPCHK(e, hipGetLastError());
-  }
-  HIPCHK(e, hipEventRecord(e->ev[1], L.st));
-  rc = dndx_finish(e, L.wlo, L.nw, "Error: choose df_mode = (1,2,3,4,5)", dN_taudtaudy, dN_2pirdrdy, dN_dphidy);
+  if (!rc && !L.empty) rc = enqueue_famod_b(e);
   if (rc) return rc;
-  // the prepass counters, as is3d_finish reads them (dndx_finish has waited for the stream)
-  unsigned long long cnt[4] = {0, 0, 0, 0};
-  HIPCHK(e, hipMemcpy(cnt, e->d_cnt.get(), sizeof(cnt), hipMemcpyDeviceToHost));
-  e->st.breakdown = (long)cnt[0]; e->st.pl_negative = (long)cnt[1]; e->st.recon_fail = (long)cnt[2]; e->st.iterations = (long)cnt[3];
-  return IS3D_OK;
+  HIPCHK(e, hipEventRecord(e->ev[1].get(), L.st));
+  rc = dndx_finish(e, L.wlo, L.nw, "Error: choose df_mode = (1,2,3,4,5)", dN_taudtaudy, dN_2pirdrdy, dN_dphidy);
+  return rc ? rc : read_counters(e);     // dndx_finish has waited for the stream
 }
 
 extern "C" int is3d_get_cell_yields(const is3d_engine* e, double* dN_dy_cell) {
@@ -1902,10 +1893,10 @@ extern "C" int is3d_launch_polarization(is3d_engine* e, double T_avg, double* de
   const long nw = whi - wlo;
   const int rc = begin_stats(e, nw, st);
   if (rc) return rc;
-  HIPCHK(e, hipEventRecord(e->ev[1], st));     // no prepass: k_polzn reads the surface itself
+  HIPCHK(e, hipEventRecord(e->ev[1].get(), st));     // no prepass: k_polzn reads the surface itself
   if (nw == 0) {
     HIPCHK(e, hipMemsetAsync(dev_out, 0, e->pz.out_size() * sizeof(double), st));
-    HIPCHK(e, hipEventRecord(e->ev[2], st));
+    HIPCHK(e, hipEventRecord(e->ev[2].get(), st));
   } else {
     const is3d::polzn::Plan P = is3d::polzn::make_plan(e->pz, nw, e->max_splits, e->split_bytes, e->slab_bytes);
     if (!P.ok) return e->fail(IS3D_ERR_ARG, "polarization: the phi / y / eta tables do not fit a workgroup's LDS tile");
@@ -1913,9 +1904,9 @@ extern "C" int is3d_launch_polarization(is3d_engine* e, double T_avg, double* de
     e->last_nchunk = 0;
     e->last_nsplit = P.nsplit;
     e->last_nslab = P.nsplit;
-    HIPCHK(e, is3d::polzn::enqueue(e->pz, P, e->d_surf, e->d_vort.get(), n, wlo, whi, T_avg, e->d_slab.get(), dev_out, st, e->ev[2]));
+    HIPCHK(e, is3d::polzn::enqueue(e->pz, P, e->d_surf, e->d_vort.get(), n, wlo, whi, T_avg, e->d_slab.get(), dev_out, st, e->ev[2].get()));
   }
-  HIPCHK(e, hipEventRecord(e->ev[3], st));
+  HIPCHK(e, hipEventRecord(e->ev[3].get(), st));
   e->launched = true;
   return IS3D_OK;
 }
@@ -1925,14 +1916,7 @@ extern "C" int is3d_calculate_polarization(is3d_engine* e, double T_avg, double*
   if (!e || !S_out) return e ? e->fail(IS3D_ERR_ARG, "null output") : IS3D_ERR_ARG;
   const long outsize = is3d_polarization_size(e);
   if (outsize < 0) return e->fail(IS3D_ERR_STATE, "polarization: params, species and momentum grid must be set");
-  HIPCHK(e, hipSetDevice(e->device));
-  if (!e->d_out.reserve(outsize)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(output) failed");
-  int rc = is3d_launch_polarization(e, T_avg, e->d_out.get(), nullptr);
-  if (rc) return rc;
-  rc = is3d_finish(e);
-  if (rc) return rc;
-  HIPCHK(e, hipMemcpy(S_out, e->d_out.get(), outsize * sizeof(double), hipMemcpyDeviceToHost));
-  return IS3D_OK;
+  return calculate(e, outsize, S_out, [&](double* d) { return is3d_launch_polarization(e, T_avg, d, nullptr); });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1993,9 +1977,9 @@ extern "C" int is3d_launch_feeddown(is3d_engine* e, double* dev_inout, void* str
       return e->fail(IS3D_ERR_ARG, "feed-down: a level has more than 2^31 workgroups");
   if (!e->d_dk_log.reserve(is3d_output_size(e))) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(decay logs) failed");
   hipStream_t st = (hipStream_t)stream;
-  HIPCHK(e, hipEventRecord(e->dk_ev[0], st));
+  HIPCHK(e, hipEventRecord(e->dk_ev[0].get(), st));
   HIPCHK(e, is3d::decay::enqueue(e->dk_plan, e->dk_pack, e->d_dk_d.get(), e->d_dk_i.get(), dev_inout, e->d_dk_log.get(), st));
-  HIPCHK(e, hipEventRecord(e->dk_ev[1], st));
+  HIPCHK(e, hipEventRecord(e->dk_ev[1].get(), st));
   e->dk_launched = true;
   return IS3D_OK;
 }
@@ -2145,14 +2129,12 @@ static int sample_any(is3d_engine* e, const is3d_sample_params* sp, const double
   }
   if (famod && c.hi > c.lo) {
     // (lambda, aT, aL) of the cells: the whole surface along the chains, or the window cold (famod_chains = 0)
-    rc = prepass_begin(e, nullptr, 0, -1, 0, 1);
-    for (int pass = 0; !rc && e->lc.chained && pass < e->lc.ca.npass; pass++) rc = chain_pass(e, pass);
-    if (!rc) rc = chain_end(e);
+    rc = run_prepass(e, nullptr, 1, 1);
     if (rc) return rc;
-    unsigned long long cnt[4] = {0, 0, 0, 0};
     HIPCHK(e, hipStreamSynchronize(nullptr));
-    HIPCHK(e, hipMemcpy(cnt, e->d_cnt.get(), sizeof(cnt), hipMemcpyDeviceToHost));
-    e->sfst = is3d_sample_famod_stats{(long)cnt[1], (long)cnt[2], (long)cnt[3]};
+    rc = read_counters(e);
+    if (rc) return rc;
+    e->sfst = is3d_sample_famod_stats{e->st.pl_negative, e->st.recon_fail, e->st.iterations};
     c.sol = e->d_sol.get();
   } else if (famod) {
     e->sfst = is3d_sample_famod_stats{};

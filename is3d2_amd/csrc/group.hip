@@ -19,10 +19,12 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
 
+#include "devbuf.h"
 #include "group.h"
 
 namespace is3d {
@@ -36,14 +38,15 @@ __global__ __launch_bounds__(256) void k_accum(double* __restrict__ out, const d
 struct Group {
   std::vector<is3d_engine*> sh;       // shard engines, one per listed device
   std::vector<int> dev;
-  std::vector<hipStream_t> st;        // shard k > 0 launches on st[k]; shard 0 on the caller's stream
-  std::vector<hipEvent_t> done;       // shard k's work (incl. its reduction step) enqueued up to here
+  // every stream, event and buffer below has one owner (devbuf.h), made and reset with its shard's device current
+  std::vector<DevStream> st;          // shard k > 0 launches on st[k]; shard 0 (st[0] empty) on the caller's stream
+  std::vector<DevEvent> done;         // shard k's work (incl. its reduction step) enqueued up to here
   std::vector<ncclComm_t> comm;       // one communicator per device when every device is distinct
   bool nccl = false;
   std::vector<long> lo, hi;           // cell window of each shard
   bool full = false;                  // every shard holds the whole surface (PTMA warm-start chains)
   std::vector<long> q0, q1;           // full: chain positions of each shard's window (cells [q0 C, q1 C))
-  std::vector<hipEvent_t> evE, evF;   // distributed chains: boundary pushed (E) / pass done (F), per shard
+  std::vector<DevEvent> evE, evF;     // distributed chains: boundary pushed (E) / pass done (F), per shard
   bool dist_chain = false;            // the launch in flight split the chains over the shards
   long ncell = 0;
   is3d_params p{};
@@ -51,12 +54,13 @@ struct Group {
   int np = 0;                         // chosen species
   is3d_spacetime_bins bins{};
   bool have_bins = false;
-  std::vector<double*> buf;           // per-shard output buffers (shard 0: the caller's dev_out)
-  double* scratch = nullptr;          // device-0 staging buffer of the copy reduction
-  long buf_n = 0;
-  double* d_out = nullptr; long out_n = 0;   // group_calculate_spectra's device-0 output
+  std::vector<DevBuf<double>> buf;    // per-shard output buffers; slot 0 stays empty: shard 0 writes ...
+  double* out0 = nullptr;             // ... the caller's dev_out
+  double* out(int k) const { return k ? buf[k].get() : out0; }
+  DevBuf<double> scratch;             // device-0 staging buffer of the copy reduction
+  DevBuf<double> d_out;               // group_calculate_spectra's device-0 output
   hipStream_t cur0 = nullptr;         // shard 0's stream of the launch in flight
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  DevEvent ev0, ev1;                  // timing events on device 0
   bool launched = false;
   bool fd_launched = false;           // group_launch_feeddown: shard 0 alone has work in flight
   is3d_stats stats{};
@@ -87,39 +91,29 @@ static const char* kStaleSplit = "the params changed whether every device needs 
 
 Group* group_create(int n, const int* devices, std::string& err) {
   if (n <= 0 || !devices) { err = "empty device list"; return nullptr; }
-  Group* g = new Group();
+  std::unique_ptr<Group, void (*)(Group*)> g(new Group(), group_destroy);   // an early return destroys what exists
   g->dev.assign(devices, devices + n);
+  g->st.resize(n); g->done.resize(n); g->evE.resize(n); g->evF.resize(n); g->buf.resize(n);
   for (int k = 0; k < n; k++) {
     is3d_engine* e = is3d_create(devices[k]);
     if (!e) {
       err = "is3d_create(" + std::to_string(devices[k]) + ") failed";
-      group_destroy(g);
       return nullptr;
     }
     g->sh.push_back(e);
-    hipStream_t s = nullptr;
-    hipEvent_t ev = nullptr;
-    if (hipSetDevice(devices[k]) != hipSuccess || (k > 0 && hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) ||
-        hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
+    if (hipSetDevice(devices[k]) != hipSuccess || (k > 0 && g->st[k].create(hipStreamNonBlocking) != hipSuccess) ||
+        g->done[k].create(hipEventDisableTiming) != hipSuccess) {
       err = "stream / event creation failed on device " + std::to_string(devices[k]);
-      group_destroy(g);
       return nullptr;
     }
-    g->st.push_back(s);
-    g->done.push_back(ev);
-    hipEvent_t e1 = nullptr, e2 = nullptr;
-    if (hipEventCreateWithFlags(&e1, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&e2, hipEventDisableTiming) != hipSuccess) {
+    if (g->evE[k].create(hipEventDisableTiming) != hipSuccess || g->evF[k].create(hipEventDisableTiming) != hipSuccess) {
       err = "event creation failed on device " + std::to_string(devices[k]);
-      group_destroy(g);
       return nullptr;
     }
-    g->evE.push_back(e1);
-    g->evF.push_back(e2);
   }
   (void)hipSetDevice(devices[0]);
-  (void)hipEventCreate(&g->ev0);
-  (void)hipEventCreate(&g->ev1);
+  (void)g->ev0.create(hipEventDefault);
+  (void)g->ev1.create(hipEventDefault);
   // RCCL needs distinct devices (one rank per GPU); IS3D_REDUCE=copy forces the copy reduction, and
   // IS3D_REDUCE=rccl also takes RCCL for a single device (a one-rank communicator: exercises the path)
   const char* mode = std::getenv("IS3D_REDUCE");
@@ -132,30 +126,26 @@ Group* group_create(int n, const int* devices, std::string& err) {
     g->nccl = ncclCommInitAll(g->comm.data(), n, devices) == ncclSuccess;
     if (!g->nccl) g->comm.clear();
   }
-  return g;
+  return g.release();
 }
 
+// Every shard's owners are reset here while that shard's device is current; their destructors (with *g) are only the
+// safety net of a path that returns early.
 void group_destroy(Group* g) {
   if (!g) return;
   for (size_t k = 0; k < g->sh.size(); k++) {
     (void)hipSetDevice(g->dev[k]);
     (void)hipDeviceSynchronize();
-    if (k > 0 && k < g->buf.size() && g->buf[k]) (void)hipFree(g->buf[k]);
+    g->buf[k].reset();
   }
   for (auto c : g->comm) if (c) ncclCommDestroy(c);
-  for (size_t k = 0; k < g->st.size(); k++) {
+  for (size_t k = 0; k < g->sh.size(); k++) {     // a shard's owners are made after its engine
     (void)hipSetDevice(g->dev[k]);
-    if (g->st[k]) (void)hipStreamDestroy(g->st[k]);
-    if (g->done[k]) (void)hipEventDestroy(g->done[k]);
-    if (k < g->evE.size() && g->evE[k]) (void)hipEventDestroy(g->evE[k]);
-    if (k < g->evF.size() && g->evF[k]) (void)hipEventDestroy(g->evF[k]);
+    g->st[k].reset(); g->done[k].reset(); g->evE[k].reset(); g->evF[k].reset();
   }
   if (!g->dev.empty()) {
     (void)hipSetDevice(g->dev[0]);
-    if (g->scratch) (void)hipFree(g->scratch);
-    if (g->d_out) (void)hipFree(g->d_out);
-    if (g->ev0) (void)hipEventDestroy(g->ev0);
-    if (g->ev1) (void)hipEventDestroy(g->ev1);
+    g->scratch.reset(); g->d_out.reset(); g->ev0.reset(); g->ev1.reset();
   }
   for (auto* e : g->sh) is3d_destroy(e);
   delete g;
@@ -355,7 +345,7 @@ static int launch_split_chains(Group* g, S stream_of) {
   const int K = (int)g->sh.size();
   std::vector<int> act;                 // shards with chain positions, in order
   for (int k = 0; k < K; k++) {
-    const int rc = is3d_internal_launch_begin(g->sh[k], g->buf[k], (void*)stream_of(k), g->q0[k], g->q1[k],
+    const int rc = is3d_internal_launch_begin(g->sh[k], g->out(k), (void*)stream_of(k), g->q0[k], g->q1[k],
                                               act.empty() ? 0 : 1);
     if (rc) return g->shard_fail(k, rc);
     if (g->q1[k] > g->q0[k]) act.push_back(k);
@@ -367,31 +357,31 @@ static int launch_split_chains(Group* g, S stream_of) {
     for (int i = na - 1; i >= 0; i--) {
       const int k = act[i], kp = i ? act[i - 1] : -1, kn = i + 1 < na ? act[i + 1] : -1;
       if (hipSetDevice(g->dev[k]) != hipSuccess) return bad("hipSetDevice");
-      if (kp >= 0 && j > 0 && hipStreamWaitEvent(stream_of(k), g->evE[kp], 0) != hipSuccess) return bad("wait");
+      if (kp >= 0 && j > 0 && hipStreamWaitEvent(stream_of(k), g->evE[kp].get(), 0) != hipSuccess) return bad("wait");
       const int rc = is3d_internal_chain_pass(g->sh[k], j);
       if (rc) return g->shard_fail(k, rc);
-      if (hipEventRecord(g->evF[k], stream_of(k)) != hipSuccess) return bad("record");
+      if (hipEventRecord(g->evF[k].get(), stream_of(k)) != hipSuccess) return bad("record");
       if (kn >= 0) {
-        if (hipStreamWaitEvent(stream_of(k), g->evF[kn], 0) != hipSuccess) return bad("wait");
+        if (hipStreamWaitEvent(stream_of(k), g->evF[kn].get(), 0) != hipSuccess) return bad("wait");
         if (hipMemcpyPeerAsync(is3d_internal_chain_bnd(g->sh[kn], 0, j & 1), g->dev[kn],
                                is3d_internal_chain_bnd(g->sh[k], 1, j & 1), g->dev[k],
                                is3d_internal_chain_bnd_bytes(g->sh[k]), stream_of(k)) != hipSuccess)
           return bad("hipMemcpyPeerAsync");
-        if (hipEventRecord(g->evE[k], stream_of(k)) != hipSuccess) return bad("record");
+        if (hipEventRecord(g->evE[k].get(), stream_of(k)) != hipSuccess) return bad("record");
       }
     }
   }
   for (int i = 0; i < na; i++) {
     const int k = act[i], kp = i ? act[i - 1] : -1, kn = i + 1 < na ? act[i + 1] : -1;
     if (hipSetDevice(g->dev[k]) != hipSuccess) return bad("hipSetDevice");
-    if (kp >= 0 && hipStreamWaitEvent(stream_of(k), g->evE[kp], 0) != hipSuccess) return bad("wait");
+    if (kp >= 0 && hipStreamWaitEvent(stream_of(k), g->evE[kp].get(), 0) != hipSuccess) return bad("wait");
     const int rc = is3d_internal_chain_end(g->sh[k]);
     if (rc) return g->shard_fail(k, rc);
     if (kn >= 0) {
       if (hipMemcpyPeerAsync(is3d_internal_chain_bnd(g->sh[kn], 0, 2), g->dev[kn], is3d_internal_chain_bnd(g->sh[k], 1, 2),
                              g->dev[k], is3d_internal_chain_bnd_bytes(g->sh[k]), stream_of(k)) != hipSuccess)
         return bad("hipMemcpyPeerAsync");
-      if (hipEventRecord(g->evE[k], stream_of(k)) != hipSuccess) return bad("record");
+      if (hipEventRecord(g->evE[k].get(), stream_of(k)) != hipSuccess) return bad("record");
     }
   }
   for (int k = 0; k < K; k++) {
@@ -409,35 +399,29 @@ static int launch_shards(Group* g, double* dev_out, void* stream, bool polzn, do
   const int K = (int)g->sh.size();
   const long out_n = (polzn ? 5 : 1) * group_output_size(g);
   if (out_n <= 0) return g->fail(IS3D_ERR_STATE, "species / grids / params not set");
-  if ((int)g->buf.size() != K || g->buf_n < out_n) {
-    for (int k = 1; k < (int)g->buf.size(); k++) if (g->buf[k]) { (void)hipSetDevice(g->dev[k]); (void)hipFree(g->buf[k]); }
-    g->buf.assign(K, nullptr);
-    for (int k = 1; k < K; k++) {
-      if (hipSetDevice(g->dev[k]) != hipSuccess || hipMalloc(&g->buf[k], out_n * sizeof(double)) != hipSuccess)
-        return g->fail(IS3D_ERR_DEVICE, "hipMalloc(shard output) failed");
-    }
-    if (!g->nccl && K > 1) {
-      (void)hipSetDevice(g->dev[0]);
-      if (g->scratch) (void)hipFree(g->scratch);
-      if (hipMalloc(&g->scratch, out_n * sizeof(double)) != hipSuccess) return g->fail(IS3D_ERR_DEVICE, "hipMalloc(scratch) failed");
-    }
-    g->buf_n = out_n;
+  for (int k = 1; k < K; k++) {
+    if (hipSetDevice(g->dev[k]) != hipSuccess || !g->buf[k].reserve(out_n))
+      return g->fail(IS3D_ERR_DEVICE, "hipMalloc(shard output) failed");
   }
-  g->buf[0] = dev_out;
+  if (!g->nccl && K > 1) {
+    (void)hipSetDevice(g->dev[0]);
+    if (!g->scratch.reserve(out_n)) return g->fail(IS3D_ERR_DEVICE, "hipMalloc(scratch) failed");
+  }
+  g->out0 = dev_out;
   g->cur0 = (hipStream_t)stream;
   (void)hipSetDevice(g->dev[0]);
-  if (hipEventRecord(g->ev0, g->cur0) != hipSuccess) return g->fail(IS3D_ERR_DEVICE, "hipEventRecord failed");
-  auto stream_of = [&](int k) { return k ? g->st[k] : g->cur0; };
+  if (hipEventRecord(g->ev0.get(), g->cur0) != hipSuccess) return g->fail(IS3D_ERR_DEVICE, "hipEventRecord failed");
+  auto stream_of = [&](int k) { return k ? g->st[k].get() : g->cur0; };
   const char* dc = std::getenv("IS3D_CHAIN_DIST");
   g->dist_chain = !polzn && g->full && K > 1 && !(dc && !std::strcmp(dc, "0"));
   if (polzn) {
     for (int k = 0; k < K; k++) {
-      const int rc = is3d_launch_polarization(g->sh[k], T_avg, g->buf[k], k ? (void*)g->st[k] : stream);
+      const int rc = is3d_launch_polarization(g->sh[k], T_avg, g->out(k), (void*)stream_of(k));
       if (rc) return g->shard_fail(k, rc);
     }
   } else if (!g->dist_chain) {
     for (int k = 0; k < K; k++) {
-      const int rc = is3d_launch(g->sh[k], g->buf[k], k ? (void*)g->st[k] : stream);
+      const int rc = is3d_launch(g->sh[k], g->out(k), (void*)stream_of(k));
       if (rc) return g->shard_fail(k, rc);
     }
   } else {
@@ -447,7 +431,7 @@ static int launch_shards(Group* g, double* dev_out, void* stream, bool polzn, do
   if (g->nccl) {
     if (ncclGroupStart() != ncclSuccess) return g->fail(IS3D_ERR_DEVICE, "ncclGroupStart failed");
     for (int k = 0; k < K; k++) {
-      if (ncclAllReduce(g->buf[k], g->buf[k], (size_t)out_n, ncclFloat64, ncclSum, g->comm[k], stream_of(k)) != ncclSuccess) {
+      if (ncclAllReduce(g->out(k), g->out(k), (size_t)out_n, ncclFloat64, ncclSum, g->comm[k], stream_of(k)) != ncclSuccess) {
         ncclGroupEnd();
         return g->fail(IS3D_ERR_DEVICE, "ncclAllReduce failed");
       }
@@ -459,25 +443,25 @@ static int launch_shards(Group* g, double* dev_out, void* stream, bool polzn, do
     const unsigned nb = (unsigned)std::min<long>((out_n + 255) / 256, 8192);
     for (int k = 1; k < K; k++) {
       (void)hipSetDevice(g->dev[k]);
-      if (hipEventRecord(g->done[k], g->st[k]) != hipSuccess) return g->fail(IS3D_ERR_DEVICE, "hipEventRecord failed");
+      if (hipEventRecord(g->done[k].get(), g->st[k].get()) != hipSuccess) return g->fail(IS3D_ERR_DEVICE, "hipEventRecord failed");
       (void)hipSetDevice(g->dev[0]);
-      if (hipStreamWaitEvent(g->cur0, g->done[k], 0) != hipSuccess) return g->fail(IS3D_ERR_DEVICE, "hipStreamWaitEvent failed");
-      const double* src = g->buf[k];
+      if (hipStreamWaitEvent(g->cur0, g->done[k].get(), 0) != hipSuccess) return g->fail(IS3D_ERR_DEVICE, "hipStreamWaitEvent failed");
+      const double* src = g->buf[k].get();
       if (g->dev[k] != g->dev[0]) {
-        if (hipMemcpyPeerAsync(g->scratch, g->dev[0], g->buf[k], g->dev[k], out_n * sizeof(double), g->cur0) != hipSuccess)
+        if (hipMemcpyPeerAsync(g->scratch.get(), g->dev[0], g->buf[k].get(), g->dev[k], out_n * sizeof(double), g->cur0) != hipSuccess)
           return g->fail(IS3D_ERR_DEVICE, "hipMemcpyPeerAsync failed");
-        src = g->scratch;
+        src = g->scratch.get();
       }
-      hipLaunchKernelGGL(k_accum, dim3(nb), dim3(256), 0, g->cur0, g->buf[0], src, out_n);
+      hipLaunchKernelGGL(k_accum, dim3(nb), dim3(256), 0, g->cur0, g->out0, src, out_n);
       if (hipGetLastError() != hipSuccess) return g->fail(IS3D_ERR_DEVICE, "k_accum launch failed");
     }
   }
   for (int k = 1; k < K; k++) {     // shard k's stream (nccl: its all-reduce step) enqueued up to here
     (void)hipSetDevice(g->dev[k]);
-    if (hipEventRecord(g->done[k], g->st[k]) != hipSuccess) return g->fail(IS3D_ERR_DEVICE, "hipEventRecord failed");
+    if (hipEventRecord(g->done[k].get(), g->st[k].get()) != hipSuccess) return g->fail(IS3D_ERR_DEVICE, "hipEventRecord failed");
   }
   (void)hipSetDevice(g->dev[0]);
-  if (hipEventRecord(g->ev1, g->cur0) != hipSuccess) return g->fail(IS3D_ERR_DEVICE, "hipEventRecord failed");
+  if (hipEventRecord(g->ev1.get(), g->cur0) != hipSuccess) return g->fail(IS3D_ERR_DEVICE, "hipEventRecord failed");
   g->launched = true;
   return IS3D_OK;
 }
@@ -535,7 +519,7 @@ int group_finish(Group* g) {
     const int rc = is3d_finish(g->sh[k]);
     if (rc && !first) { first = rc; first_k = k; }
     (void)hipSetDevice(g->dev[k]);
-    if (k > 0) (void)hipEventSynchronize(g->done[k]);
+    if (k > 0) (void)hipEventSynchronize(g->done[k].get());
     is3d_stats s{};
     is3d_get_stats(g->sh[k], &s);
     agg.cells += s.cells; agg.breakdown += s.breakdown; agg.pl_negative += s.pl_negative;
@@ -544,9 +528,9 @@ int group_finish(Group* g) {
     agg.ms_spectra = std::max(agg.ms_spectra, s.ms_spectra);
   }
   (void)hipSetDevice(g->dev[0]);
-  if (hipEventSynchronize(g->ev1) != hipSuccess) return g->fail(IS3D_ERR_DEVICE, "group synchronisation failed");
+  if (hipEventSynchronize(g->ev1.get()) != hipSuccess) return g->fail(IS3D_ERR_DEVICE, "group synchronisation failed");
   float ms = 0.f;
-  if (hipEventElapsedTime(&ms, g->ev0, g->ev1) == hipSuccess) agg.ms_total = ms;
+  if (hipEventElapsedTime(&ms, g->ev0.get(), g->ev1.get()) == hipSuccess) agg.ms_total = ms;
   if (g->full && !g->dist_chain) {
     // every shard walked the whole PTMA chain and prepared every cell: count that work once (shard 0's, the
     // same solves everywhere)
@@ -567,18 +551,12 @@ static int calculate(Group* g, bool polzn, double T_avg, double* out) {
   const long n = (polzn ? 5 : 1) * group_output_size(g);
   if (n <= 0) return g->fail(IS3D_ERR_STATE, "species / grids / params not set");
   (void)hipSetDevice(g->dev[0]);
-  if (g->out_n < n) {
-    if (g->d_out) (void)hipFree(g->d_out);
-    g->d_out = nullptr;
-    g->out_n = 0;
-    if (hipMalloc(&g->d_out, n * sizeof(double)) != hipSuccess) return g->fail(IS3D_ERR_DEVICE, "hipMalloc(output) failed");
-    g->out_n = n;
-  }
-  int rc = launch_shards(g, g->d_out, nullptr, polzn, T_avg);
+  if (!g->d_out.reserve(n)) return g->fail(IS3D_ERR_DEVICE, "hipMalloc(output) failed");
+  int rc = launch_shards(g, g->d_out.get(), nullptr, polzn, T_avg);
   if (!rc) rc = group_finish(g);
   if (rc) return rc;
   (void)hipSetDevice(g->dev[0]);
-  if (hipMemcpy(out, g->d_out, n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+  if (hipMemcpy(out, g->d_out.get(), n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
     return g->fail(IS3D_ERR_DEVICE, polzn ? "polarization download failed" : "spectra download failed");
   return IS3D_OK;
 }

@@ -9,13 +9,15 @@
 #include <string>
 #include <vector>
 
+#include "devbuf.h"
+
 namespace is3d {
 namespace polzn {
 
 // device constants of one (species, classes, grid, dimension) setup: one blob of doubles, one of ints
 struct Tables {
-  double* d = nullptr;
-  int* i = nullptr;
+  DevBuf<double> d;                // the blobs the views below point into (move-only)
+  DevBuf<int> i;
   int npart = 0, ncls = 0, npT = 0, nphi = 0, nq = 0, ny_out = 0, dim3d = 0;
   const double *cmass = nullptr, *csign = nullptr, *pT = nullptr, *cphi = nullptr, *sphi = nullptr, *qv = nullptr, *qw = nullptr;
   const int *cmem_off = nullptr, *cmem = nullptr;   // members (original species indices) of each class
@@ -29,7 +31,6 @@ struct Tables {
 std::string tables_build(Tables& t, int dimension, bool classes, const std::vector<double>& mass,
                          const std::vector<double>& sign, const std::vector<double>& pT, const std::vector<double>& phi,
                          const std::vector<double>& y, const std::vector<double>& eta, const std::vector<double>& eta_w);
-void tables_free(Tables& t);
 
 // launch plan of nw cells: a workgroup owns one pT and one cell range (split); each split writes its own partial
 // slab, summed by k_polzn_reduce in split order (no atomics: bit-reproducible)

@@ -153,16 +153,10 @@ __global__ __launch_bounds__(kWg) void k_polzn_reduce(RedArgs A) {
 
 }  // namespace
 
-void tables_free(Tables& t) {
-  if (t.d) (void)hipFree(t.d);
-  if (t.i) (void)hipFree(t.i);
-  t = Tables{};
-}
-
 std::string tables_build(Tables& t, int dimension, bool classes, const std::vector<double>& mass,
                          const std::vector<double>& sign, const std::vector<double>& pT, const std::vector<double>& phi,
                          const std::vector<double>& y, const std::vector<double>& eta, const std::vector<double>& eta_w) {
-  tables_free(t);
+  t = Tables{};
   const int np = (int)mass.size();
   if (np <= 0 || pT.empty() || phi.empty()) return "species / pT / phi tables are empty";
   std::vector<double> qv, qw;
@@ -197,17 +191,18 @@ std::string tables_build(Tables& t, int dimension, bool classes, const std::vect
   hi.push_back(0);
   for (int c = 0; c < nc; c++) hi.push_back(hi.back() + (int)mem[c].size());
   for (int c = 0; c < nc; c++) hi.insert(hi.end(), mem[c].begin(), mem[c].end());
-  if (hipMalloc((void**)&t.d, hd.size() * sizeof(double)) != hipSuccess || hipMalloc((void**)&t.i, hi.size() * sizeof(int)) != hipSuccess ||
-      hipMemcpy(t.d, hd.data(), hd.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(t.i, hi.data(), hi.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
-    tables_free(t);
+  if (!t.d.reserve((long)hd.size()) || !t.i.reserve((long)hi.size()) ||
+      hipMemcpy(t.d.get(), hd.data(), hd.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(t.i.get(), hi.data(), hi.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
+    t = Tables{};
     return "hipMalloc / upload of the polarization tables failed";
   }
   t.npart = np; t.ncls = nc; t.npT = npT; t.nphi = nphi; t.nq = nq; t.dim3d = dimension == 3;
   t.ny_out = dimension == 3 ? nq : 1;
-  t.cmass = t.d + o_m; t.csign = t.d + o_s; t.pT = t.d + o_pT; t.cphi = t.d + o_c; t.sphi = t.d + o_sn;
-  t.qv = t.d + o_qv; t.qw = t.d + o_qw;
-  t.cmem_off = t.i; t.cmem = t.i + nc + 1;
+  const double* d = t.d.get();
+  t.cmass = d + o_m; t.csign = d + o_s; t.pT = d + o_pT; t.cphi = d + o_c; t.sphi = d + o_sn;
+  t.qv = d + o_qv; t.qw = d + o_qw;
+  t.cmem_off = t.i.get(); t.cmem = t.i.get() + nc + 1;
   return "";
 }
 

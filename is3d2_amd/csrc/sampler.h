@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "devbuf.h"
 #include "sampler_bins.h"
 #include "sampler_math.h"
 
@@ -19,13 +20,12 @@ namespace sampler {
 
 // chosen species in their original order (the species draw follows the reference's discrete_distribution order)
 struct Tables {
-  double* d = nullptr;
+  DevBuf<double> d;                // the blob the views below point into (move-only)
   int npart = 0;
   const double *mass = nullptr, *sign = nullptr, *degen = nullptr, *baryon = nullptr;
 };
 std::string tables_build(Tables& t, const std::vector<double>& mass, const std::vector<double>& sign,
                          const std::vector<double>& degen, const std::vector<double>& baryon);
-void tables_free(Tables& t);
 
 struct Config {
   Run run;

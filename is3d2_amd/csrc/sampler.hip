@@ -238,88 +238,57 @@ struct ToLong {
 };
 
 // exclusive sum of in[0 .. n) (ints) into out (longs); in[n - 1] is the caller's trailing zero, so out[n - 1] = total
-hipError_t scan(const int* in, long* out, long n, void*& tmp, size_t& tmp_cap) {
+hipError_t scan(const int* in, long* out, long n, DevBuf<char>& tmp) {
   hipcub::TransformInputIterator<long, ToLong, const int*> it(in, ToLong());
   size_t need = 0;
   hipError_t h = hipcub::DeviceScan::ExclusiveSum(nullptr, need, it, out, (int)n, (hipStream_t) nullptr);
   if (h != hipSuccess) return h;
-  if (need > tmp_cap) {
-    if (tmp) (void)hipFree(tmp);
-    tmp = nullptr; tmp_cap = 0;
-    if ((h = hipMalloc(&tmp, need)) != hipSuccess) return h;
-    tmp_cap = need;
-  }
-  return hipcub::DeviceScan::ExclusiveSum(tmp, need, it, out, (int)n, (hipStream_t) nullptr);
+  if (!tmp.reserve((long)need)) return hipErrorOutOfMemory;
+  return hipcub::DeviceScan::ExclusiveSum(tmp.get(), need, it, out, (int)n, (hipStream_t) nullptr);
 }
+
+hipError_t alloc(bool ok) { return ok ? hipSuccess : hipErrorOutOfMemory; }
 
 // working buffers of a call, grown on demand and freed when it ends
 struct Buffers {
-  Cell* cells = nullptr; double* dn = nullptr; int* err = nullptr; unsigned long long* tally = nullptr;
-  int* counts = nullptr; long* slots = nullptr; long pair_cap = 0;
-  Particle* cand = nullptr; Particle* out = nullptr; int* flags = nullptr; long* pos = nullptr; long cand_cap = 0;
-  void* tmp = nullptr; size_t tmp_cap = 0;
-  ~Buffers() {
-    for (void* p : {(void*)cells, (void*)dn, (void*)err, (void*)tally, (void*)counts, (void*)slots, (void*)cand, (void*)out,
-                    (void*)flags, (void*)pos, tmp})
-      if (p) (void)hipFree(p);
-  }
-  hipError_t pairs(long n) {
-    if (n <= pair_cap) return hipSuccess;
-    if (counts) (void)hipFree(counts);
-    if (slots) (void)hipFree(slots);
-    counts = nullptr; slots = nullptr; pair_cap = 0;
-    hipError_t h = hipMalloc((void**)&counts, n * sizeof(int));
-    if (h == hipSuccess) h = hipMalloc((void**)&slots, n * sizeof(long));
-    if (h == hipSuccess) pair_cap = n;
-    return h;
-  }
-  hipError_t cands(long n) {
-    if (n <= cand_cap) return hipSuccess;
-    for (void* p : {(void*)cand, (void*)out, (void*)flags, (void*)pos})
-      if (p) (void)hipFree(p);
-    cand = out = nullptr; flags = nullptr; pos = nullptr; cand_cap = 0;
-    hipError_t h = hipMalloc((void**)&cand, n * sizeof(Particle));
-    if (h == hipSuccess) h = hipMalloc((void**)&out, n * sizeof(Particle));
-    if (h == hipSuccess) h = hipMalloc((void**)&flags, n * sizeof(int));
-    if (h == hipSuccess) h = hipMalloc((void**)&pos, n * sizeof(long));
-    if (h == hipSuccess) cand_cap = n;
-    return h;
-  }
+  DevBuf<Cell> cells;
+  DevBuf<double> dn;
+  DevBuf<int> err, counts, flags;
+  DevBuf<unsigned long long> tally;
+  DevBuf<long> slots, pos;
+  DevBuf<Particle> cand, out;
+  DevBuf<char> tmp;     // the scans' scratch
+  hipError_t pairs(long n) { return alloc(counts.reserve(n) && slots.reserve(n)); }
+  hipError_t cands(long n) { return alloc(cand.reserve(n) && out.reserve(n) && flags.reserve(n) && pos.reserve(n)); }
 };
 
 }  // namespace
 
-void tables_free(Tables& t) {
-  if (t.d) (void)hipFree(t.d);
-  t = Tables{};
-}
-
 std::string tables_build(Tables& t, const std::vector<double>& mass, const std::vector<double>& sign,
                          const std::vector<double>& degen, const std::vector<double>& baryon) {
-  tables_free(t);
+  t = Tables{};
   const size_t np = mass.size();
   if (np == 0 || sign.size() != np || degen.size() != np || baryon.size() != np) return "species tables are empty";
   std::vector<double> h;
   for (const auto* v : {&mass, &sign, &degen, &baryon}) h.insert(h.end(), v->begin(), v->end());
-  if (hipMalloc((void**)&t.d, h.size() * sizeof(double)) != hipSuccess ||
-      hipMemcpy(t.d, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
-    tables_free(t);
+  if (!t.d.reserve((long)h.size()) ||
+      hipMemcpy(t.d.get(), h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
+    t = Tables{};
     return "hipMalloc / upload of the sampler's species tables failed";
   }
   t.npart = (int)np;
-  t.mass = t.d; t.sign = t.d + np; t.degen = t.d + 2 * np; t.baryon = t.d + 3 * np;
+  const double* d = t.d.get();
+  t.mass = d; t.sign = d + np; t.degen = d + 2 * np; t.baryon = d + 3 * np;
   return "";
 }
 
 hipError_t uniforms(uint64_t seed, int purpose, long cell, long event, long candidate, int n, double* host_out) {
-  double* d = nullptr;
-  hipError_t h = hipMalloc((void**)&d, (size_t)std::max(n, 1) * sizeof(double));
-  if (h != hipSuccess) return h;
-  hipLaunchKernelGGL(k_uniforms, dim3(1), dim3(1), 0, 0, (unsigned long long)seed, purpose, cell, event, candidate, n, d);
-  h = hipGetLastError();
+  DevBuf<double> d;
+  if (!d.reserve(n)) return hipErrorOutOfMemory;
+  hipLaunchKernelGGL(k_uniforms, dim3(1), dim3(1), 0, 0, (unsigned long long)seed, purpose, cell, event, candidate, n, d.get());
+  hipError_t h = hipGetLastError();
   if (h == hipSuccess) h = hipDeviceSynchronize();
-  if (h == hipSuccess && n > 0) h = hipMemcpy(host_out, d, (size_t)n * sizeof(double), hipMemcpyDeviceToHost);
-  (void)hipFree(d);
+  if (h == hipSuccess && n > 0) h = hipMemcpy(host_out, d.get(), (size_t)n * sizeof(double), hipMemcpyDeviceToHost);
   return h;
 }
 
@@ -340,23 +309,20 @@ int run(const Tables& t, const Config& c, std::vector<Particle>& parts, std::vec
     if (h_ != hipSuccess) { msg = std::string(#x) + ": " + hipGetErrorString(h_); return S_DEVICE; } \
   } while (0)
   Buffers B;
-  SCHK(hipMalloc((void**)&B.cells, nw * sizeof(Cell)));
-  SCHK(hipMalloc((void**)&B.dn, nw * sizeof(double)));
-  SCHK(hipMalloc((void**)&B.err, sizeof(int)));
-  SCHK(hipMalloc((void**)&B.tally, 8 * sizeof(unsigned long long)));
-  SCHK(hipMemset(B.err, 0, sizeof(int)));
-  SCHK(hipMemset(B.tally, 0, 8 * sizeof(unsigned long long)));
+  SCHK(alloc(B.cells.reserve(nw) && B.dn.reserve(nw) && B.err.reserve(1) && B.tally.reserve(8)));
+  SCHK(hipMemset(B.err.get(), 0, sizeof(int)));
+  SCHK(hipMemset(B.tally.get(), 0, 8 * sizeof(unsigned long long)));
   Args A{};
   A.run = c.run; A.tb = c.tb; A.surf = c.surf; A.sol = c.sol; A.n = c.n; A.lo = c.lo; A.hi = c.hi; A.cell_base = c.cell_base;
   A.seed = c.seed; A.mass = t.mass; A.sign = t.sign; A.degen = t.degen; A.baryon = t.baryon; A.dens = c.dens;
-  A.npart = t.npart; A.cells = B.cells; A.dn = B.dn; A.err = B.err; A.tally = B.tally;
+  A.npart = t.npart; A.cells = B.cells.get(); A.dn = B.dn.get(); A.err = B.err.get(); A.tally = B.tally.get();
   const bool famod = c.sol != nullptr;
   if (famod) hipLaunchKernelGGL(k_cells<true>, dim3((unsigned)nw), dim3(kWave), lds, 0, A);
   else hipLaunchKernelGGL(k_cells<false>, dim3((unsigned)nw), dim3(kWave), lds, 0, A);
   SCHK(hipGetLastError());
   std::vector<double> dn((size_t)nw);
-  SCHK(hipMemcpy(dn.data(), B.dn, nw * sizeof(double), hipMemcpyDeviceToHost));
-  SCHK(hipMemcpy(&df_err, B.err, sizeof(int), hipMemcpyDeviceToHost));
+  SCHK(hipMemcpy(dn.data(), B.dn.get(), nw * sizeof(double), hipMemcpyDeviceToHost));
+  SCHK(hipMemcpy(&df_err, B.err.get(), sizeof(int), hipMemcpyDeviceToHost));
   if (df_err) return S_DF;
   // expected candidates of one event over cells [0, i): the batch planner's estimate
   std::vector<double> acc((size_t)nw + 1, 0.0);
@@ -374,7 +340,7 @@ int run(const Tables& t, const Config& c, std::vector<Particle>& parts, std::vec
       if (a == 0 && nw <= max_pairs) { nev = std::min(c.n_events - e0, max_pairs / nw); b = nw; }
       const long ncb = b - a, np = nev * ncb;
       SCHK(B.pairs(np));
-      A.e0 = e0; A.nev = nev; A.c0 = c.lo + a; A.c1 = c.lo + b; A.counts = B.counts; A.slots = B.slots;
+      A.e0 = e0; A.nev = nev; A.c0 = c.lo + a; A.c1 = c.lo + b; A.counts = B.counts.get(); A.slots = B.slots.get();
       hipLaunchKernelGGL(k_count, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, 0, A);
       SCHK(hipGetLastError());
       if (famod) hipLaunchKernelGGL((k_sample<false, true, true>), dim3((unsigned)ncb), dim3(kWave), lds, 0, A);
@@ -406,12 +372,12 @@ int run(const Tables& t, const Config& c, std::vector<Particle>& parts, std::vec
       long total = 0;
       if (!too_big) {
         SCHK(B.pairs(np));
-        A.e0 = e0; A.nev = nev; A.c0 = c.lo + a; A.c1 = c.lo + b; A.counts = B.counts; A.slots = B.slots;
-        SCHK(hipMemsetAsync(B.counts + (np - 1), 0, sizeof(int), 0));
+        A.e0 = e0; A.nev = nev; A.c0 = c.lo + a; A.c1 = c.lo + b; A.counts = B.counts.get(); A.slots = B.slots.get();
+        SCHK(hipMemsetAsync(B.counts.get() + (np - 1), 0, sizeof(int), 0));
         hipLaunchKernelGGL(k_count, dim3((unsigned)((np - 1 + 255) / 256)), dim3(256), 0, 0, A);
         SCHK(hipGetLastError());
-        SCHK(scan(B.counts, B.slots, np, B.tmp, B.tmp_cap));
-        SCHK(hipMemcpy(&total, B.slots + (np - 1), sizeof(long), hipMemcpyDeviceToHost));
+        SCHK(scan(B.counts.get(), B.slots.get(), np, B.tmp));
+        SCHK(hipMemcpy(&total, B.slots.get() + (np - 1), sizeof(long), hipMemcpyDeviceToHost));
         too_big = total + 1 >= 0x7fffffffL || (double)(np - 1) * kPairBytes + (double)total * kCandBytes > (double)budget;
       }
       if (too_big) {
@@ -426,22 +392,22 @@ int run(const Tables& t, const Config& c, std::vector<Particle>& parts, std::vec
       st.candidates += total;
       if (total > 0) {
         SCHK(B.cands(total + 1));
-        A.cand = B.cand; A.flags = B.flags;
-        SCHK(hipMemsetAsync(B.flags + total, 0, sizeof(int), 0));
+        A.cand = B.cand.get(); A.flags = B.flags.get();
+        SCHK(hipMemsetAsync(B.flags.get() + total, 0, sizeof(int), 0));
         if (famod && c.bins) hipLaunchKernelGGL((k_sample<true, true, true>), dim3((unsigned)ncb), dim3(kWave), lds, 0, A);
         else if (famod) hipLaunchKernelGGL((k_sample<true, false, true>), dim3((unsigned)ncb), dim3(kWave), lds, 0, A);
         else if (c.bins) hipLaunchKernelGGL((k_sample<true, true>), dim3((unsigned)ncb), dim3(kWave), lds, 0, A);
         else hipLaunchKernelGGL((k_sample<true, false>), dim3((unsigned)ncb), dim3(kWave), lds, 0, A);
         SCHK(hipGetLastError());
-        SCHK(scan(B.flags, B.pos, total + 1, B.tmp, B.tmp_cap));
+        SCHK(scan(B.flags.get(), B.pos.get(), total + 1, B.tmp));
         long kept = 0;
-        SCHK(hipMemcpy(&kept, B.pos + total, sizeof(long), hipMemcpyDeviceToHost));
+        SCHK(hipMemcpy(&kept, B.pos.get() + total, sizeof(long), hipMemcpyDeviceToHost));
         if (kept > 0) {
-          hipLaunchKernelGGL(k_compact, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, 0, B.cand, B.flags, B.pos, total, B.out);
+          hipLaunchKernelGGL(k_compact, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, 0, B.cand.get(), B.flags.get(), B.pos.get(), total, B.out.get());
           SCHK(hipGetLastError());
           const size_t at = parts.size();
           parts.resize(at + (size_t)kept);
-          SCHK(hipMemcpy(parts.data() + at, B.out, (size_t)kept * sizeof(Particle), hipMemcpyDeviceToHost));
+          SCHK(hipMemcpy(parts.data() + at, B.out.get(), (size_t)kept * sizeof(Particle), hipMemcpyDeviceToHost));
         }
       }
       break;
@@ -450,7 +416,7 @@ int run(const Tables& t, const Config& c, std::vector<Particle>& parts, std::vec
   }
 #undef SCHK
   unsigned long long tally[8] = {0};
-  if (hipMemcpy(tally, B.tally, sizeof(tally), hipMemcpyDeviceToHost) != hipSuccess) { msg = "reading the sampler tallies failed"; return S_DEVICE; }
+  if (hipMemcpy(tally, B.tally.get(), sizeof(tally), hipMemcpyDeviceToHost) != hipSuccess) { msg = "reading the sampler tallies failed"; return S_DEVICE; }
   st.breakdown = (long)tally[0]; st.proposals = (long)tally[1]; st.acceptances = (long)tally[2];
   st.capped = (long)(tally[3] + tally[5]); st.clamped = (long)tally[4];
   st.kept = (long)parts.size();

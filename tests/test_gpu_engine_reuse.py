@@ -1,5 +1,5 @@
-"""GPU tier: one engine used again and again.  Every device buffer of the engine has one owner (csrc/devbuf.h) that
-grows it on demand and keeps it otherwise, and the entry points share their host sequences (the launch prologue, the
+"""GPU tier: one engine used again and again.  Every device buffer, stream and event in csrc -- the engine's, the
+sampler's, the device group's -- has one owner (csrc/devbuf.h) that makes it on demand and keeps it otherwise, and the entry points share their host sequences (the launch prologue, the
 prepass, the error mapping), so a call must not depend on what the engine did before: each result here equals, bit for
 bit, the same call on a fresh engine."""
 import numpy as np
@@ -113,3 +113,126 @@ def test_device_list_engine_spectra_and_polarization():
     assert parity(grp, one)[0] < 1e-12
     assert parity(polg, pol1)[0] < 1e-12
     assert np.array_equal(again1, one) and np.array_equal(againg, grp)
+
+
+def same(a, b):
+    """Bit equality of two results: arrays (structured ones too), dicts and tuples of them, numbers."""
+    if isinstance(a, (tuple, list)):
+        return len(a) == len(b) and all(same(x, y) for x, y in zip(a, b))
+    if isinstance(a, dict):
+        return a.keys() == b.keys() and all(same(a[k], b[k]) for k in a)
+    if isinstance(a, np.ndarray):
+        return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+    return a == b
+
+
+# "sample_bytes" of tests/test_gpu_sampler_bins.py's batch-window cases.  A call that keeps the list: 100000 ("the list
+# path's own batches"; this surface draws 683 candidates an event at 204 bytes each).  A binned-only call: its batches of
+# (event, cell) pairs at 12 bytes each, 24 pairs for this 64-cell surface where that test has 100 for 300 cells, so one
+# event alone takes three windows of cells
+SMALL_SAMPLE_BYTES = {"list": 100000, "binned+list": 100000, "binned": 12 * 24}
+
+
+def test_sampler_buffers_across_calls():
+    """sample and sample_binned with and without the list, 1, 8 and 1 events, "sample_bytes" default, small and default
+    again on one engine: the call's working buffers (sampler.hip Buffers: pairs, candidates, scan scratch) grow batch
+    by batch and die with the call, so the lists, offsets, histograms and stats are a fresh engine's."""
+    spec = make_spec(hrg_eos=2, chosen="pikp", df_mode=1, dimension=2)
+    s = surf(64, 33)
+    plasma = surface_averages(s)
+    calls = {"list": lambda e, nev: e.sample(3, nev, 2, 0, plasma),
+             "binned+list": lambda e, nev: e.sample_binned(3, nev, 2, 0, plasma, keep_list=True),
+             "binned": lambda e, nev: e.sample_binned(3, nev, 2, 0, plasma)}
+
+    def engine():
+        e = build_engine(spec, s, T_avg=T_AVG)
+        e.set_sample_bins()
+        return e
+
+    ref = {}
+    for small in (False, True):
+        for nev in (1, 8):
+            for name, call in calls.items():
+                f = engine()
+                if small:
+                    f.set_tuning("sample_bytes", SMALL_SAMPLE_BYTES[name])
+                ref[small, nev, name] = (call(f, nev), f.sample_stats())
+                batches = f.get_tuning("sample_batches")
+                f.close()
+                print(small, nev, name, ref[small, nev, name][1])
+                assert ref[small, nev, name][1]["kept"] > 0
+                assert batches > 1 if small else batches == 1, (small, nev, name, batches)
+    e = engine()
+    for small in (False, True, False):
+        for nev in (1, 8, 1):
+            for name, call in calls.items():
+                e.set_tuning("sample_bytes", SMALL_SAMPLE_BYTES[name] if small else -1)
+                got = (call(e, nev), e.sample_stats())
+                assert same(got, ref[small, nev, name]), (small, nev, name)
+                assert (e.get_tuning("sample_batches") > 1) == small
+    e.close()
+
+
+def test_lazy_streams_and_events_survive_reuse_and_teardown():
+    """The side / fold streams and their events exist from the first chunked F_TS launch on (3+1D, folded slabs: the
+    smallest case of tests/test_gpu_north_star.py's chunked test).  Chunked, one chunk, chunked on one engine, then a
+    second engine in the same process after the first is closed: each result is a fresh engine's with that tuning."""
+    spec = make_spec(hrg_eos=2, chosen="smash", df_mode=2, dimension=3, pT="pT48", phi="phi32", y="y21")
+    s = synth.as_read(synth.surface(200, seed=41, dimension=3, full3d=True))
+    chunked = {"phitab_one_bytes": 0, "phitab_chunk_bytes": 1}
+    one_chunk = {"phitab_one_bytes": -1, "phitab_chunk_bytes": 1}
+
+    def call(e, tuning):
+        for k, v in tuning.items():
+            e.set_tuning(k, v)
+        out = e.calculate_spectra()
+        n = e.get_tuning("phitab_chunks")
+        assert (n > 1) if tuning is chunked else (n == 1), n
+        if tuning is chunked:     # the folded plan: an accumulator slab and two buffers of one chunk's splits
+            assert e.get_tuning("slabs") == 1 + 2 * -(-e.get_tuning("splits") // n)
+        return out
+
+    ref = {}
+    for name, tuning in (("chunked", chunked), ("one", one_chunk)):
+        f = build_engine(spec, s, T_avg=T_AVG)
+        ref[name] = call(f, tuning)
+        f.close()
+    assert np.any(ref["one"] != 0.0)
+    e = build_engine(spec, s, T_avg=T_AVG)
+    for name, tuning in (("chunked", chunked), ("one", one_chunk), ("chunked", chunked)):
+        assert np.array_equal(call(e, tuning), ref[name]), name
+    e.close()
+    e2 = build_engine(spec, s, T_avg=T_AVG)
+    assert np.array_equal(call(e2, chunked), ref["chunked"])
+    e2.close()
+
+
+def test_device_list_engine_operations_interleaved():
+    """devices = [0, 0] (the copy reduction, a fixed order): polarization, spectra, the binned sampler, dN/dX and the
+    polarization again on one group engine -- the shard outputs and the device-0 output take five spectra sizes, one
+    and five again -- each bit-equal to the same call on a fresh [0, 0] engine."""
+    spec = make_spec(hrg_eos=2, chosen="pikp", df_mode=1, dimension=2)
+    s = dict(surf(64, 34))
+    s.update(zip(_lib.VORTICITY_FIELDS, synth.vorticity(64, 5)))
+    plasma = surface_averages(s)
+
+    def engine():
+        e = build_engine(spec, s, T_avg=T_AVG, devices=[0, 0])
+        e.set_sample_bins()
+        return e
+
+    calls = [("polarization", lambda e: e.calculate_polarization(T_AVG)),
+             ("spectra", lambda e: e.calculate_spectra()),
+             ("sample_binned", lambda e: e.sample_binned(3, 2, 2, 0, plasma, keep_list=True)),
+             ("dN_dX", lambda e: e.calculate_dN_dX()),
+             ("polarization", lambda e: e.calculate_polarization(T_AVG))]
+    ref = {}
+    for name, call in calls[:4]:
+        f = engine()
+        ref[name] = call(f)
+        f.close()
+    assert np.any(ref["polarization"] != 0.0) and np.any(ref["spectra"] != 0.0) and len(ref["sample_binned"][2]) > 0
+    e = engine()
+    for i, (name, call) in enumerate(calls):
+        assert same(call(e), ref[name]), (i, name)
+    e.close()

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Device-code identity of two source trees: tools/isa_diff.sh <tree_a> <tree_b>
-# Compiles the eight device units of each tree for gfx950 with the Makefile's flags (the same build id on
+# Compiles the nine device units of each tree for gfx950 with the Makefile's flags (the same build id on
 # both sides), and compares the disassembly and the code-object notes (kernel list, VGPR/SGPR, LDS, scratch,
 # max workgroup size).  Needs no GPU.  Exit 0 = every unit identical.  KEEP=1 keeps the work directory.
 set -u
@@ -8,7 +8,7 @@ set -u
 ROCM=${ROCM_PATH:-/opt/rocm}; LLVM=$ROCM/lib/llvm/bin; ARCH=${ARCH:-gfx950}
 FLAGS="-O3 -std=c++17 -fPIC --offload-arch=$ARCH -Wall -Wno-unused-function -Wno-unused-variable"
 W=$(mktemp -d); [ "${KEEP:-0}" = 1 ] || trap 'rm -rf "$W"' EXIT
-UNITS="engine group polzn sampler spectra_12 spectra_3 spectra_4 spectra_5"
+UNITS="engine group polzn sampler decay spectra_12 spectra_3 spectra_4 spectra_5"
 one() {  # <tree> <out dir> <unit>
   local src=$3.hip def=
   case $3 in spectra_*) src=spectra_tu.hip; def=-DIS3D_TU=${3#spectra_};; engine) def='-DIS3D_BUILD_ID="isa_diff"';; esac
