@@ -476,6 +476,37 @@ int is3d_decay_feeddown(is3d_engine *e, double *dN_inout);
 int is3d_launch_feeddown(is3d_engine *e, double *dev_inout, void *stream);
 int is3d_get_decay_stats(const is3d_engine *e, is3d_decay_stats *out);
 
+/* do_resonance_decays for operation = 2: Monte Carlo decays of a particle list, the counterpart of the feed-down above
+ * with the same channel plan (is3d_set_decays; method in is3d2_amd/csrc/decay_mc_math.h and DESIGN.md 7.7).  Every
+ * particle whose species has a kept channel decays down its chains on the GPU: 2-body isotropic, 3-body flat Dalitz;
+ * zero lifetime, so daughters inherit the parent's position and cell; a daughter that is not a chosen species (-1) is
+ * dropped and counted.  A particle stays in the list as a residual when the channel draw falls on the branching of
+ * skipped rows (counted in undecayed) or a 3-body rejection loop reaches its cap (capped).  Primaries keep their
+ * order; each is replaced by its leaves in depth-first daughter-slot order.  The list is a pure function of (seed,
+ * input list): bit-identical for every "sample_bytes" batching, and for a sub-range of events decayed alone.
+ *
+ * is3d_decay_particles decays a caller's list in[offsets[0] .. offsets[n_events]): event k is in[offsets[k] ..
+ * offsets[k + 1]), its records carry one value of `event`, and that value increases from one non-empty event to the next
+ * (two events with one value would share their random streams).
+ * is3d_decay_sampled decays the engine's last sampled list (is3d_sample, is3d_sample_binned with keep_list = 1,
+ * is3d_sample_famod with binned = 0 or 2) in place of it.  After either call is3d_sample_count, is3d_sample_offsets
+ * and is3d_get_particles return the decayed list and is3d_get_particle_origins the index, in the input list, of the
+ * primary each record descends from.  bin = 1 (needs is3d_set_sample_bins): is3d_get_sample_hist then returns the
+ * histograms of the decayed list; the rapidity binned is 0.5 log((E + pz) / (E - pz)) in both dimensions.
+ * A device-list engine runs the call on devices[0] over the merged list.
+ * Errors: IS3D_ERR_STATE without is3d_set_decays, without a sampled list (is3d_decay_sampled), or without bins for
+ * bin = 1; IS3D_ERR_ARG for a negative seed, a species index out of range, events that are not contiguous and
+ * increasing, a plan of more than 16 levels, an event of 2^32 or more primaries, or a primary whose decay
+ * products alone exceed the "sample_bytes" bound (with the size needed). */
+typedef struct {
+  long primaries, decays, undecayed, dropped_daughters, capped, final_particles, passes, batches;
+  double ms_total;                /* device time, HIP events: every batch attempt, the halved ones included */
+} is3d_decay_list_stats;
+int is3d_decay_particles(is3d_engine *e, long seed, int n_events, const long *offsets, const is3d_particle *in, int bin);
+int is3d_decay_sampled(is3d_engine *e, long seed, int bin);
+int is3d_get_particle_origins(const is3d_engine *e, long first, long count, long *origin);
+int is3d_get_decay_list_stats(const is3d_engine *e, is3d_decay_list_stats *out);
+
 #ifdef __cplusplus
 }
 #endif

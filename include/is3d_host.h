@@ -63,6 +63,15 @@ int is3d_host_total_yield(const char *workdir, int device, int num_devices, doub
 int is3d_host_sample(const char *workdir, const int *devices, int num_devices, int write_files, int write_csv,
                      is3d_particle *out, long *mcid_out, long capacity, long *offsets, long offsets_capacity,
                      long *n_particles, long *n_events, double *n_total, long *seed, char *err, int errlen);
+/* is3d_host_sample with the bookkeeping of do_resonance_decays = 1 (the sampled list is decayed down its chains by
+ * is3d_decay_sampled with the sampler's seed, and every output above is the decayed list's; test_sampler = 1: the final
+ * hadrons are binned): origins (optional, capacity) = for each record the index, in the sampled list, of the primary it
+ * descends from; decay_stats (optional) = is3d_get_decay_list_stats.  With the key 0 or absent nothing is written to
+ * origins and the stats are zero. */
+int is3d_host_sample_decays(const char *workdir, const int *devices, int num_devices, int write_files, int write_csv,
+                            is3d_particle *out, long *mcid_out, long capacity, long *offsets, long offsets_capacity,
+                            long *n_particles, long *n_events, double *n_total, long *seed, long *origins,
+                            is3d_decay_list_stats *decay_stats, char *err, int errlen);
 /* operation = 2 and test_sampler = 1 in <workdir>/iS3D_parameters.dat: as is3d_host_sample, with every kept particle
  * binned on the device (is3d_sample_binned, keep_list = 0) with the parameter file's pT / y / phip / eta / tau / r bins.
  * write_files: the results/sampled tree of write_sampled_*_to_file_test (EmissionFunction.cpp:685-975), nine files per
@@ -73,6 +82,12 @@ int is3d_host_sample_hist_size(const char *workdir, is3d_sample_bins *bins, int 
 int is3d_host_sample_binned(const char *workdir, const int *devices, int num_devices, int write_files, long *counts,
                             long counts_capacity, double *vn, long vn_capacity, long *n_events, double *n_total,
                             long *seed, is3d_sample_stats *stats, char *err, int errlen);
+/* ... with decay_stats (optional) = is3d_get_decay_list_stats of the decays that do_resonance_decays = 1 ran on the kept
+ * list before it was binned (zero with the key 0 or absent). */
+int is3d_host_sample_binned_decays(const char *workdir, const int *devices, int num_devices, int write_files, long *counts,
+                                   long counts_capacity, double *vn, long vn_capacity, long *n_events, double *n_total,
+                                   long *seed, is3d_sample_stats *stats, is3d_decay_list_stats *decay_stats, char *err,
+                                   int errlen);
 /* The two writers alone, for a list the caller holds: offsets[n_events + 1], list / mcid / mass per particle. */
 int is3d_host_write_particle_lists(const char *workdir, long n_events, const long *offsets, const is3d_particle *list,
                                    const long *mcid, const double *mass, int write_csv, char *err, int errlen);

@@ -30,7 +30,8 @@ EXPORTS = ["is3d_abi_version", "is3d_build_id", "is3d_create", "is3d_create_devi
            "is3d_sample_uniforms", "is3d_set_sample_bins", "is3d_sample_binned", "is3d_sample_hist_size",
            "is3d_get_sample_hist", "is3d_sample_famod", "is3d_get_sample_famod_stats",
            "is3d_calculate_dN_dX_famod",
-           "is3d_set_decays", "is3d_decay_feeddown", "is3d_launch_feeddown", "is3d_get_decay_stats"]
+           "is3d_set_decays", "is3d_decay_feeddown", "is3d_launch_feeddown", "is3d_get_decay_stats",
+           "is3d_decay_particles", "is3d_decay_sampled", "is3d_get_particle_origins", "is3d_get_decay_list_stats"]
 
 VORTICITY_FIELDS = ["wtx", "wty", "wtn", "wxy", "wxn", "wyn"]
 
@@ -109,6 +110,12 @@ DECAY_DTYPE = np.dtype([("parent", "<i4"), ("n_body", "<i4"), ("daughter", "<i4"
 class DecayStats(C.Structure):
     _fields_ = [(k, C.c_long) for k in ("channels", "kept", "skipped_many_body", "skipped_closed", "adjusted",
                                         "levels")] + [("branching_skipped", C.c_double), ("ms_total", C.c_double)]
+
+
+class DecayListStats(C.Structure):
+    """is3d_decay_list_stats: the counters of the last Monte Carlo decay of a particle list."""
+    _fields_ = [(k, C.c_long) for k in ("primaries", "decays", "undecayed", "dropped_daughters", "capped",
+                                        "final_particles", "passes", "batches")] + [("ms_total", C.c_double)]
 
 
 # (name in Engine.sample_binned's dict, the bins field that sizes it)
@@ -201,6 +208,10 @@ def load():
     lib.is3d_decay_feeddown.argtypes = [C.c_void_p, pd]
     lib.is3d_launch_feeddown.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     lib.is3d_get_decay_stats.argtypes = [C.c_void_p, P(DecayStats)]
+    lib.is3d_decay_particles.argtypes = [C.c_void_p, C.c_long, C.c_int, P(C.c_long), C.c_void_p, C.c_int]
+    lib.is3d_decay_sampled.argtypes = [C.c_void_p, C.c_long, C.c_int]
+    lib.is3d_get_particle_origins.argtypes = [C.c_void_p, C.c_long, C.c_long, P(C.c_long)]
+    lib.is3d_get_decay_list_stats.argtypes = [C.c_void_p, P(DecayListStats)]
     _lib = lib
     return lib
 

@@ -213,8 +213,16 @@ inline Rule make_rule() {
   return r;
 }
 
+// a kept channel: the row as given (slots past n_body cleared) with the masses the closed-channel rule left it with
+struct Kept { is3d_decay_channel c; double M, m[3]; };
+
 // the launch plan: levels of parents, and per level the receivers with their two-body terms in summation order
 struct Plan {
+  // what every consumer of the channel table needs (the feed-down below, the Monte Carlo decays of decay_mc_math.h):
+  // the kept channels in canonical order, species p's being kept[first[p] .. first[p + 1]), and the level at which a
+  // parent decays (-1: no kept channel)
+  std::vector<Kept> kept;
+  std::vector<int> first, level_of;
   std::vector<Sub> subs;
   std::vector<int> recv_d, recv_s0, recv_s1;   // receiver r: daughter species, its terms subs[s0 .. s1)
   std::vector<int> lvl_r0;                     // level l: receivers [lvl_r0[l], lvl_r0[l + 1])
@@ -287,8 +295,7 @@ inline std::string build_plan(Plan& P, const Rule& r, int npart, const double* s
                               const is3d_decay_channel* ch) {
   P = Plan{};
   P.stats.channels = n;
-  struct Kept { is3d_decay_channel c; double M, m[3]; };
-  std::vector<Kept> kept;
+  std::vector<Kept>& kept = P.kept;
   for (int i = 0; i < n; i++) {
     const is3d_decay_channel& c = ch[i];
     if (c.n_body < 1) return "decay channel " + std::to_string(i) + ": n_body < 1";
@@ -340,7 +347,10 @@ inline std::string build_plan(Plan& P, const Rule& r, int npart, const double* s
   };
   std::stable_sort(kept.begin(), kept.end(), key_less);
   // levels (Kahn by rounds): indeg[d] = kept slots that feed d
-  std::vector<int> indeg(npart, 0), first(npart + 1, 0);
+  std::vector<int> indeg(npart, 0);
+  std::vector<int>& first = P.first;
+  first.assign((size_t)npart + 1, 0);
+  P.level_of.assign((size_t)npart, -1);
   std::vector<char> is_parent(npart, 0), done(npart, 0);
   for (const Kept& k : kept) {
     is_parent[k.c.parent] = 1;
@@ -364,6 +374,7 @@ inline std::string build_plan(Plan& P, const Rule& r, int npart, const double* s
     std::vector<int> recv;
     for (int p : lvl) {
       done[p] = 1;
+      P.level_of[p] = (int)P.lvl_p0.size() - 1;
       left--;
       for (int q = first[p]; q < first[p + 1]; q++)
         for (int s = 0; s < kept[q].c.n_body; s++) {

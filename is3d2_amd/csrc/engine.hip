@@ -67,6 +67,7 @@
 #include "polzn.h"
 #include "sampler.h"
 #include "decay.h"
+#include "decay_list.h"
 #include "devbuf.h"
 
 using namespace is3d;
@@ -218,6 +219,12 @@ struct is3d_engine {
   DevBuf<int> d_dk_i;
   DevEvent dk_ev[2];
   is3d_decay_stats dk_stats{};
+  // Monte Carlo decays of a particle list (decay_list.hip): the plan's tables on the device (rebuilt after
+  // is3d_set_decays), and the origins and stats of the last decayed list (a new sample clears them)
+  is3d::decay_list::Tables dl;
+  bool dl_dirty = true, decayed = false;
+  std::vector<long> origins;
+  is3d_decay_list_stats dl_stats{};
 
   int fail(int code, const std::string& msg) { err = msg; return code; }
 };
@@ -1938,6 +1945,7 @@ extern "C" int is3d_set_decays(is3d_engine* e, int n, const is3d_decay_channel* 
   e->dk_stats = e->dk_plan.stats;
   e->have_decays = true;
   e->dk_dirty = true;
+  e->dl_dirty = true;
   return IS3D_OK;
 }
 
@@ -2082,6 +2090,7 @@ static int sample_any(is3d_engine* e, const is3d_sample_params* sp, const double
   if (!e || e->grp) return IS3D_ERR_ARG;
   e->sampled = false;
   e->binned = false;
+  e->decayed = false;
   if (!sp || (!famod && !plasma)) return e->fail(IS3D_ERR_ARG, "is3d_sample: null argument");
   if (!famod && e->have_params && e->p.df_mode == PTMA)
     return e->fail(IS3D_ERR_UNSUPPORTED, "is3d_sample: df_mode 5 has its own method (sample_dN_pTdpTdphidy_famod): call is3d_sample_famod");
@@ -2271,6 +2280,138 @@ extern "C" int is3d_sample_uniforms(is3d_engine* e, long seed, int purpose, long
     return e ? e->fail(IS3D_ERR_ARG, "is3d_sample_uniforms: bad argument") : IS3D_ERR_ARG;
   HIPCHK(e, hipSetDevice(e->device));
   HIPCHK(e, is3d::sampler::uniforms((uint64_t)seed, purpose, cell, event, candidate, n, out));
+  return IS3D_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// Monte Carlo decays of a particle list (do_resonance_decays with operation = 2; method in decay_mc_math.h, kernels in
+// decay_list.hip)
+// ------------------------------------------------------------------------------------------
+// in may be the engine's own list: nothing of the engine changes before the call has succeeded
+static int decay_list_any(is3d_engine* e, long seed, int n_events, const long* offsets, const is3d_particle* in, int bin,
+                          const char* who) {
+  const std::string w = std::string(who) + ": ";
+  if (!e->have_decays) return e->fail(IS3D_ERR_STATE, w + "no decay channels set (is3d_set_decays)");
+  if (bin && !e->have_sbins) return e->fail(IS3D_ERR_STATE, w + "is3d_set_sample_bins not called");
+  if (seed < 0) return e->fail(IS3D_ERR_ARG, w + "the seed must be non-negative");
+  if (n_events < 0 || !offsets) return e->fail(IS3D_ERR_ARG, w + "bad event offsets");
+  const std::string plan_err = is3d::decay_mc::check_plan(e->dk_plan);
+  if (!plan_err.empty()) return e->fail(IS3D_ERR_ARG, w + plan_err);
+  const int np = (int)e->mass.size();
+  const long i0 = offsets[0], n = offsets[n_events] - i0;
+  if (i0 < 0 || n < 0 || (n > 0 && !in)) return e->fail(IS3D_ERR_ARG, w + "bad event offsets");
+  for (int k = 0; k < n_events; k++)
+    if (offsets[k + 1] < offsets[k]) return e->fail(IS3D_ERR_ARG, w + "the event offsets decrease at event " + std::to_string(k));
+  std::vector<uint32_t> prim((size_t)n);
+  long last_event = 0;
+  bool seen = false;
+  for (int k = 0; k < n_events; k++) {
+    const long a = offsets[k], b = offsets[k + 1];
+    if (b - a > 0xffffffffL) return e->fail(IS3D_ERR_ARG, w + "event " + std::to_string(k) + " has 2^32 or more primaries");
+    for (long i = a; i < b; i++) {
+      if (in[i].species < 0 || in[i].species >= np)
+        return e->fail(IS3D_ERR_ARG, w + "record " + std::to_string(i) + ": species index out of range");
+      if (in[i].event != in[a].event)
+        return e->fail(IS3D_ERR_ARG, w + "record " + std::to_string(i) + ": the events are not contiguous");
+      prim[(size_t)(i - i0)] = (uint32_t)(i - a);
+    }
+    if (b > a) {
+      // equal values would give two events one set of streams (primary index, event, path)
+      if (seen && in[a].event <= last_event)
+        return e->fail(IS3D_ERR_ARG, w + "record " + std::to_string(a) + ": the event field does not increase from event to event");
+      last_event = in[a].event;
+      seen = true;
+    }
+  }
+  HIPCHK(e, hipSetDevice(e->device));
+  if (e->dl_dirty) {
+    const std::string m = is3d::decay_list::tables_build(e->dl, e->dk_plan, e->mass);
+    if (!m.empty()) return e->fail(IS3D_ERR_DEVICE, w + m);
+    e->dl_dirty = false;
+  }
+  is3d::decay_list::Config c;
+  c.seed = (uint64_t)seed;
+  c.sample_bytes = e->sample_bytes;
+  is3d::sampler::Bins sb{};
+  long nc = 0, nv = 0;
+  if (bin) {
+    sb = sampler_bins(e->sbins);
+    nc = is3d::sampler::hist_counts(sb, np);
+    nv = is3d::sampler::hist_vn(sb, np);
+    if (!e->d_hist.reserve(nc + nv)) return e->fail(IS3D_ERR_DEVICE, w + "hipMalloc(histogram) failed");
+    HIPCHK(e, hipMemset(e->d_hist.get(), 0, (size_t)(nc + nv) * sizeof(unsigned long long)));
+    c.bins = &sb; c.hist = e->d_hist.get();
+  }
+  static_assert(sizeof(is3d_particle) == sizeof(is3d::sampler::Particle), "is3d_particle is the sampler's record");
+  std::vector<is3d::sampler::Particle> out;
+  std::vector<long> origin;
+  is3d::decay_list::Stats st;
+  std::string msg;
+  const int s = is3d::decay_list::run(e->dl, c, n, reinterpret_cast<const is3d::sampler::Particle*>(in) + i0, prim.data(), out,
+                                      origin, st, msg);
+  if (s == is3d::decay_list::S_DEVICE) return e->fail(IS3D_ERR_DEVICE, w + msg);
+  if (s == is3d::decay_list::S_BUDGET) return e->fail(IS3D_ERR_ARG, w + msg);
+  std::vector<long long> hist;
+  if (bin) {
+    hist.assign((size_t)(nc + nv), 0);
+    HIPCHK(e, hipMemcpy(hist.data(), e->d_hist.get(), hist.size() * sizeof(long long), hipMemcpyDeviceToHost));
+  }
+  // the offsets of the decayed list: origins are non-decreasing, so event k ends where the origins reach its end
+  std::vector<long> off((size_t)n_events + 1, 0);
+  size_t j = 0;
+  for (int k = 0; k < n_events; k++) {
+    while (j < origin.size() && origin[j] < offsets[k + 1] - i0) j++;
+    off[(size_t)k + 1] = (long)j;
+  }
+  for (long& o : origin) o += i0;
+  e->particles.swap(out);
+  e->particle_offsets.swap(off);
+  e->origins.swap(origin);
+  e->dl_stats = is3d_decay_list_stats{st.primaries, st.decays, st.undecayed, st.dropped_daughters, st.capped,
+                                      st.final_particles, st.passes, st.batches, st.ms_total};
+  if (bin) {
+    e->hist.swap(hist);
+    e->hist_nc = nc; e->hist_nv = nv;
+    e->binned = true;
+  }
+  e->sampled = true;
+  e->decayed = true;
+  return IS3D_OK;
+}
+
+extern "C" int is3d_decay_particles(is3d_engine* e, long seed, int n_events, const long* offsets, const is3d_particle* in, int bin) {
+  if (e && e->grp) return is3d::group_decay_particles(e->grp, seed, n_events, offsets, in, bin);
+  if (!e) return IS3D_ERR_ARG;
+  const int rc = decay_list_any(e, seed, n_events, offsets, in, bin, "is3d_decay_particles");
+  if (!rc) e->sampled_famod = false;
+  return rc;
+}
+
+extern "C" int is3d_decay_sampled(is3d_engine* e, long seed, int bin) {
+  if (e && e->grp) return is3d::group_decay_sampled(e->grp, seed, bin);
+  if (!e) return IS3D_ERR_ARG;
+  if (!e->have_decays) return e->fail(IS3D_ERR_STATE, "is3d_decay_sampled: no decay channels set (is3d_set_decays)");
+  if (!e->sampled || e->particle_offsets.empty() ||
+      (e->particles.empty() && e->sst.kept > 0))     // a binned-only call counted particles and kept none
+    return e->fail(IS3D_ERR_STATE, "is3d_decay_sampled: no sampled list (is3d_sample, or a binned call that keeps the list)");
+  return decay_list_any(e, seed, (int)e->particle_offsets.size() - 1, e->particle_offsets.data(),
+                        reinterpret_cast<const is3d_particle*>(e->particles.data()), bin, "is3d_decay_sampled");
+}
+
+extern "C" int is3d_get_particle_origins(const is3d_engine* e, long first, long count, long* origin) {
+  if (e && e->grp) return is3d::group_get_particle_origins(e->grp, first, count, origin);
+  if (!e || (!origin && count > 0)) return IS3D_ERR_ARG;
+  if (!e->sampled || !e->decayed) return IS3D_ERR_STATE;
+  if (first < 0 || count < 0 || first + count > (long)e->origins.size()) return IS3D_ERR_ARG;
+  std::copy(e->origins.begin() + first, e->origins.begin() + first + count, origin);
+  return IS3D_OK;
+}
+
+extern "C" int is3d_get_decay_list_stats(const is3d_engine* e, is3d_decay_list_stats* out) {
+  if (e && e->grp) return out ? is3d::group_get_decay_list_stats(e->grp, out) : IS3D_ERR_ARG;
+  if (!e || !out) return IS3D_ERR_ARG;
+  if (!e->sampled || !e->decayed) return IS3D_ERR_STATE;
+  *out = e->dl_stats;
   return IS3D_OK;
 }
 

@@ -76,6 +76,11 @@ int group_set_decays(Group* g, int n, const is3d_decay_channel* ch);
 int group_launch_feeddown(Group* g, double* dev_inout, void* stream);
 int group_decay_feeddown(Group* g, double* dN_inout);
 int group_get_decay_stats(const Group* g, is3d_decay_stats* out);
+// Monte Carlo decays of a particle list: run on devices[0] (shard 0) over the merged list, which then replaces it
+int group_decay_particles(Group* g, long seed, int n_events, const long* offsets, const is3d_particle* in, int bin);
+int group_decay_sampled(Group* g, long seed, int bin);
+int group_get_particle_origins(const Group* g, long first, long count, long* origin);
+int group_get_decay_list_stats(const Group* g, is3d_decay_list_stats* out);
 }  // namespace is3d
 
 // engine.hip internals the group uses on its shard engines (not part of the public ABI)

@@ -70,6 +70,7 @@ struct Group {
   is3d_sample_stats sstats{};
   is3d_sample_famod_stats sfstats{};
   bool sampled = false, sampled_famod = false;
+  bool decayed = false;               // the list is shard 0's decayed list (group_decay_particles)
   // ... and the sum of the shards' integer histograms of the last binned call (counts, then fixed-point vn sums)
   std::vector<long long> hist;
   long hist_nc = 0, hist_nv = 0;
@@ -503,6 +504,49 @@ int group_decay_feeddown(Group* g, double* dN_inout) {
 }
 int group_get_decay_stats(const Group* g, is3d_decay_stats* out) { return is3d_get_decay_stats(g->sh[0], out); }
 
+// shard 0 decays the list and the group takes its result: list, offsets and, for bin = 1, the histogram
+int group_decay_particles(Group* g, long seed, int n_events, const long* offsets, const is3d_particle* in, int bin) {
+  is3d_engine* e0 = g->sh[0];
+  int rc = is3d_decay_particles(e0, seed, n_events, offsets, in, bin);
+  if (rc) return g->shard_fail(0, rc);
+  const long n = is3d_sample_count(e0);
+  std::vector<is3d_particle> parts((size_t)std::max(n, 0L));
+  std::vector<long> off((size_t)n_events + 1, 0);
+  rc = is3d_sample_offsets(e0, off.data());
+  if (!rc && n > 0) rc = is3d_get_particles(e0, 0, n, parts.data());
+  if (rc) return g->shard_fail(0, rc);
+  if (bin) {
+    const long long* h = is3d_internal_sample_hist(e0);
+    if (!h || is3d_sample_hist_size(e0, &g->hist_nc, &g->hist_nv) < 0) return g->shard_fail(0, IS3D_ERR_STATE);
+    g->hist.assign(h, h + g->hist_nc + g->hist_nv);
+    g->binned = true;
+  }
+  g->particles.swap(parts);
+  g->particle_offsets.swap(off);
+  g->sampled = true;
+  g->sampled_famod = false;            // a caller's list, as on one engine (group_decay_sampled puts it back)
+  g->decayed = true;
+  return IS3D_OK;
+}
+int group_decay_sampled(Group* g, long seed, int bin) {
+  if (!g->sampled || g->particle_offsets.empty() || (g->particles.empty() && g->sstats.kept > 0))
+    return g->fail(IS3D_ERR_STATE, "is3d_decay_sampled: no sampled list (is3d_sample, or a binned call that keeps the list)");
+  const std::vector<is3d_particle> in = g->particles;     // shard 0's call replaces the group's list
+  const std::vector<long> off = g->particle_offsets;
+  const bool famod = g->sampled_famod;
+  const int rc = group_decay_particles(g, seed, (int)off.size() - 1, off.data(), in.data(), bin);
+  if (!rc) g->sampled_famod = famod;
+  return rc;
+}
+int group_get_particle_origins(const Group* g, long first, long count, long* origin) {
+  if (!g->sampled || !g->decayed) return IS3D_ERR_STATE;
+  return is3d_get_particle_origins(g->sh[0], first, count, origin);
+}
+int group_get_decay_list_stats(const Group* g, is3d_decay_list_stats* out) {
+  if (!g->sampled || !g->decayed) return IS3D_ERR_STATE;
+  return is3d_get_decay_list_stats(g->sh[0], out);
+}
+
 int group_finish(Group* g) {
   if (g->fd_launched && !g->launched) {
     g->fd_launched = false;
@@ -675,6 +719,7 @@ int group_get_sample_hist(const Group* g, long* counts, double* vn) {
 static int sample_shards(Group* g, const is3d_sample_params* p, const double* plasma, int binned, bool famod) {
   g->sampled = false;
   g->sampled_famod = false;
+  g->decayed = false;
   g->binned = false;
   if (!p || (!famod && !plasma)) return g->fail(IS3D_ERR_ARG, "is3d_sample: null argument");
   if (famod && (binned < 0 || binned > 2)) return g->fail(IS3D_ERR_ARG, "is3d_sample_famod: binned must be 0, 1 or 2");

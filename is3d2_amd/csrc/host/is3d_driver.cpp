@@ -55,9 +55,11 @@ EmissionFunctionArray::EmissionFunctionArray(const ParameterReader& params, cons
   }
   // the decay rows of the chosen species as the engine's channel table: indices into the chosen list (first match,
   // -1 for a daughter that is not chosen), masses and widths from the PDG list; |n_body| (the UrQMD table flags some
-  // rows with a negative count); lightest_particle is read and not used, as in the reference.  Only operation = 1
-  // uses the table: under any other operation the key changes nothing, so a row it could not resolve must not fail the run
-  if ((int)p_.get("do_resonance_decays", 0.0) == 1 && (int)p_.get("operation", 1.0) == 1) {
+  // rows with a negative count); lightest_particle is read and not used, as in the reference.  Operations 1
+  // (the feed-down of the spectra) and 2 (the Monte Carlo decays of the sampled list) use the table: under operation 0
+  // the key changes nothing, so a row it could not resolve must not fail the run
+  const int op_key = (int)p_.get("operation", 1.0);
+  if ((int)p_.get("do_resonance_decays", 0.0) == 1 && (op_key == 1 || op_key == 2)) {
     auto find = [&](long mc) {
       for (size_t n = 0; n < particles.size(); n++) if (particles[n].mcid == mc) return (int)n;
       return -1;
@@ -197,10 +199,19 @@ void EmissionFunctionArray::run_sharded(const RunOptions& opt, int operation) {
       sp.y_cut = p_.get("y_cut", 0.5);
       // df_mode 5 has a method of its own (EmissionFunction.cpp:1255-1275): sample_dN_pTdpTdphidy_famod
       const bool famod = prm.df_mode == 5;
+      // do_resonance_decays = 1: the sampled list is decayed down its chains (is3d_decay_sampled, the sampler's seed)
+      // before anything reads it, so the lists, the offsets and the binned files carry the final hadrons
+      const bool decays = (int)p_.get("do_resonance_decays", 0.0) == 1;
+      if (decays) set_or_throw(e, is3d_set_decays(e, (int)decays_.size(), decays_.data()));
       if (operation == 4) {      // test_sampler = 1: binned only, no list (EmissionFunction.cpp:1279-1291)
         sbins_ = read_sample_bins(p_);
         set_or_throw(e, is3d_set_sample_bins(e, &sbins_));
-        set_or_throw(e, famod ? is3d_sample_famod(e, &sp, 1) : is3d_sample_binned(e, &sp, plasma, 0));
+        if (decays) {            // the decays need the list: it is kept, decayed and binned, and not written
+          set_or_throw(e, famod ? is3d_sample_famod(e, &sp, 2) : is3d_sample_binned(e, &sp, plasma, 1));
+          set_or_throw(e, is3d_decay_sampled(e, sample_seed_, 1));
+        } else {
+          set_or_throw(e, famod ? is3d_sample_famod(e, &sp, 1) : is3d_sample_binned(e, &sp, plasma, 0));
+        }
         long nc = 0, nv = 0;
         if (is3d_sample_hist_size(e, &nc, &nv) < 0) throw EngineError(IS3D_ERR_STATE, "is3d_sample_hist_size failed");
         hist_counts_.assign((size_t)nc, 0);
@@ -208,6 +219,7 @@ void EmissionFunctionArray::run_sharded(const RunOptions& opt, int operation) {
         set_or_throw(e, is3d_get_sample_hist(e, hist_counts_.data(), hist_vn_.data()));
       } else {
         set_or_throw(e, famod ? is3d_sample_famod(e, &sp, 0) : is3d_sample(e, &sp, plasma));
+        if (decays) set_or_throw(e, is3d_decay_sampled(e, sample_seed_, 0));
       }
       famod_sampled_ = famod;
       if (famod) set_or_throw(e, is3d_get_sample_famod_stats(e, &famod_stats_));
@@ -215,7 +227,19 @@ void EmissionFunctionArray::run_sharded(const RunOptions& opt, int operation) {
       sample_offsets_.assign((size_t)sample_events_ + 1, 0);
       set_or_throw(e, is3d_sample_offsets(e, sample_offsets_.data()));
       set_or_throw(e, is3d_get_particles(e, 0, (long)records_.size(), records_.data()));
-      set_or_throw(e, is3d_get_sample_stats(e, &sample_stats_));
+      set_or_throw(e, is3d_get_sample_stats(e, &sample_stats_));     // the sampler's, decays or not
+      origins_.clear();
+      decay_list_stats_ = is3d_decay_list_stats{};
+      if (decays) {
+        origins_.assign(records_.size(), 0);
+        set_or_throw(e, is3d_get_particle_origins(e, 0, (long)origins_.size(), origins_.data()));
+        set_or_throw(e, is3d_get_decay_list_stats(e, &decay_list_stats_));
+        if (operation == 4) {      // test_sampler = 1 never lists: the decayed list was binned and is dropped
+          records_.clear();
+          origins_.clear();
+          sample_offsets_.assign((size_t)sample_events_ + 1, 0);
+        }
+      }
     } else if (operation == 0) {
       set_or_throw(e, is3d_set_momentum_weights(e, pTw.data(), phiw.data()));
       set_or_throw(e, is3d_set_spacetime_bins(e, &bins));
@@ -384,7 +408,8 @@ void IS3D::run_particlization(int fo_from_file, const RunOptions& opt) {
       std::printf("\nSampling 1 particlization event...\n\n");
     }
     dN_.clear();
-    final_particles_.clear(); particle_offsets_.clear(); particle_records_.clear();
+    final_particles_.clear(); particle_offsets_.clear(); particle_records_.clear(); particle_origins_.clear();
+    decay_list_stats_ = is3d_decay_list_stats{};
     hist_counts_.clear(); hist_vn_.clear();
     if (opt.sample) {            // EmissionFunction.cpp:1251-1301: sample, then write the lists
       // sampler_seed < 0: the clock, as the reference (ParticleSampler.cpp:646-648); the engine sees a seed >= 0
@@ -397,6 +422,8 @@ void IS3D::run_particlization(int fo_from_file, const RunOptions& opt) {
       final_particles_ = efa.sampled();
       particle_offsets_ = efa.sample_offsets();
       particle_records_ = efa.sampled_records();
+      particle_origins_ = efa.sample_origins();
+      decay_list_stats_ = efa.decay_list_stats();
       sample_stats_ = efa.sample_stats();
       if (!opt.quiet) {
         const is3d_sample_stats& st = sample_stats_;
@@ -407,6 +434,12 @@ void IS3D::run_particlization(int fo_from_file, const RunOptions& opt) {
         }
         std::printf("Sampled %ld particles in %ld events (%ld candidates, %ld dropped at an iteration cap)\n", st.kept, nevents_,
                     st.candidates, st.capped);
+        if ((int)prm.get("do_resonance_decays", 0.0) == 1) {
+          const is3d_decay_list_stats& d = decay_list_stats_;
+          std::printf("Resonance decays: %ld decays of %ld primaries in %ld passes -> %ld final hadrons (%ld undecayed, %ld daughters "
+                      "dropped, %ld capped), %.3f ms\n", d.decays, d.primaries, d.passes, d.final_particles, d.undecayed,
+                      d.dropped_daughters, d.capped, d.ms_total);
+        }
       }
       if (binned) {
         hist_counts_ = efa.hist_counts();
@@ -527,6 +560,14 @@ extern "C" int is3d_host_total_yield(const char* workdir, int device, int num_de
 extern "C" int is3d_host_sample(const char* workdir, const int* devices, int num_devices, int write_files, int write_csv,
                                 is3d_particle* out, long* mcid_out, long capacity, long* offsets, long offsets_capacity,
                                 long* n_particles, long* n_events, double* n_total, long* seed, char* err, int errlen) {
+  return is3d_host_sample_decays(workdir, devices, num_devices, write_files, write_csv, out, mcid_out, capacity, offsets,
+                                 offsets_capacity, n_particles, n_events, n_total, seed, nullptr, nullptr, err, errlen);
+}
+
+extern "C" int is3d_host_sample_decays(const char* workdir, const int* devices, int num_devices, int write_files, int write_csv,
+                                       is3d_particle* out, long* mcid_out, long capacity, long* offsets, long offsets_capacity,
+                                       long* n_particles, long* n_events, double* n_total, long* seed, long* origins,
+                                       is3d_decay_list_stats* decay_stats, char* err, int errlen) {
   if (!devices || num_devices <= 0) { put_err(err, errlen, "empty device list"); return IS3D_ERR_ARG; }
   try {
     IS3D run(workdir ? workdir : ".");
@@ -550,6 +591,11 @@ extern "C" int is3d_host_sample(const char* workdir, const int* devices, int num
       for (long i = 0; i < n; i++) mcid_out[i] = run.final_particles()[(size_t)i].mcid;
     }
     if (offsets) std::copy(run.particle_offsets().begin(), run.particle_offsets().end(), offsets);
+    if (origins) {
+      if ((long)run.particle_origins().size() > capacity) { put_err(err, errlen, "output buffer too small"); return IS3D_ERR_ARG; }
+      std::copy(run.particle_origins().begin(), run.particle_origins().end(), origins);
+    }
+    if (decay_stats) *decay_stats = run.decay_list_stats();
     return IS3D_OK;
   } catch (const EngineError& ex) {
     put_err(err, errlen, ex.what());
@@ -577,6 +623,14 @@ extern "C" int is3d_host_sample_hist_size(const char* workdir, is3d_sample_bins*
 extern "C" int is3d_host_sample_binned(const char* workdir, const int* devices, int num_devices, int write_files, long* counts,
                                        long counts_capacity, double* vn, long vn_capacity, long* n_events, double* n_total,
                                        long* seed, is3d_sample_stats* stats, char* err, int errlen) {
+  return is3d_host_sample_binned_decays(workdir, devices, num_devices, write_files, counts, counts_capacity, vn, vn_capacity,
+                                        n_events, n_total, seed, stats, nullptr, err, errlen);
+}
+
+extern "C" int is3d_host_sample_binned_decays(const char* workdir, const int* devices, int num_devices, int write_files,
+                                              long* counts, long counts_capacity, double* vn, long vn_capacity, long* n_events,
+                                              double* n_total, long* seed, is3d_sample_stats* stats,
+                                              is3d_decay_list_stats* decay_stats, char* err, int errlen) {
   if (!devices || num_devices <= 0) { put_err(err, errlen, "empty device list"); return IS3D_ERR_ARG; }
   try {
     IS3D run(workdir ? workdir : ".");
@@ -591,6 +645,7 @@ extern "C" int is3d_host_sample_binned(const char* workdir, const int* devices, 
     if (n_total) *n_total = run.total_yield();
     if (seed) *seed = run.sampler_seed();
     if (stats) *stats = run.sample_stats();
+    if (decay_stats) *decay_stats = run.decay_list_stats();
     if ((counts && (long)run.hist_counts().size() > counts_capacity) || (vn && (long)run.hist_vn().size() > vn_capacity)) {
       put_err(err, errlen, "output buffer too small");
       return IS3D_ERR_ARG;

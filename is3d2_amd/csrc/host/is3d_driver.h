@@ -99,8 +99,16 @@ class EmissionFunctionArray {
   // engine's bookkeeping (zero when the key is 0 or absent)
   const std::vector<is3d_decay_channel>& decay_channels() const { return decays_; }
   const is3d_decay_stats& decay_stats() const { return decay_stats_; }
+  // do_resonance_decays = 1 with operation = 2: the sampled list is decayed by is3d_decay_sampled (the sampler's seed)
+  // right after sampling; sampled(), sample_offsets() and sampled_records() then hold the final hadrons,
+  // sample_origins() the index in the sampled list of the primary each descends from and decay_list_stats() the
+  // engine's counters (empty / zero when the key is 0 or absent).  With test_sampler = 1 the final hadrons are binned
+  const std::vector<long>& sample_origins() const { return origins_; }
+  const is3d_decay_list_stats& decay_list_stats() const { return decay_list_stats_; }
 
  private:
+  std::vector<long> origins_;
+  is3d_decay_list_stats decay_list_stats_{};
   std::vector<is3d_decay_channel> decays_;
   is3d_decay_stats decay_stats_{};
   const ParameterReader& p_;
@@ -161,6 +169,10 @@ class IS3D {
   const std::vector<long>& particle_offsets() const { return particle_offsets_; }
   const std::vector<is3d_particle>& particle_records() const { return particle_records_; }
   const is3d_sample_stats& sample_stats() const { return sample_stats_; }
+  // do_resonance_decays = 1: the lists above are the decayed ones; particle_origins()[i] = the sampled primary record
+  // i descends from, decay_list_stats() the counters of the decays
+  const std::vector<long>& particle_origins() const { return particle_origins_; }
+  const is3d_decay_list_stats& decay_list_stats() const { return decay_list_stats_; }
   long sampler_seed() const { return seed_; }
   // ... with test_sampler = 1: no list (the offsets are zero); the histograms of is3d_get_sample_hist and their bins
   const std::vector<long>& hist_counts() const { return hist_counts_; }
@@ -177,6 +189,8 @@ class IS3D {
   std::vector<SampledParticle> final_particles_;
   std::vector<long> particle_offsets_;
   std::vector<is3d_particle> particle_records_;
+  std::vector<long> particle_origins_;
+  is3d_decay_list_stats decay_list_stats_{};
   is3d_sample_stats sample_stats_{};
   std::vector<long> hist_counts_;
   std::vector<double> hist_vn_;

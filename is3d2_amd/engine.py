@@ -96,6 +96,7 @@ class Engine:
         if not self._e:
             raise IS3DError(_lib.IS3D_ERR_DEVICE, "is3d_create(%d) failed (no HIP device?)" % device)
         self._keep = []
+        self._list_events = 0      # events of the particle list the engine holds
 
     def close(self):
         if getattr(self, "_e", None):
@@ -363,6 +364,7 @@ class Engine:
         pl = _arr(plasma)
         sp = _lib.SampleParams(int(seed), int(n_events), int(fast), float(y_cut))
         self._chk(self.lib.is3d_sample(self._e, C.byref(sp), _dp(pl)))
+        self._list_events = int(n_events)
         n = self.lib.is3d_sample_count(self._e)
         parts = np.zeros(max(n, 0), dtype=_lib.PARTICLE_DTYPE)
         offsets = np.zeros(int(n_events) + 1, dtype=np.int64)
@@ -400,6 +402,7 @@ class Engine:
         pl = _arr(plasma)
         sp = _lib.SampleParams(int(seed), int(n_events), int(fast), float(y_cut))
         self._chk(self.lib.is3d_sample_binned(self._e, C.byref(sp), _dp(pl), int(bool(keep_list))))
+        self._list_events = int(n_events)
         hist, stats = self.sample_hist(), self.sample_stats()
         if not keep_list:
             return hist, stats
@@ -427,6 +430,7 @@ class Engine:
         chain (famod_chains as for the spectra, the sampler's rule); sample_famod_stats() has its counters."""
         sp = _lib.SampleParams(int(seed), int(n_events), 0, float(y_cut))
         self._chk(self.lib.is3d_sample_famod(self._e, C.byref(sp), 0))
+        self._list_events = int(n_events)
         parts, offsets = self._sampled_list(n_events)
         return parts, offsets, self.sample_stats()
 
@@ -434,6 +438,7 @@ class Engine:
         """sample_binned() for df_mode 5: (hist, stats), or (hist, stats, particles, offsets) with keep_list."""
         sp = _lib.SampleParams(int(seed), int(n_events), 0, float(y_cut))
         self._chk(self.lib.is3d_sample_famod(self._e, C.byref(sp), 2 if keep_list else 1))
+        self._list_events = int(n_events)
         hist, stats = self.sample_hist(), self.sample_stats()
         if not keep_list:
             return hist, stats
@@ -448,6 +453,49 @@ class Engine:
     def sample_stats(self):
         s = _lib.SampleStats()
         self._chk(self.lib.is3d_get_sample_stats(self._e, C.byref(s)))
+        return {k: getattr(s, k) for k, _ in s._fields_}
+
+    # --- do_resonance_decays for the sampler: Monte Carlo decays of a particle list ----------
+    def _decayed_list(self):
+        n = self.lib.is3d_sample_count(self._e)
+        parts = np.zeros(max(n, 0), dtype=_lib.PARTICLE_DTYPE)
+        origins = np.zeros(max(n, 0), dtype=np.int64)
+        if n > 0:
+            self._chk(self.lib.is3d_get_particles(self._e, 0, n, C.c_void_p(parts.ctypes.data)))
+            self._chk(self.lib.is3d_get_particle_origins(self._e, 0, n, origins.ctypes.data_as(C.POINTER(C.c_long))))
+        return parts, origins
+
+    def decay_sampled(self, seed, binned=False):
+        """Decay the last sampled list down the chains of set_decays' channels, in place of it.  Returns (particles,
+        offsets, origins, stats): the final hadrons in sample()'s shapes (primaries in their order, each replaced by
+        its leaves), origins[i] = index in the sampled list of the primary record i descends from, and the
+        is3d_decay_list_stats fields.  binned = True (set_sample_bins first): sample_hist() then holds the
+        histograms of the decayed list.  The list is a pure function of (seed, sampled list)."""
+        self._chk(self.lib.is3d_decay_sampled(self._e, int(seed), int(bool(binned))))
+        parts, origins = self._decayed_list()
+        offsets = np.zeros(self._list_events + 1, dtype=np.int64)     # the events of the list the engine holds
+        self._chk(self.lib.is3d_sample_offsets(self._e, offsets.ctypes.data_as(C.POINTER(C.c_long))))
+        return parts, offsets, origins, self.decay_list_stats()
+
+    def decay_particles(self, particles, offsets, seed, binned=False):
+        """decay_sampled() for a caller's list: particles (PARTICLE_DTYPE) with events contiguous, offsets[n_events
+        + 1] into it (offsets[0] may be > 0: a sub-range of events), the records' event field non-decreasing.
+        Returns (particles, offsets, origins, stats); origins index the array given."""
+        parts = np.ascontiguousarray(particles, dtype=_lib.PARTICLE_DTYPE)
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        self._list_events = len(off) - 1
+        self._chk(self.lib.is3d_decay_particles(self._e, int(seed), len(off) - 1, off.ctypes.data_as(C.POINTER(C.c_long)),
+                                                C.c_void_p(parts.ctypes.data), int(bool(binned))))
+        out, origins = self._decayed_list()
+        new_off = np.zeros(len(off), dtype=np.int64)
+        self._chk(self.lib.is3d_sample_offsets(self._e, new_off.ctypes.data_as(C.POINTER(C.c_long))))
+        return out, new_off, origins, self.decay_list_stats()
+
+    def decay_list_stats(self):
+        """The last decay_sampled / decay_particles: primaries, decays, undecayed, dropped_daughters, capped,
+        final_particles, passes, batches, ms_total (device time)."""
+        s = _lib.DecayListStats()
+        self._chk(self.lib.is3d_get_decay_list_stats(self._e, C.byref(s)))
         return {k: getattr(s, k) for k, _ in s._fields_}
 
     def sample_uniforms(self, seed, purpose, cell, event, candidate, n):

@@ -33,7 +33,11 @@ def load():
                                          PL, PL, PD, PL, C.c_char_p, C.c_int]
         lib.is3d_host_write_particle_lists.argtypes = [C.c_char_p, C.c_long, PL, C.c_void_p, PL, PD, C.c_int, C.c_char_p,
                                                        C.c_int]
-        from ._lib import SampleBins, SampleStats
+        from ._lib import DecayListStats, SampleBins, SampleStats
+        lib.is3d_host_sample_binned_decays.argtypes = [C.c_char_p, PI, C.c_int, C.c_int, PL, C.c_long, PD, C.c_long, PL, PD, PL,
+                                                       C.POINTER(SampleStats), C.POINTER(DecayListStats), C.c_char_p, C.c_int]
+        lib.is3d_host_sample_decays.argtypes = [C.c_char_p, PI, C.c_int, C.c_int, C.c_int, C.c_void_p, PL, C.c_long, PL,
+                                                C.c_long, PL, PL, PD, PL, PL, C.POINTER(DecayListStats), C.c_char_p, C.c_int]
         lib.is3d_host_sample_hist_size.argtypes = [C.c_char_p, C.POINTER(SampleBins), PI, PL, PL]
         lib.is3d_host_sample_binned.argtypes = [C.c_char_p, PI, C.c_int, C.c_int, PL, C.c_long, PD, C.c_long, PL, PD, PL,
                                                 C.POINTER(SampleStats), C.c_char_p, C.c_int]
@@ -168,8 +172,13 @@ def sample(workdir, devices=(0,), write_files=True, write_csv=False):
     test_sampler = 1 in the run directory: the particles are binned on the device and never listed, as in the
     reference -- write_files writes the results/sampled/* tree and no particle list, the returned list is empty and
     "hist" holds the histograms (Engine.sample_hist's dict) and "stats" the sampler's counters; "hist" is None for
-    test_sampler = 0."""
-    from ._lib import PARTICLE_DTYPE, SampleBins, SampleStats
+    test_sampler = 0.
+
+    do_resonance_decays = 1: the sampled list is decayed down its chains on the GPU (Engine.decay_sampled with the
+    sampler's seed) before anything is returned or written -- particles, mcid, offsets and the files are the final
+    hadrons', and the dict gains "origins" (index of each record's primary in the sampled list) and "decay_stats";
+    with test_sampler = 1 the final hadrons are binned."""
+    from ._lib import PARTICLE_DTYPE, DecayListStats, SampleBins, SampleStats
     from .engine import split_sample_hist
     lib = load()
     pfile = os.path.join(workdir, "iS3D_parameters.dat")
@@ -183,6 +192,10 @@ def sample(workdir, devices=(0,), write_files=True, write_csv=False):
         binned = param(pfile, "test_sampler") != 0
     except KeyError:
         binned = False
+    try:
+        decays = param(pfile, "do_resonance_decays") == 1
+    except KeyError:
+        decays = False
     if binned:
         PL = C.POINTER(C.c_long)
         bins, npart, nc, nv = SampleBins(), C.c_int(), C.c_long(), C.c_long()
@@ -190,14 +203,15 @@ def sample(workdir, devices=(0,), write_files=True, write_csv=False):
             raise HostError(1, "cannot read iS3D_parameters.dat / PDG/chosen_particles.dat")
         counts = np.zeros(nc.value, dtype=np.int64)
         vn = np.zeros(nv.value)
-        st = SampleStats()
-        rc = lib.is3d_host_sample_binned(workdir.encode(), pdv, len(dv), int(write_files), counts.ctypes.data_as(PL), len(counts),
-                                         vn.ctypes.data_as(C.POINTER(C.c_double)), len(vn), C.byref(nev), C.byref(nt),
-                                         C.byref(seed), C.byref(st), err, 512)
+        st, dst = SampleStats(), DecayListStats()
+        rc = lib.is3d_host_sample_binned_decays(workdir.encode(), pdv, len(dv), int(write_files), counts.ctypes.data_as(PL),
+                                                len(counts), vn.ctypes.data_as(C.POINTER(C.c_double)), len(vn), C.byref(nev),
+                                                C.byref(nt), C.byref(seed), C.byref(st), C.byref(dst), err, 512)
         if rc:
             raise HostError(rc, err.value.decode())
         hist = split_sample_hist(counts, vn, {k: getattr(bins, k) for k, _ in bins._fields_})
-        return dict(particles=np.zeros(0, dtype=PARTICLE_DTYPE), mcid=np.zeros(0, dtype=np.int64),
+        extra = dict(origins=np.zeros(0, dtype=np.int64), decay_stats={k: getattr(dst, k) for k, _ in dst._fields_}) if decays else {}
+        return dict(extra, particles=np.zeros(0, dtype=PARTICLE_DTYPE), mcid=np.zeros(0, dtype=np.int64),
                     offsets=np.zeros(nev.value + 1, dtype=np.int64), n_total=nt.value, n_events=nev.value, seed=seed.value,
                     hist=hist, stats={k: getattr(st, k) for k, _ in st._fields_})
     rc = lib.is3d_host_sample(workdir.encode(), pdv, len(dv), 0, 0, None, None, 0, None, 0, C.byref(n), C.byref(nev),
@@ -208,12 +222,18 @@ def sample(workdir, devices=(0,), write_files=True, write_csv=False):
     mcid = np.zeros(n.value, dtype=np.int64)
     off = np.zeros(nev.value + 1, dtype=np.int64)
     PL = C.POINTER(C.c_long)
-    rc = lib.is3d_host_sample(workdir.encode(), pdv, len(dv), int(write_files), int(write_csv), C.c_void_p(parts.ctypes.data),
-                              mcid.ctypes.data_as(PL), n.value, off.ctypes.data_as(PL), len(off), C.byref(n), C.byref(nev),
-                              C.byref(nt), C.byref(seed), err, 512)
+    origins = np.zeros(n.value if decays else 0, dtype=np.int64)
+    dst = DecayListStats()
+    rc = lib.is3d_host_sample_decays(workdir.encode(), pdv, len(dv), int(write_files), int(write_csv),
+                                     C.c_void_p(parts.ctypes.data), mcid.ctypes.data_as(PL), n.value, off.ctypes.data_as(PL),
+                                     len(off), C.byref(n), C.byref(nev), C.byref(nt), C.byref(seed),
+                                     origins.ctypes.data_as(PL) if decays else None, C.byref(dst), err, 512)
     if rc:
         raise HostError(rc, err.value.decode())
-    return dict(particles=parts, mcid=mcid, offsets=off, n_total=nt.value, n_events=nev.value, seed=seed.value, hist=None)
+    out = dict(particles=parts, mcid=mcid, offsets=off, n_total=nt.value, n_events=nev.value, seed=seed.value, hist=None)
+    if decays:        # do_resonance_decays = 1: the list is the decayed one
+        out.update(origins=origins, decay_stats={k: getattr(dst, k) for k, _ in dst._fields_})
+    return out
 
 
 def write_particle_lists(workdir, particles, offsets, mcid, mass, write_csv=True):
