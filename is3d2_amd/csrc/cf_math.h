@@ -263,6 +263,10 @@ enum Surf : int {
   S_PIXX, S_PIXY, S_PIXN, S_PIYY, S_PIYN, S_BULKPI, S_MUB, S_NB, S_VX, S_VY, S_VN, NSURF
 };
 
+// the PTMA hadron table of aniso_math.h's Newton sums (here so that a kernel argument struct can hold one without that
+// header's __constant__ tables).  etab: the kernel's LDS copy of the 2^(j/kExpTabN) table (device); nullptr on the host
+struct Hadrons { int n; const double *mass, *sign, *degen; const double* etab = nullptr; };
+
 // ---------------------------------------------------------------------------
 // delta-f coefficient tables (DeltafData.cpp)
 // ---------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-// decay.h -- private interface between engine.hip and the resonance-decay feed-down kernels (decay.hip).
+// decay.h -- private interface between engine_post.hip and the resonance-decay feed-down kernels (decay.hip).
 //
 // The method is in decay_math.h (the reference has no working routine).  The engine owns every buffer (DevBuf
 // members) and passes plain pointers; decay.hip packs the plan's tables and launches two kernels per level.

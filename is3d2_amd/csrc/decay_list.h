@@ -1,4 +1,4 @@
-// decay_list.h -- private interface between engine.hip and the Monte Carlo decays of a particle list (decay_list.hip).
+// decay_list.h -- private interface between engine_sample.hip and the Monte Carlo decays of a particle list (decay_list.hip).
 //
 // The method is in decay_mc_math.h.  The engine passes the list on the host and the plan's tables;
 // decay_list.hip owns the working buffers of a call and returns the decayed list on the host.

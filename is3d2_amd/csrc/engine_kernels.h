@@ -1,13 +1,14 @@
 // engine_kernels.h -- the device code of the engine.hip translation unit: the prepass (k_prep, k_aniso, the PTMA
-// warm-start chain kernels, k_famod_b, k_renorm), the slab fold and reduction, operation 0's binning, the yield /
-// density kernels of operation 2 and the Jonah table, each with its argument struct.  The momentum integrals are in
-// kernels.h.  engine.hip includes this header once, after kernels.h and its using-directives; it is not a unit of
-// its own.
+// warm-start chain kernels, k_famod_b, k_renorm), the fallback-cell scan, the slab fold and reduction, the cell costs,
+// the df-coefficient probe and the Jonah table, each with its argument struct (PrepArgs and ChainArgs, which the
+// engine keeps between the stages of a launch, are in engine.h).  The momentum integrals are in kernels.h.  engine.hip includes
+// this header once, after kernels.h and its using-directives; it is not a unit of its own.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "aniso_math.h"
 #include "cf_math.h"
+#include "engine.h"     // PrepArgs, ChainArgs, kFbBlocks
 #include "kernels.h"
 
 namespace {
@@ -19,18 +20,6 @@ struct DevTables {            // device copy of the delta-f tables (pointers int
 // ------------------------------------------------------------------------------------------
 // prepass kernels
 // ------------------------------------------------------------------------------------------
-struct PrepArgs {
-  PrepConsts k;
-  DfTables tb;
-  const double* surf;   // [NSURF][n]
-  double* rec;          // [n][NREC]
-  double* aux;          // PTM/PTB: [9][n]; PTMA: [9][n] Newton inputs
-  long n;               // cells held (the field stride of surf / aux)
-  long c0, c1;          // cells [c0, c1) prepared by this launch
-  int* err;
-  unsigned long long* cnt;  // [0] breakdown [1] pl<0 [2] recon fail [3] iterations
-};
-
 template <int MODE>
 __global__ __launch_bounds__(256) void k_prep(PrepArgs A) {
   const long c = A.c0 + (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -67,14 +56,6 @@ __global__ __launch_bounds__(256) void k_prep(PrepArgs A) {
 #pragma unroll
   for (int f = 0; f < NREC; f++) A.rec[c * NREC + f] = R[f];
 }
-
-struct WaveSum {
-  __device__ double operator()(double v) const {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-  }
-};
 
 // sum over the W wavefronts of a workgroup (W x 64 lanes share one cell's Newton terms): each wave's sums, then the
 // W partials from LDS in wave order (every lane gets the same bits), two barriers per red_all call of up to kRedN
@@ -169,25 +150,6 @@ __global__ __launch_bounds__(64, 1) void k_aniso(AnisoArgs A) {
 // kChainPasses passes a single-wavefront finisher completes any remaining ripple serially (exact).
 constexpr int kChainPasses = 24;
 
-struct ChainArgs {
-  const double* rec; const double* ain; double* sol;   // ain [9][n], sol [6][n]
-  double* sta;           // [4][n] chain state after each cell (prev_ok, lambda, aT, aL)
-  int* info;             // [n] Newton iterations | pl/pt < 0 << 16 | reconstruction failure << 17
-  double* send;          // [2][4][nseg] segment end states, by pass parity
-  double* sstart;        // [4][nseg] the start state of each segment's stored run
-  int* changed;          // [kChainPasses] pass j changed some segment's end state
-  long n, C, L, nspc;    // cells, chains, positions per segment, segments per chain
-  // positions [q0, q1) of every chain (cells [q0 C, q1 C)): the whole chain on one engine; a device group's shard
-  // solves its own range, starting each chain from the end state its predecessor shard pushes into bin
-  long q0, q1;
-  int has_pred;          // q0 > 0: chain position q0 - 1 lives on the previous shard
-  int npass;             // passes enqueued (<= kChainPasses)
-  double* bin;           // [3][4 C + 1] boundary in: end states of position q0 - 1 by pass parity, [2] = final + walk flag
-  double* bout;          // [3][4 C + 1] boundary out: this range's end states (position q1 - 1), same slots
-  Hadrons h;
-  double fp2;
-  int srule;             // the particle sampler's chain rule (aniso_math.h aniso_cell)
-};
 constexpr int kBndSlots = 3;   // bin / bout slots: pass parity 0, 1 and the finisher's
 
 __device__ __forceinline__ bool state_eq(const double* a, const double* b) {
@@ -446,8 +408,6 @@ __global__ __launch_bounds__(256) void k_cell_cost(const double* rec, long n, do
 // writes them in order after the counts of the ranges before it (wave ballots + an LDS prefix per 256 cells) --
 // deterministic, and no host round trip (the count stays on the device).  (One workgroup walking per-thread chunks
 // took 44 ms per config-5 pass, 5e6 cells.)
-constexpr int kFbBlocks = 1024;
-
 __device__ __forceinline__ bool fb_cell(const double* rec, long c) {
   const double* R = rec + c * NREC;
   return R[R_KIND] == 1.0 || (R[R_KIND] == 2.0 && R[R_NARROW] != 0.0);
@@ -491,14 +451,6 @@ __global__ __launch_bounds__(256) void k_fbwrite(const double* rec, long n, cons
     if (t == 0) s_base += s_w[0] + s_w[1] + s_w[2] + s_w[3];
     __syncthreads();
   }
-}
-
-// the ascending fallback-cell list of nw records into list[1 ..], its length into list[0]; list holds nw + 1 +
-// kFbBlocks ints (the per-range counts after the list)
-static void enqueue_fbscan(const double* rec, long nw, int* list, hipStream_t st) {
-  int* bcnt = list + 1 + nw;
-  hipLaunchKernelGGL(k_fbcount, dim3(kFbBlocks), dim3(256), 0, st, rec, nw, bcnt);
-  hipLaunchKernelGGL(k_fbwrite, dim3(kFbBlocks), dim3(256), 0, st, rec, nw, (const int*)bcnt, list + 1, list);
 }
 
 struct ReduceArgs {
@@ -590,135 +542,6 @@ __global__ __launch_bounds__(256) void k_fold(double* acc, const double* src, lo
     for (int z = 0; z < ns; z++) a += src[(long)z * sstride + i];
     acc[i] = a;
   }
-}
-
-// per-cell spacetime bin indices (SpacetimeDistribution.cpp:380-392): keys[0..2][c] = itau, ir, iphi (-1 outside)
-struct KeyArgs {
-  const double *tau, *x, *y; long n;
-  double tau_min, tau_width, r_min, r_width, phip_width;
-  int tau_bins, r_bins, phip_bins;
-  int* keys;
-};
-
-__global__ __launch_bounds__(256) void k_stkeys(KeyArgs A) {
-  const long c = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= A.n) return;
-  const double two_pi = 2.0 * M_PI;
-  const double x = A.x[c], y = A.y[c], tau = A.tau[c];
-  const double r = sqrt(x * x + y * y);
-  double phi = atan2(y, x);
-  if (phi < 0.0) phi += two_pi;
-  const long itau = (int)floor((tau - A.tau_min) / A.tau_width);
-  const long ir = (int)floor((r - A.r_min) / A.r_width);
-  const long iphi = (int)floor(phi / A.phip_width);
-  A.keys[c] = (itau >= 0 && itau < A.tau_bins) ? (int)itau : -1;
-  A.keys[A.n + c] = (ir >= 0 && ir < A.r_bins) ? (int)ir : -1;
-  A.keys[2 * A.n + c] = (iphi >= 0 && iphi < A.phip_bins) ? (int)iphi : -1;
-}
-
-// part[s_orig][e] = prefactor g_s x sum over the cells of entry e = (distribution, thread slice n, bin),
-// cells in ascending order (the reference's per-thread order); perm/offs: CSR built on the host
-struct BinArgs {
-  const double* ycell; long n; int npart;          // ycell: [class][n]; npart sorted species
-  const int *perm; const long* offs; long nent;
-  const int* sorig; const double* sdegen; double prefactor;
-  const int* scls;                                  // sorted species -> integrand class
-  double* part;
-};
-
-__global__ __launch_bounds__(256) void k_stbin(BinArgs A) {
-  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= A.nent * A.npart) return;
-  const int s = (int)(idx / A.nent);
-  const long e = idx % A.nent;
-  const double f = A.prefactor * A.sdegen[s];
-  double acc = 0.0;
-  for (long i = A.offs[e]; i < A.offs[e + 1]; i++) {
-    acc += f * A.ycell[(long)A.scls[s] * A.n + A.perm[i]];
-  }
-  A.part[(long)A.sorig[s] * A.nent + e] = acc;
-}
-
-// ------------------------------------------------------------------------------------------
-// operation = 2 oversampling estimate (ParticleSampler.cpp:447-636, DeltafData.cpp:555-690)
-// ------------------------------------------------------------------------------------------
-struct DensArgs {
-  DfTables tb;
-  const double *gla;              // [alpha][pts] roots then [alpha][pts] weights
-  int gla_alpha, gla_pts;
-  double T, E, P, muB, nB;        // Plasma averages
-  const double *smass, *ssign, *sdegen, *sbaryon; const int* sorig;
-  int npart, df_mode;
-  double two_pi2_hbarC3;
-  double* dens;                   // [3][npart] original species order
-  int* err;
-};
-
-// one wavefront per (mass-sorted) species: lane k holds Gauss-Laguerre node k of each alpha
-__global__ __launch_bounds__(64) void k_densities(DensArgs A) {
-  const int s = blockIdx.x, lane = threadIdx.x;
-  DfCoef df;
-  const int err = df_eval(A.tb, A.T, A.muB, A.E, A.P, 0.0, df);     // DeltafData.cpp:574
-  if (err) { if (lane == 0) atomicMax(A.err, err); return; }
-  const double mass = A.smass[s], sign = A.ssign[s], baryon = A.sbaryon[s];
-  const double mbar = mass / A.T, chem = baryon * (A.muB / A.T);
-  const double* W = A.gla + (long)A.gla_alpha * A.gla_pts;
-  static constexpr int kAlpha[6] = {1, 1, 1, 2, 3, 3};
-  double J[6];
-  WaveSum ws;
-#pragma unroll
-  for (int q = 0; q < 6; q++) {
-    double v = 0.0;
-    for (int k = lane; k < A.gla_pts; k += 64) {
-      const long o = (long)kAlpha[q] * A.gla_pts + k;
-      v += W[o] * gt_term(q, A.gla[o], mbar, chem, sign);
-    }
-    J[q] = ws(v);
-  }
-  if (lane == 0) {
-    double d3[3];
-    species_densities(A.df_mode, df, A.T, A.nB / (A.E + A.P), mass, A.sdegen[s], baryon, J, A.two_pi2_hbarC3, d3);
-    const int so = A.sorig[s];
-    for (int i = 0; i < 3; i++) A.dens[(long)i * A.npart + so] = d3[i];
-  }
-}
-
-struct YieldArgs {
-  PrepConsts k;
-  DfTables tb;
-  const double* surf; long n;
-  const double* dens; int npart;
-  double* partial;                // [gridDim.x] per-block sums
-  int* err;
-};
-
-// one thread per cell, fixed-order tree sum per block (bit-reproducible); the host adds the blocks in order
-__global__ __launch_bounds__(256) void k_yield(YieldArgs A) {
-  __shared__ double red[256];
-  __shared__ double dsum[3];
-  const int tid = threadIdx.x;
-  if (tid < 3) {                  // species sums in species order
-    double a = 0.0;
-    for (int i = 0; i < A.npart; i++) a += A.dens[(long)tid * A.npart + i];
-    dsum[tid] = a;
-  }
-  __syncthreads();
-  const long c = (long)blockIdx.x * 256 + tid;
-  double v = 0.0;
-  if (c < A.n) {
-    double sv[NSURF];
-#pragma unroll
-    for (int f = 0; f < NSURF; f++) sv[f] = A.surf[(long)f * A.n + c];
-    const int err = yield_cell(A.k, A.tb, sv, dsum, &v);
-    if (err) { atomicMax(A.err, err); v = 0.0; }
-  }
-  red[tid] = v;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) red[tid] += red[tid + o];
-    __syncthreads();
-  }
-  if (tid == 0) A.partial[blockIdx.x] = red[0];
 }
 
 // ------------------------------------------------------------------------------------------

@@ -1,0 +1,164 @@
+// engine_post.hip -- what the engine (engine.h) does to or beside the continuous spectra: spin polarization from thermal
+// vorticity and the resonance-decay feed-down.  Host side only: the kernels are in polzn.hip and decay.hip.
+#include <hip/hip_runtime.h>
+
+#include <string>
+
+#include "../../include/is3d_amd.h"
+#include "group.h"
+#include "engine.h"
+
+using namespace is3d;
+
+// ------------------------------------------------------------------------------------------
+// spin polarization from thermal vorticity (mode 5; Polarization.cpp:25-263, kernels in polzn.hip)
+// ------------------------------------------------------------------------------------------
+extern "C" int is3d_set_vorticity(is3d_engine* e, long n, const is3d_vorticity* w) {
+  if (e && e->grp) return is3d::group_set_vorticity(e->grp, n, w);
+  if (!e) return IS3D_ERR_ARG;
+  if (!e->sf.have_surf) return e->fail(IS3D_ERR_STATE, "is3d_set_vorticity: set the surface first");
+  if (!w || n != e->sf.ncell) return e->fail(IS3D_ERR_ARG, "is3d_set_vorticity: the vorticity must have one entry per surface cell");
+  const double* f[6] = {w->wtx, w->wty, w->wtn, w->wxy, w->wxn, w->wyn};
+  for (int k = 0; k < 6; k++)
+    if (!f[k] && n > 0) return e->fail(IS3D_ERR_ARG, "is3d_set_vorticity: vorticity component missing");
+  HIPCHK(e, hipSetDevice(e->device));
+  if (!e->pol.d_vort.reserve(6L * n)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(vorticity) failed");
+  for (int k = 0; k < 6 && n > 0; k++)
+    HIPCHK(e, hipMemcpy(e->pol.d_vort.get() + (size_t)k * n, f[k], n * sizeof(double), hipMemcpyHostToDevice));
+  e->pol.have_vort = true;
+  return IS3D_OK;
+}
+
+extern "C" long is3d_polarization_size(const is3d_engine* e) {
+  const long n = is3d_output_size(e);
+  return n < 0 ? n : 5 * n;
+}
+
+extern "C" int is3d_launch_polarization(is3d_engine* e, double T_avg, double* dev_out, void* stream) {
+  if (e && e->grp) return is3d::group_launch_polarization(e->grp, T_avg, dev_out, stream);
+  if (!e) return IS3D_ERR_ARG;
+  if (!e->in.have_params || !e->in.have_species || !e->in.have_grid)
+    return e->fail(IS3D_ERR_STATE, "polarization: params, species and momentum grid must be set");
+  if (!e->sf.have_surf) return e->fail(IS3D_ERR_STATE, "polarization: no surface set");
+  if (!e->pol.have_vort) return e->fail(IS3D_ERR_STATE, "polarization: no thermal vorticity set for this surface (is3d_set_vorticity)");
+  if (!(T_avg > 0.0)) return e->fail(IS3D_ERR_ARG, "polarization: T_avg must be positive");
+  if (!dev_out) return e->fail(IS3D_ERR_ARG, "null output buffer");
+  HIPCHK(e, hipSetDevice(e->device));
+  if (e->is_stale(D_POLZN)) {
+    const std::string msg = is3d::polzn::tables_build(e->pol.tables, e->in.p.dimension, e->in.classes, e->in.mass, e->in.sign, e->in.pT, e->in.phi,
+                                                      e->in.y, e->in.eta, e->in.eta_w);
+    if (!msg.empty()) return e->fail(IS3D_ERR_ARG, "polarization: " + msg);
+    e->rebuilt(D_POLZN);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const long n = e->sf.ncell;
+  long wlo, whi;
+  cell_window(e, wlo, whi);
+  const long nw = whi - wlo;
+  const int rc = begin_stats(e, nw, st);
+  if (rc) return rc;
+  HIPCHK(e, hipEventRecord(e->ws.ev[1].get(), st));     // no prepass: k_polzn reads the surface itself
+  if (nw == 0) {
+    HIPCHK(e, hipMemsetAsync(dev_out, 0, e->pol.tables.out_size() * sizeof(double), st));
+    HIPCHK(e, hipEventRecord(e->ws.ev[2].get(), st));
+  } else {
+    const is3d::polzn::Plan P = is3d::polzn::make_plan(e->pol.tables, nw, e->ws.max_splits, e->ws.split_bytes, e->ws.slab_bytes);
+    if (!P.ok) return e->fail(IS3D_ERR_ARG, "polarization: the phi / y / eta tables do not fit a workgroup's LDS tile");
+    if (!e->ws.d_slab.reserve(P.nsplit * P.sstride)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(slabs) failed");
+    e->ws.last_nchunk = 0;
+    e->ws.last_nsplit = P.nsplit;
+    e->ws.last_nslab = P.nsplit;
+    HIPCHK(e, is3d::polzn::enqueue(e->pol.tables, P, e->sf.d_surf, e->pol.d_vort.get(), n, wlo, whi, T_avg, e->ws.d_slab.get(), dev_out, st, e->ws.ev[2].get()));
+  }
+  HIPCHK(e, hipEventRecord(e->ws.ev[3].get(), st));
+  e->ws.launched = true;
+  return IS3D_OK;
+}
+
+extern "C" int is3d_calculate_polarization(is3d_engine* e, double T_avg, double* S_out) {
+  if (e && e->grp) return is3d::group_calculate_polarization(e->grp, T_avg, S_out);
+  if (!e || !S_out) return e ? e->fail(IS3D_ERR_ARG, "null output") : IS3D_ERR_ARG;
+  const long outsize = is3d_polarization_size(e);
+  if (outsize < 0) return e->fail(IS3D_ERR_STATE, "polarization: params, species and momentum grid must be set");
+  return calculate(e, outsize, S_out, [&](double* d) { return is3d_launch_polarization(e, T_avg, d, nullptr); });
+}
+
+// ------------------------------------------------------------------------------------------
+// resonance-decay feed-down of the continuous spectra (do_resonance_decays; method in decay_math.h, kernels in decay.hip)
+// ------------------------------------------------------------------------------------------
+extern "C" int is3d_set_decays(is3d_engine* e, int n, const is3d_decay_channel* ch) {
+  if (e && e->grp) return is3d::group_set_decays(e->grp, n, ch);
+  if (!e) return IS3D_ERR_ARG;
+  if (!e->in.have_species || !e->in.have_grid) return e->fail(IS3D_ERR_STATE, "is3d_set_decays: set the species and the momentum grid first");
+  if (n < 0 || (n > 0 && !ch)) return e->fail(IS3D_ERR_ARG, "is3d_set_decays: bad channel table");
+  e->input_changed(IN_DECAYS);     // no decays are set until this call has succeeded
+  std::string msg = is3d::decay::check_grid((int)e->in.pT.size(), e->in.pT.data(), (int)e->in.phi.size(), e->in.phi.data(), 0, nullptr);
+  if (!msg.empty()) return e->fail(IS3D_ERR_ARG, "is3d_set_decays: " + msg);
+  e->fd.rule = is3d::decay::make_rule();
+  msg = is3d::decay::build_plan(e->fd.plan, e->fd.rule, (int)e->in.mass.size(), e->in.mass.data(), n, ch);
+  if (!msg.empty()) return e->fail(IS3D_ERR_ARG, "is3d_set_decays: " + msg);
+  e->fd.ch.assign(ch, ch + n);
+  e->fd.stats = e->fd.plan.stats;
+  e->rebuilt(D_DECAY_PLAN);
+  return IS3D_OK;
+}
+
+extern "C" int is3d_get_decay_stats(const is3d_engine* e, is3d_decay_stats* out) {
+  if (e && e->grp) return out ? is3d::group_get_decay_stats(e->grp, out) : IS3D_ERR_ARG;
+  if (!e || !out) return IS3D_ERR_ARG;
+  if (!e->have_decays()) return IS3D_ERR_STATE;
+  *out = e->fd.stats;
+  return IS3D_OK;
+}
+
+extern "C" int is3d_launch_feeddown(is3d_engine* e, double* dev_inout, void* stream) {
+  if (e && e->grp) return is3d::group_launch_feeddown(e->grp, dev_inout, stream);
+  if (!e) return IS3D_ERR_ARG;
+  if (!e->in.have_params || !e->in.have_species || !e->in.have_grid)
+    return e->fail(IS3D_ERR_STATE, "feed-down: params, species and momentum grid must be set");
+  if (!e->have_decays()) return e->fail(IS3D_ERR_STATE, "feed-down: no decay channels set (is3d_set_decays)");
+  if (!dev_inout) return e->fail(IS3D_ERR_ARG, "null spectra buffer");
+  HIPCHK(e, hipSetDevice(e->device));
+  const int ny = e->in.p.dimension == 3 ? (int)e->in.y.size() : 1;
+  if (e->is_stale(D_DECAY_PACK)) {
+    if (ny < 1) return e->fail(IS3D_ERR_ARG, "feed-down: empty y table");
+    const std::string msg = is3d::decay::check_grid((int)e->in.pT.size(), e->in.pT.data(), (int)e->in.phi.size(), e->in.phi.data(), ny, e->in.y.data());
+    if (!msg.empty()) return e->fail(IS3D_ERR_ARG, "feed-down: " + msg);
+    e->fd.pack = is3d::decay::pack(e->fd.plan, e->fd.rule, e->in.pT, e->in.phi, ny, e->in.y);
+    const is3d::decay::Packed& K = e->fd.pack;
+    if (K.nb < 1 || K.lds > 64 * 1024) return e->fail(IS3D_ERR_ARG, "feed-down: the phi table does not fit a workgroup's LDS");
+    if (!e->fd.d_d.reserve((long)K.d.size()) || !e->fd.d_i.reserve((long)K.i.size()))
+      return e->fail(IS3D_ERR_DEVICE, "hipMalloc(decay tables) failed");
+    HIPCHK(e, hipMemcpy(e->fd.d_d.get(), K.d.data(), K.d.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(e, hipMemcpy(e->fd.d_i.get(), K.i.data(), K.i.size() * sizeof(int), hipMemcpyHostToDevice));
+    e->rebuilt(D_DECAY_PACK);
+  }
+  const long per = (long)e->in.pT.size() * ny;
+  for (int l = 0; l < e->fd.plan.levels(); l++)
+    if ((long)(e->fd.plan.lvl_r0[l + 1] - e->fd.plan.lvl_r0[l]) * per > 0x7fffffffL)
+      return e->fail(IS3D_ERR_ARG, "feed-down: a level has more than 2^31 workgroups");
+  if (!e->fd.d_log.reserve(is3d_output_size(e))) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(decay logs) failed");
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(e, hipEventRecord(e->fd.ev[0].get(), st));
+  HIPCHK(e, is3d::decay::enqueue(e->fd.plan, e->fd.pack, e->fd.d_d.get(), e->fd.d_i.get(), dev_inout, e->fd.d_log.get(), st));
+  HIPCHK(e, hipEventRecord(e->fd.ev[1].get(), st));
+  e->fd.launched = true;
+  return IS3D_OK;
+}
+
+extern "C" int is3d_decay_feeddown(is3d_engine* e, double* dN) {
+  if (e && e->grp) return is3d::group_decay_feeddown(e->grp, dN);
+  if (!e || !dN) return e ? e->fail(IS3D_ERR_ARG, "null spectra array") : IS3D_ERR_ARG;
+  const long n = is3d_output_size(e);
+  if (n < 0) return e->fail(IS3D_ERR_STATE, "feed-down: params, species and momentum grid must be set");
+  if (!e->have_decays()) return e->fail(IS3D_ERR_STATE, "feed-down: no decay channels set (is3d_set_decays)");
+  HIPCHK(e, hipSetDevice(e->device));
+  if (!e->fd.d_io.reserve(n)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(spectra) failed");
+  HIPCHK(e, hipMemcpy(e->fd.d_io.get(), dN, n * sizeof(double), hipMemcpyHostToDevice));
+  int rc = is3d_launch_feeddown(e, e->fd.d_io.get(), nullptr);
+  if (rc) return rc;
+  rc = is3d_finish(e);
+  if (rc) return rc;
+  HIPCHK(e, hipMemcpy(dN, e->fd.d_io.get(), n * sizeof(double), hipMemcpyDeviceToHost));
+  return IS3D_OK;
+}

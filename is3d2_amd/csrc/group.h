@@ -1,4 +1,4 @@
-// group.h -- private interface between engine.hip's C ABI and the multi-device engine (group.hip).
+// group.h -- private interface between the engine units' C ABI (engine.h) and the multi-device engine (group.hip).
 //
 // is3d_create_devices(n, devices) returns an is3d_engine whose `grp` holds one engine per device
 // (the multi-GPU fan-out happens inside the compute call).  Every setter is forwarded to
@@ -14,6 +14,7 @@
 
 namespace is3d {
 struct Group;
+struct SampledList;
 // shard cost of a cell with u.dsigma <= 0 (skipped by every kernel, MomentumSpectra.cpp:132): its record prep only
 constexpr double kSkipCost = 0.02;
 
@@ -62,28 +63,23 @@ int group_calculate_polarization(Group* g, double T_avg, double* S_out);
 int group_sample(Group* g, const is3d_sample_params* p, const double* plasma, int binned);
 // is3d_sample_famod (df_mode 5): the same merge; each shard reconstructs (lambda, aT, aL) itself first
 int group_sample_famod(Group* g, const is3d_sample_params* p, int binned);
-int group_get_sample_famod_stats(const Group* g, is3d_sample_famod_stats* out);
 int group_set_sample_bins(Group* g, const is3d_sample_bins* b);
 long group_sample_hist_size(const Group* g, long* n_counts, long* n_vn);
-int group_get_sample_hist(const Group* g, long* counts, double* vn);
-long group_sample_count(const Group* g);
-int group_sample_offsets(const Group* g, long* offsets);
-int group_get_particles(const Group* g, long first, long count, is3d_particle* out);
-int group_get_sample_stats(const Group* g, is3d_sample_stats* out);
+// the group's list (sampled_list.h): what every list getter of a device-list engine reads
+const SampledList& group_list(const Group* g);
 // resonance-decay feed-down: runs on devices[0] (shard 0), on the summed spectra; group_finish after
 // group_launch_feeddown finishes that shard alone
 int group_set_decays(Group* g, int n, const is3d_decay_channel* ch);
 int group_launch_feeddown(Group* g, double* dev_inout, void* stream);
 int group_decay_feeddown(Group* g, double* dN_inout);
 int group_get_decay_stats(const Group* g, is3d_decay_stats* out);
-// Monte Carlo decays of a particle list: run on devices[0] (shard 0) over the merged list, which then replaces it
+// Monte Carlo decays of a particle list: run on devices[0] (shard 0) over the merged list; the group takes shard 0's
+// decayed list, origins and stats in place of it
 int group_decay_particles(Group* g, long seed, int n_events, const long* offsets, const is3d_particle* in, int bin);
 int group_decay_sampled(Group* g, long seed, int bin);
-int group_get_particle_origins(const Group* g, long first, long count, long* origin);
-int group_get_decay_list_stats(const Group* g, is3d_decay_list_stats* out);
 }  // namespace is3d
 
-// engine.hip internals the group uses on its shard engines (not part of the public ABI)
+// engine internals the group uses on its shard engines (not part of the public ABI)
 // staged launch (engine.hip launch_begin / chain_pass / chain_end / launch_end): a shard solves positions
 // [q0, q1) of PTMA's warm-start chains (q1 < 0: the whole chains), its first segments starting from the end
 // states the previous shard pushes into its boundary slots (has_pred)
@@ -98,8 +94,8 @@ long is3d_internal_chain_bnd_bytes(const is3d_engine* e);
 // (binned: as group_sample)
 int is3d_internal_sample(is3d_engine* e, const is3d_sample_params* p, const double* plasma, long cell_base, int binned);
 int is3d_internal_sample_famod(is3d_engine* e, const is3d_sample_params* p, long cell_base, int binned);
-// the histogram of the last binned call in its integer form: n_counts counts, then the n_vn fixed-point vn sums
-const long long* is3d_internal_sample_hist(const is3d_engine* e);
+// a shard's list, histogram and stats of its last sample or list-decay call
+const is3d::SampledList& is3d_internal_sampled_list(const is3d_engine* e);
 extern "C" {
 // engine-owned copy of cells [lo, lo + n) of a field-major device surface (25 x src_n doubles) on src_device
 int is3d_internal_copy_surface(is3d_engine* e, long n, const double* src, long src_n, int src_device, long lo);

@@ -26,6 +26,7 @@
 
 #include "devbuf.h"
 #include "group.h"
+#include "sampled_list.h"
 
 namespace is3d {
 
@@ -64,17 +65,9 @@ struct Group {
   bool launched = false;
   bool fd_launched = false;           // group_launch_feeddown: shard 0 alone has work in flight
   is3d_stats stats{};
-  // particle sampler: the merged list of the last group_sample
-  std::vector<is3d_particle> particles;
-  std::vector<long> particle_offsets;
-  is3d_sample_stats sstats{};
-  is3d_sample_famod_stats sfstats{};
-  bool sampled = false, sampled_famod = false;
-  bool decayed = false;               // the list is shard 0's decayed list (group_decay_particles)
-  // ... and the sum of the shards' integer histograms of the last binned call (counts, then fixed-point vn sums)
-  std::vector<long long> hist;
-  long hist_nc = 0, hist_nv = 0;
-  bool binned = false;
+  // particle sampler: the shards' lists of the last group_sample merged per event, their stats and integer histograms
+  // summed; after a list decay, shard 0's decayed list
+  SampledList list;
   std::string err;
   int fail(int code, const std::string& m) { err = m; return code; }
   int shard_fail(int k, int rc) {
@@ -504,47 +497,26 @@ int group_decay_feeddown(Group* g, double* dN_inout) {
 }
 int group_get_decay_stats(const Group* g, is3d_decay_stats* out) { return is3d_get_decay_stats(g->sh[0], out); }
 
-// shard 0 decays the list and the group takes its result: list, offsets and, for bin = 1, the histogram
-int group_decay_particles(Group* g, long seed, int n_events, const long* offsets, const is3d_particle* in, int bin) {
-  is3d_engine* e0 = g->sh[0];
-  int rc = is3d_decay_particles(e0, seed, n_events, offsets, in, bin);
+// shard 0 decays the list `in` and the group takes its result as a whole: list, offsets, origins, decay stats and, for
+// bin = 1, the histogram (the group's sample stats stay)
+static int decay_on_shard0(Group* g, long seed, int n_events, const long* offsets, const is3d_particle* in, int bin) {
+  const int rc = is3d_decay_particles(g->sh[0], seed, n_events, offsets, in, bin);
   if (rc) return g->shard_fail(0, rc);
-  const long n = is3d_sample_count(e0);
-  std::vector<is3d_particle> parts((size_t)std::max(n, 0L));
-  std::vector<long> off((size_t)n_events + 1, 0);
-  rc = is3d_sample_offsets(e0, off.data());
-  if (!rc && n > 0) rc = is3d_get_particles(e0, 0, n, parts.data());
-  if (rc) return g->shard_fail(0, rc);
-  if (bin) {
-    const long long* h = is3d_internal_sample_hist(e0);
-    if (!h || is3d_sample_hist_size(e0, &g->hist_nc, &g->hist_nv) < 0) return g->shard_fail(0, IS3D_ERR_STATE);
-    g->hist.assign(h, h + g->hist_nc + g->hist_nv);
-    g->binned = true;
-  }
-  g->particles.swap(parts);
-  g->particle_offsets.swap(off);
-  g->sampled = true;
-  g->sampled_famod = false;            // a caller's list, as on one engine (group_decay_sampled puts it back)
-  g->decayed = true;
+  SampledList d = is3d_internal_sampled_list(g->sh[0]);
+  g->list.replace_decayed(d, bin != 0);
   return IS3D_OK;
 }
-int group_decay_sampled(Group* g, long seed, int bin) {
-  if (!g->sampled || g->particle_offsets.empty() || (g->particles.empty() && g->sstats.kept > 0))
-    return g->fail(IS3D_ERR_STATE, "is3d_decay_sampled: no sampled list (is3d_sample, or a binned call that keeps the list)");
-  const std::vector<is3d_particle> in = g->particles;     // shard 0's call replaces the group's list
-  const std::vector<long> off = g->particle_offsets;
-  const bool famod = g->sampled_famod;
-  const int rc = group_decay_particles(g, seed, (int)off.size() - 1, off.data(), in.data(), bin);
-  if (!rc) g->sampled_famod = famod;
+int group_decay_particles(Group* g, long seed, int n_events, const long* offsets, const is3d_particle* in, int bin) {
+  const int rc = decay_on_shard0(g, seed, n_events, offsets, in, bin);
+  if (!rc) g->list.famod = false;      // a caller's list, as on one engine
   return rc;
 }
-int group_get_particle_origins(const Group* g, long first, long count, long* origin) {
-  if (!g->sampled || !g->decayed) return IS3D_ERR_STATE;
-  return is3d_get_particle_origins(g->sh[0], first, count, origin);
-}
-int group_get_decay_list_stats(const Group* g, is3d_decay_list_stats* out) {
-  if (!g->sampled || !g->decayed) return IS3D_ERR_STATE;
-  return is3d_get_decay_list_stats(g->sh[0], out);
+int group_decay_sampled(Group* g, long seed, int bin) {
+  const SampledList& l = g->list;
+  if (!l.has_list())
+    return g->fail(IS3D_ERR_STATE, "is3d_decay_sampled: no sampled list (is3d_sample, or a binned call that keeps the list)");
+  return decay_on_shard0(g, seed, (int)l.offsets.size() - 1, l.offsets.data(),
+                         reinterpret_cast<const is3d_particle*>(l.particles.data()), bin);
 }
 
 int group_finish(Group* g) {
@@ -701,26 +673,19 @@ int group_total_yield(Group* g, const double* plasma, double y_cut, double* n_to
 }
 
 int group_set_sample_bins(Group* g, const is3d_sample_bins* b) {
-  g->binned = false;
+  g->list.bins_changed();
   return each(g, [&](is3d_engine* e) { return is3d_set_sample_bins(e, b); });
 }
 
 long group_sample_hist_size(const Group* g, long* n_counts, long* n_vn) { return is3d_sample_hist_size(g->sh[0], n_counts, n_vn); }
 
-int group_get_sample_hist(const Group* g, long* counts, double* vn) {
-  if (!g->binned) return IS3D_ERR_STATE;
-  for (long i = 0; i < g->hist_nc; i++) counts[i] = (long)g->hist[(size_t)i];
-  for (long i = 0; i < g->hist_nv; i++) vn[i] = (double)g->hist[(size_t)(g->hist_nc + i)] * (1.0 / 4294967296.0);   // sampler_bins.h kVnQuantum
-  return IS3D_OK;
-}
+const SampledList& group_list(const Group* g) { return g->list; }
 
 // famod (is3d_sample_famod): with famod_chains > 0 every shard holds the whole surface, solves the whole chain itself
 // and samples its window; with famod_chains = 0 the shards hold their windows and solve them cold
 static int sample_shards(Group* g, const is3d_sample_params* p, const double* plasma, int binned, bool famod) {
-  g->sampled = false;
-  g->sampled_famod = false;
-  g->decayed = false;
-  g->binned = false;
+  SampledList& out = g->list;
+  out.begin_sample();
   if (!p || (!famod && !plasma)) return g->fail(IS3D_ERR_ARG, "is3d_sample: null argument");
   if (famod && (binned < 0 || binned > 2)) return g->fail(IS3D_ERR_ARG, "is3d_sample_famod: binned must be 0, 1 or 2");
   if (stale_split(g)) return g->fail(IS3D_ERR_STATE, kStaleSplit);
@@ -731,56 +696,45 @@ static int sample_shards(Group* g, const is3d_sample_params* p, const double* pl
     return famod ? is3d_internal_sample_famod(g->sh[k], p, base, binned) : is3d_internal_sample(g->sh[k], p, plasma, base, binned);
   });
   if (rc) return rc;
+  std::vector<const SampledList*> sh(K);
+  for (int k = 0; k < K; k++) sh[k] = &is3d_internal_sampled_list(g->sh[k]);
   const long nev = p->n_events;
-  std::vector<std::vector<long>> off(K, std::vector<long>((size_t)nev + 1, 0));
   long total = 0;
   is3d_sample_stats agg{};
   for (int k = 0; k < K; k++) {
-    is3d_sample_stats s{};
-    int r = is3d_sample_offsets(g->sh[k], off[k].data());
-    if (!r) r = is3d_get_sample_stats(g->sh[k], &s);
-    if (r) return g->shard_fail(k, r);
-    total += off[k][nev];
+    const is3d_sample_stats& s = sh[k]->stats;
+    total += sh[k]->offsets[nev];
     agg.cells += s.cells; agg.breakdown += s.breakdown; agg.candidates += s.candidates; agg.kept += s.kept;
     agg.proposals += s.proposals; agg.acceptances += s.acceptances; agg.capped += s.capped; agg.clamped += s.clamped;
     agg.batches += s.batches;
   }
-  g->particles.resize((size_t)total);
-  g->particle_offsets.assign((size_t)nev + 1, 0);
-  long at = 0;
+  // per event, the shard lists in shard order
+  out.particles.clear();
+  out.particles.reserve((size_t)total);
+  out.offsets.assign((size_t)nev + 1, 0);
   for (long ev = 0; ev < nev; ev++) {
-    g->particle_offsets[ev] = at;
-    for (int k = 0; k < K; k++) {
-      const long n = off[k][ev + 1] - off[k][ev];
-      const int r = is3d_get_particles(g->sh[k], off[k][ev], n, g->particles.data() + at);
-      if (r) return g->shard_fail(k, r);
-      at += n;
-    }
+    out.offsets[ev] = (long)out.particles.size();
+    for (int k = 0; k < K; k++)
+      out.particles.insert(out.particles.end(), sh[k]->particles.begin() + sh[k]->offsets[ev],
+                           sh[k]->particles.begin() + sh[k]->offsets[ev + 1]);
   }
-  g->particle_offsets[nev] = at;
-  g->sstats = agg;
+  out.offsets[nev] = (long)out.particles.size();
+  out.stats = agg;
   if (famod) {       // the whole chain on every shard: its counters once (shard 0's); windows solved cold: their sum
     is3d_sample_famod_stats f{};
     for (int k = 0; k < (g->full ? 1 : K); k++) {
-      is3d_sample_famod_stats s{};
-      const int r = is3d_get_sample_famod_stats(g->sh[k], &s);
-      if (r) return g->shard_fail(k, r);
+      const is3d_sample_famod_stats& s = sh[k]->famod_stats;
       f.plpt_negative += s.plpt_negative; f.reconstruction_fail += s.reconstruction_fail; f.iterations += s.iterations;
     }
-    g->sfstats = f;
+    out.famod_stats = f;
   }
   if (binned) {      // integer sums: exact, so the shard order plays no part
-    if (is3d_sample_hist_size(g->sh[0], &g->hist_nc, &g->hist_nv) < 0) return g->shard_fail(0, IS3D_ERR_STATE);
-    g->hist.assign((size_t)(g->hist_nc + g->hist_nv), 0);
-    for (int k = 0; k < K; k++) {
-      const long long* h = is3d_internal_sample_hist(g->sh[k]);
-      if (!h) return g->shard_fail(k, IS3D_ERR_STATE);
-      for (size_t i = 0; i < g->hist.size(); i++) g->hist[i] += h[i];
-    }
-    g->binned = true;
+    out.hist_nc = sh[0]->hist_nc; out.hist_nv = sh[0]->hist_nv;
+    out.hist.assign(sh[0]->hist.size(), 0);
+    for (int k = 0; k < K; k++)
+      for (size_t i = 0; i < out.hist.size(); i++) out.hist[i] += sh[k]->hist[i];
   }
-  g->sampled = true;
-  g->sampled_famod = famod;
+  out.commit_sample(famod, binned != 0);
   return IS3D_OK;
 }
 
@@ -788,34 +742,6 @@ int group_sample(Group* g, const is3d_sample_params* p, const double* plasma, in
   return sample_shards(g, p, plasma, binned, false);
 }
 int group_sample_famod(Group* g, const is3d_sample_params* p, int binned) { return sample_shards(g, p, nullptr, binned, true); }
-
-int group_get_sample_famod_stats(const Group* g, is3d_sample_famod_stats* out) {
-  if (!g->sampled || !g->sampled_famod) return IS3D_ERR_STATE;
-  *out = g->sfstats;
-  return IS3D_OK;
-}
-
-long group_sample_count(const Group* g) { return g->sampled ? (long)g->particles.size() : -1; }
-
-int group_sample_offsets(const Group* g, long* offsets) {
-  if (!offsets) return IS3D_ERR_ARG;
-  if (!g->sampled) return IS3D_ERR_STATE;
-  std::copy(g->particle_offsets.begin(), g->particle_offsets.end(), offsets);
-  return IS3D_OK;
-}
-
-int group_get_particles(const Group* g, long first, long count, is3d_particle* out) {
-  if (!g->sampled) return IS3D_ERR_STATE;
-  if (first < 0 || count < 0 || first + count > (long)g->particles.size() || (!out && count > 0)) return IS3D_ERR_ARG;
-  std::copy(g->particles.begin() + first, g->particles.begin() + first + count, out);
-  return IS3D_OK;
-}
-
-int group_get_sample_stats(const Group* g, is3d_sample_stats* out) {
-  if (!g->sampled) return IS3D_ERR_STATE;
-  *out = g->sstats;
-  return IS3D_OK;
-}
 
 int group_get_jonah_table(const Group* g, double* l2, double* z, double* bp, double* bpmax) {
   return is3d_get_jonah_table(g->sh[0], l2, z, bp, bpmax);

@@ -12,6 +12,15 @@ namespace kern {
 
 constexpr int kBlock = 256;
 
+// sum over the 64 lanes of a wavefront (every lane gets the same bits)
+struct WaveSum {
+  __device__ double operator()(double v) const {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+  }
+};
+
 // ---- sizing parameters: plain numbers with no code path behind them, overridable for A/B builds
 // (make variant EXTRA=-DIS3D_KTILE=...).  How each value was chosen is noted where it is used.
 #ifndef IS3D_KTILE
@@ -39,7 +48,7 @@ constexpr int kBlock = 256;
 #define IS3D_DNDX_MOD_UNROLL 2     // k_dndx modified lanes: fours of phi points per unrolled loop trip
 #endif
 #ifndef IS3D_DNDX_TILE_MOD
-#define IS3D_DNDX_TILE_MOD 4       // k_dndx: cells per record tile of the modified launch (engine.hip sizes its LDS the same way)
+#define IS3D_DNDX_TILE_MOD 4       // k_dndx: cells per record tile of the modified launch (engine_dndx.hip sizes its LDS the same way)
 #endif
 #ifndef IS3D_DNDX_TILE
 #define IS3D_DNDX_TILE 8           // k_dndx: cells per record tile of the Grad / RTA-CE launches

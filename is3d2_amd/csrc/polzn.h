@@ -1,4 +1,4 @@
-// polzn.h -- private interface between engine.hip and the spin-polarization kernels (polzn.hip).
+// polzn.h -- private interface between engine_post.hip and the spin-polarization kernels (polzn.hip).
 //
 // The mode-5 output of the reference (EmissionFunctionArray::calculate_spin_polzn, Polarization.cpp:25-263):
 // S_t, S_x, S_y, S_n, Snorm [species][pT][phi][y] summed over freeze-out cells.  The math and the two deliberate

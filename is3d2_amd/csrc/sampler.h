@@ -1,4 +1,4 @@
-// sampler.h -- private interface between engine.hip and the operation = 2 particle sampler (sampler.hip).
+// sampler.h -- private interface between engine_sample.hip and the operation = 2 particle sampler (sampler.hip).
 //
 // The GPU form of EmissionFunctionArray::sample_dN_pTdpTdphidy (ParticleSampler.cpp:638-1134; df_mode 1-4) and of
 // sample_dN_pTdpTdphidy_famod (:1138-1627; df_mode 5, Config::sol).  The

@@ -236,3 +236,114 @@ def test_device_list_engine_operations_interleaved():
     for i, (name, call) in enumerate(calls):
         assert same(call(e), ref[name]), (i, name)
     e.close()
+
+
+# a decay table over pikp: K -> pi pi (open in floating point) and the pion's stability marker
+PIKP_CHANNELS = [dict(parent=1, n_body=2, daughter=[0, 0], branching=1.0, mass_parent=0.494, width_parent=0.0,
+                      mass=[0.138, 0.138], width=[0.0, 0.0]),
+                 dict(parent=0, n_body=1, daughter=[0], branching=1.0, mass_parent=0.138, width_parent=0.0,
+                      mass=[0.138], width=[0.0])]
+
+
+def test_changed_inputs_match_a_fresh_engine():
+    """One input of a live engine changed at a time -- the species list, the classes switch, the momentum grid, the
+    params (df_mode, dimension), the PDG, the Gauss-Laguerre table, the delta-f tables, the decay table -- and after
+    each change every operation that applies: what an input invalidates (engine.h kInvalidates) must leave the engine
+    computing, bit for bit, what a fresh engine given the same final inputs computes.  A new species list drops the
+    decay channels, as on a fresh engine that never had any (tests/test_gpu_decay.py)."""
+    from is3d2_amd import data as D
+
+    s = dict(surf(64, 35))
+    s.update(zip(_lib.VORTICITY_FIELDS, synth.vorticity(64, 5)))
+    plasma = surface_averages(s)
+    spec0 = make_spec(hrg_eos=2, chosen="pikp", df_mode=1, dimension=2, pT="pT24", phi="phi24", eta="eta24")
+    state = dict(spec=spec0, classes=True, T_avg=T_AVG, decays=None)
+
+    def fresh(st):
+        e = build_engine(st["spec"], s, T_avg=st["T_avg"], species_classes=st["classes"])
+        e.set_sample_bins()
+        if st["decays"] is not None:
+            e.set_decays(st["decays"])
+        return e
+
+    def attempt(f):
+        try:
+            return f()
+        except IS3DError as err:       # an error is a result too: the live engine must give the fresh one's
+            return ("error", err.code)
+
+    def failed(r):
+        return isinstance(r, tuple) and len(r) == 2 and isinstance(r[0], str) and r[0] == "error"
+
+    def operations(e, st):
+        out = {"spectra": attempt(e.calculate_spectra),
+               "polarization": attempt(lambda: e.calculate_polarization(T_AVG)),
+               "sample_binned": attempt(lambda: e.sample_binned(3, 2, 2, 0, plasma)),
+               "sample": attempt(lambda: e.sample(3, 2, 2, 0, plasma))}
+        out["decay_sampled"] = attempt(lambda: e.decay_sampled(5)[:3])      # the stats carry a device time
+        out["feeddown"] = attempt(lambda: e.feeddown(out["spectra"]))
+        out["decay_stats"] = attempt(lambda: {k: v for k, v in e.decay_stats().items() if k != "ms_total"})
+        return out
+
+    def respec(**kw):
+        sp = dict(state["spec"])
+        sp.update(kw)
+        return sp
+
+    sp3 = spec0["species"]
+    sp2 = {k: v[:2].copy() for k, v in sp3.items()}
+    species = lambda e, sp: e.set_species(sp["mass"], sp["sign"], sp["degen"], sp["baryon"])
+    phi32, phi32_w = D.grid("phi32")
+    pdg = spec0["pdg"]
+    pdg_cut = {k: v[:-7].copy() for k, v in pdg.items()}
+    gla64 = D.gauss_laguerre(64)
+
+    def grid(e, sp):
+        e.set_momentum_grid(sp["pT"], sp["phi"], sp["y"], sp["eta"], sp["eta_w"])
+        e.set_momentum_weights(sp["pT_w"], sp["phi_w"])      # the weights are the grid's
+
+    def params(**kw):
+        return dict(state["spec"]["params"], **kw)
+
+    # (name, the new state's entries, the one setter call on the live engine)
+    steps = [
+        ("species: two of three", dict(spec=lambda: respec(species=sp2)), lambda e, st: species(e, sp2)),
+        ("species: back", dict(spec=lambda: respec(species=sp3)), lambda e, st: species(e, sp3)),
+        ("classes off", dict(classes=lambda: False), lambda e, st: e.set_species_classes(False)),
+        ("grid phi32", dict(spec=lambda: respec(phi=phi32, phi_w=phi32_w)), lambda e, st: grid(e, st["spec"])),
+        ("df_mode 2", dict(spec=lambda: respec(params=params(df_mode=2))), lambda e, st: e.set_params(**st["spec"]["params"])),
+        ("dimension 3", dict(spec=lambda: respec(params=params(dimension=3))), lambda e, st: e.set_params(**st["spec"]["params"])),
+        ("dimension 2", dict(spec=lambda: respec(params=params(dimension=2))), lambda e, st: e.set_params(**st["spec"]["params"])),
+        ("pdg", dict(spec=lambda: respec(pdg=pdg_cut)),
+         lambda e, st: e.set_pdg(pdg_cut["mass"], pdg_cut["sign"], pdg_cut["gspin"], pdg_cut["baryon"])),
+        ("gauss-laguerre 64", dict(spec=lambda: respec(gla=gla64)), lambda e, st: e.set_gauss_laguerre(*gla64)),
+        ("df tables at another T_avg", dict(T_avg=lambda: 0.16), lambda e, st: e.set_df_tables(*st["spec"]["df"], 0.16)),
+        ("decays", dict(decays=lambda: PIKP_CHANNELS), lambda e, st: e.set_decays(PIKP_CHANNELS)),
+        ("species with decays set", dict(spec=lambda: respec(species=sp2), decays=lambda: None), lambda e, st: species(e, sp2)),
+    ]
+    live = fresh(state)
+    got = operations(live, state)
+    assert np.any(got["spectra"] != 0.0) and np.any(got["polarization"] != 0.0) and len(got["sample"][0]) > 0
+    assert got["feeddown"] == ("error", _lib.IS3D_ERR_STATE) and got["decay_sampled"] == ("error", _lib.IS3D_ERR_STATE)
+    for name, change, setter in steps:
+        state.update({k: v() for k, v in change.items()})
+        setter(live, state)
+        got = operations(live, state)
+        f = fresh(state)
+        want = operations(f, state)
+        f.close()
+        print(name, {op: r if failed(r) else "ok" for op, r in want.items()})
+        for op in want:
+            assert same(got[op], want[op]), (name, op)
+        # the operations ran: no error stands in for a result, except where no decay channels are set
+        for op in ("spectra", "polarization", "sample", "sample_binned"):
+            assert not failed(want[op]), (name, op, want[op])
+        assert np.any(want["spectra"] != 0.0) and want["sample"][2]["kept"] > 0, name
+        for op in ("feeddown", "decay_sampled", "decay_stats"):
+            if state["decays"] is None:     # the channels are gone with the species they indexed
+                assert want[op] == ("error", _lib.IS3D_ERR_STATE), (name, op, want[op])
+            else:
+                assert not failed(want[op]), (name, op, want[op])
+        if state["decays"] is not None:
+            assert not np.array_equal(want["feeddown"], want["spectra"]) and len(want["decay_sampled"][0]) > len(want["sample"][0])
+    live.close()

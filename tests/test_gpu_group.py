@@ -163,6 +163,86 @@ def test_group_surface_from_device():
     assert parity(got, one)[0] < 1e-12
 
 
+def list_getters(e, n_events):
+    """Every list getter of the C ABI on e: name -> (code, payload).  Buffers are sized from the engine's own counts."""
+    import ctypes as C
+    from is3d2_amd import _lib
+    lib, h = e.lib, e._e
+    out = {}
+    n = lib.is3d_sample_count(h)
+    out["count"] = (0, n)
+    off = np.zeros(n_events + 1, dtype=np.int64)
+    out["offsets"] = (lib.is3d_sample_offsets(h, off.ctypes.data_as(C.POINTER(C.c_long))), off)
+    m = max(n, 0)
+    parts = np.zeros(max(m, 1), dtype=_lib.PARTICLE_DTYPE)
+    out["particles"] = (lib.is3d_get_particles(h, 0, m, C.c_void_p(parts.ctypes.data)), parts[:m].tobytes())
+    org = np.zeros(max(m, 1), dtype=np.int64)
+    out["origins"] = (lib.is3d_get_particle_origins(h, 0, m, org.ctypes.data_as(C.POINTER(C.c_long))), org[:m])
+    nc, nv = C.c_long(0), C.c_long(0)
+    lib.is3d_sample_hist_size(h, C.byref(nc), C.byref(nv))
+    counts, vn = np.zeros(max(nc.value, 1), dtype=np.int64), np.zeros(max(nv.value, 1))
+    out["hist"] = (lib.is3d_get_sample_hist(h, counts.ctypes.data_as(C.POINTER(C.c_long)),
+                                            vn.ctypes.data_as(C.POINTER(C.c_double))), (counts, vn))
+    for name, struct, get, drop in (("stats", _lib.SampleStats, lib.is3d_get_sample_stats, ("batches",)),      # per shard
+                                    ("famod_stats", _lib.SampleFamodStats, lib.is3d_get_sample_famod_stats, ()),
+                                    ("decay_stats", _lib.DecayListStats, lib.is3d_get_decay_list_stats, ("ms_total",))):
+        st = struct()
+        out[name] = (get(h, C.byref(st)), {k: getattr(st, k) for k, _ in st._fields_ if k not in drop})
+    return out
+
+
+def test_group_list_getters_follow_the_one_device_engine():
+    """The list, histogram and stats getters read one SampledList (csrc/sampled_list.h): the engine's, or the group's
+    merge of its shards'.  A one-device engine and a [0, 0] engine driven through the same calls return the same code
+    from every getter after every step and, where that is IS3D_OK, the same payload (lists and integer histograms bit
+    for bit; the stats without the per-shard batch count and the device time)."""
+    from is3d2_amd import _lib
+    from is3d2_amd.engine import surface_averages
+    channels = [dict(parent=1, n_body=2, daughter=[0, 0], branching=1.0, mass_parent=0.494, width_parent=0.0,
+                     mass=[0.138, 0.138], width=[0.0, 0.0])]
+    s = synth.as_read(synth.surface(64, seed=35))
+    plasma = surface_averages(s)
+    spec = make_spec(hrg_eos=2, chosen="pikp", df_mode=1, dimension=2)
+    one, grp = build_engine(spec, s), build_engine(spec, s, devices=[0, 0])
+    for e in (one, grp):
+        e.set_decays(channels)
+    mine = {}
+
+    def caller_list(e):
+        parts, off = mine["list"]
+        return e.decay_particles(parts, off, 7, binned=True)
+
+    steps = [("fresh", lambda e: None),
+             ("sample", lambda e: e.sample(3, 2, 2, 0, plasma)),
+             ("bins", lambda e: e.set_sample_bins()),
+             ("sample_binned, list dropped", lambda e: e.sample_binned(3, 2, 2, 0, plasma)),
+             ("sample_binned, list kept", lambda e: e.sample_binned(4, 2, 2, 0, plasma, keep_list=True)),
+             ("set_sample_bins", lambda e: e.set_sample_bins(pT_bins=50)),
+             ("decay_sampled", lambda e: e.decay_sampled(5)),
+             ("decay_particles", caller_list),
+             ("sample again", lambda e: e.sample(6, 2, 2, 0, plasma))]
+    seen = set()
+    for name, call in steps:
+        res = [call(e) for e in (one, grp)]
+        if name == "sample":
+            mine["list"] = res[0][:2]
+            assert len(res[0][0]) > 0
+        a, b = list_getters(one, 2), list_getters(grp, 2)
+        print(name, {k: v[0] for k, v in a.items()})
+        for k in a:
+            assert a[k][0] == b[k][0], (name, k, a[k][0], b[k][0])
+            if a[k][0] == _lib.IS3D_OK:
+                ok = all(np.array_equal(x, y) for x, y in zip(a[k][1], b[k][1])) if k == "hist" else \
+                    np.array_equal(a[k][1], b[k][1]) if isinstance(a[k][1], np.ndarray) else a[k][1] == b[k][1]
+                assert ok, (name, k)
+            seen.add((k, a[k][0]))
+    one.close()
+    grp.close()
+    # the sequence met both answers of every getter that has two
+    for k in ("offsets", "particles", "origins", "hist", "stats", "decay_stats"):
+        assert (k, _lib.IS3D_OK) in seen and (k, _lib.IS3D_ERR_STATE) in seen, k
+
+
 def test_group_bad_device_list():
     with pytest.raises(Exception):
         Engine(devices=[0, 97])
