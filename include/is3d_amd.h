@@ -507,6 +507,29 @@ int is3d_decay_sampled(is3d_engine *e, long seed, int bin);
 int is3d_get_particle_origins(const is3d_engine *e, long first, long count, long *origin);
 int is3d_get_decay_list_stats(const is3d_engine *e, is3d_decay_list_stats *out);
 
+/* Sample and decay in one device-resident pass: every compacted batch of the sampler is decayed where
+ * it lies, so no primary is downloaded or uploaded.  The result is, byte for byte, that of the two calls above:
+ * is3d_sample (df_mode 1-4) or is3d_sample_famod(.., 0) (df_mode 5: plasma and p->fast are ignored, plasma may be
+ * null, and is3d_get_sample_famod_stats is valid afterwards) followed by is3d_decay_sampled(e, decay_seed, bin).
+ *   list = 1: is3d_sample_count, is3d_sample_offsets, is3d_get_particles and is3d_get_particle_origins return the
+ *     decayed list (origins index the primary list the two calls would have held), is3d_get_sample_hist the
+ *     histograms of the final hadrons when bin = 1, and both stats getters their values; only `batches` and
+ *     `ms_total` of the stats depend on how the work was cut.
+ *   list = 0, bin = 1: the histograms of the final hadrons only.  No particle record reaches the host: the count and
+ *     the offsets are 0 as after a binned-only sample, is3d_get_particle_origins accepts only count = 0, and the
+ *     sample stats and the decay-list stats are the true ones.
+ * The sampler plans its batches within half of "sample_bytes" and the decay stage's records take the rest; a batch
+ * whose products need more is decayed in sub-ranges (halved, never sampled again).  No bound changes the result.
+ * is3d_get_tuning(e, "list_h2d_bytes") / "list_d2h_bytes": the bytes of particle records, stream keys and origins
+ * that the last sampling or list-decay call (this one, or any of those above) copied to / from the device.
+ * A device-list engine runs the two-call sequence underneath (the shards sample, the merged list decays on
+ * devices[0]); decaying per shard is out of scope, since a primary's index inside its event depends on the other
+ * shards' counts.
+ * Errors: IS3D_ERR_ARG for list = 0 and bin = 0; IS3D_ERR_STATE without is3d_set_decays or, for bin = 1, without bins;
+ * otherwise the errors of the two calls it replaces.  A failed call leaves no list (is3d_sample_count is -1). */
+int is3d_sample_decayed(is3d_engine *e, const is3d_sample_params *p, const double *plasma, long decay_seed, int list,
+                        int bin);
+
 #ifdef __cplusplus
 }
 #endif

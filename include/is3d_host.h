@@ -63,9 +63,9 @@ int is3d_host_total_yield(const char *workdir, int device, int num_devices, doub
 int is3d_host_sample(const char *workdir, const int *devices, int num_devices, int write_files, int write_csv,
                      is3d_particle *out, long *mcid_out, long capacity, long *offsets, long offsets_capacity,
                      long *n_particles, long *n_events, double *n_total, long *seed, char *err, int errlen);
-/* is3d_host_sample with the bookkeeping of do_resonance_decays = 1 (the sampled list is decayed down its chains by
- * is3d_decay_sampled with the sampler's seed, and every output above is the decayed list's; test_sampler = 1: the final
- * hadrons are binned): origins (optional, capacity) = for each record the index, in the sampled list, of the primary it
+/* is3d_host_sample with the bookkeeping of do_resonance_decays = 1 (the sampled hadrons are decayed down their chains
+ * on the device by is3d_sample_decayed with the sampler's seed, and every output above is the decayed list's;
+ * test_sampler = 1: the final hadrons are binned and no list is made): origins (optional, capacity) = for each record the index, in the sampled list, of the primary it
  * descends from; decay_stats (optional) = is3d_get_decay_list_stats.  With the key 0 or absent nothing is written to
  * origins and the stats are zero. */
 int is3d_host_sample_decays(const char *workdir, const int *devices, int num_devices, int write_files, int write_csv,

@@ -31,7 +31,8 @@ EXPORTS = ["is3d_abi_version", "is3d_build_id", "is3d_create", "is3d_create_devi
            "is3d_get_sample_hist", "is3d_sample_famod", "is3d_get_sample_famod_stats",
            "is3d_calculate_dN_dX_famod",
            "is3d_set_decays", "is3d_decay_feeddown", "is3d_launch_feeddown", "is3d_get_decay_stats",
-           "is3d_decay_particles", "is3d_decay_sampled", "is3d_get_particle_origins", "is3d_get_decay_list_stats"]
+           "is3d_decay_particles", "is3d_decay_sampled", "is3d_get_particle_origins", "is3d_get_decay_list_stats",
+           "is3d_sample_decayed"]
 
 VORTICITY_FIELDS = ["wtx", "wty", "wtn", "wxy", "wxn", "wyn"]
 
@@ -212,6 +213,7 @@ def load():
     lib.is3d_decay_sampled.argtypes = [C.c_void_p, C.c_long, C.c_int]
     lib.is3d_get_particle_origins.argtypes = [C.c_void_p, C.c_long, C.c_long, P(C.c_long)]
     lib.is3d_get_decay_list_stats.argtypes = [C.c_void_p, P(DecayListStats)]
+    lib.is3d_sample_decayed.argtypes = [C.c_void_p, P(SampleParams), pd, C.c_long, C.c_int, C.c_int]
     _lib = lib
     return lib
 

@@ -4,17 +4,21 @@
 // not depend on the batches below.  A batch of primaries is uploaded and expanded in place, one pass per level of the
 // plan (after pass l no species of a level <= l can appear again):
 //   k_dl_init    one thread per primary: the working record (the 96-byte particle, origin, stream key) from the upload
+//   k_dl_init_batch  the same from a sampler's compacted batch on the device: the key from the batch's event bounds
+//                (k_dl_bounds, sample_decay_plan.h), nothing uploaded (is3d_sample_decayed)
 //   per pass:
 //   k_dl_count   one thread per working record: the channel draw (and a 3-body channel's s23 rejection loop, which
 //                decides whether the decay is capped) -> the number of records the particle becomes
 //   scan         exclusive sum: every record's position after the pass
 //   k_dl_emit    redraws the channel from the reopened stream, does the kinematics and writes the daughters at the
 //                scanned position; a record that does not decay in this pass is copied
-//   k_dl_final   the records as is3d_particle + origin; BIN: also binned (sampler_bins.h) into the call's histogram
+//   k_dl_final   the records as is3d_particle + origin; BIN: also binned (sampler_bins.h) into the call's histogram;
+//                the form that only bins writes no record
 // Expansion in place keeps the order for free: primaries in input order, each replaced by its leaves in depth-first
 // daughter-slot order.  The records ping-pong between two buffers.  Nothing appends with atomics; the only atomics
 // are the 64-bit integer tallies and the histogram adds, so the histogram is the same bits for every batching.
 #include "decay_list.h"
+#include "sample_decay_plan.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -39,8 +43,8 @@ struct Rec {
 };
 static_assert(sizeof(Rec) == 112, "working record");
 
-constexpr long kPrimBytes = sizeof(Particle) + sizeof(uint32_t);                        // the upload of one primary
-constexpr long kRecBytes = 2 * sizeof(Rec) + 12 + sizeof(Particle) + sizeof(long);      // both buffers, count + position, the output
+static_assert(kPrimBytes == sizeof(Particle) + sizeof(uint32_t), "the upload of one primary");
+static_assert(kRecBytes == 2 * sizeof(Rec) + 12 + sizeof(Particle) + sizeof(long), "both buffers, count + position, the output");
 
 struct Args {
   Table T;
@@ -97,14 +101,34 @@ __global__ __launch_bounds__(kBlock) void k_dl_emit(Args A) {
   if (t.capped) atomicAdd(&A.tally[3], (unsigned long long)t.capped);
 }
 
-template <bool BIN>
+// the working records straight from a sampler's compacted batch: the key's high word from the batch's event bounds
+__global__ __launch_bounds__(kBlock) void k_dl_init_batch(const Particle* in, long n, long origin0, const long* bounds, long nev,
+                                                          long first, unsigned long long carry, Rec* out) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  Rec r;
+  r.p = in[i];
+  r.origin = origin0 + i;
+  r.key = (unsigned long long)sdp::in_event_index(bounds, nev, first + i, carry) << 32;
+  out[i] = r;
+}
+
+__global__ __launch_bounds__(kBlock) void k_dl_bounds(const long* slots, const long* pos, long nev, long ncb, long* bounds) {
+  const long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k <= nev) bounds[k] = sdp::event_first(slots, pos, k, ncb);
+}
+
+// LIST: the records as is3d_particle + origin; BIN: binned into the call's histogram (alone: nothing is written)
+template <bool LIST, bool BIN>
 __global__ __launch_bounds__(kBlock) void k_dl_final(const Rec* in, long n, Particle* out, long* origin, sampler::Bins bins,
                                                      int npart, unsigned long long* hist) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const Particle p = in[i].p;
-  out[i] = p;
-  origin[i] = in[i].origin;
+  if (LIST) {
+    out[i] = p;
+    origin[i] = in[i].origin;
+  }
   if (BIN) {
     const sampler::Landing l = sampler::bin_particle(bins, sampler::particle_rapidity(3, 0.0, p.E, p.pz), p.eta, p.px, p.py, p.tau, p.x, p.y);
     sampler::hist_accumulate(bins, npart, p.species, l, [hist](long word, long long v) { atomicAdd(hist + word, (unsigned long long)v); });
@@ -154,6 +178,119 @@ std::string tables_build(Tables& t, const decay::Plan& P, const std::vector<doub
   return "";
 }
 
+hipError_t batch_bounds(const long* slots, const long* pos, long nev, long ncb, long* d_bounds) {
+  hipLaunchKernelGGL(k_dl_bounds, dim3(blocks(nev + 1)), dim3(kBlock), 0, 0, slots, pos, nev, ncb, d_bounds);
+  return hipGetLastError();
+}
+
+struct Stage::Buffers {
+  DevBuf<Rec> rec[2];
+  DevBuf<int> counts;
+  DevBuf<long> pos, origin;
+  DevBuf<Particle> out;
+  DevBuf<unsigned long long> tally;
+  DevBuf<char> tmp;
+  DevEvent ev0, ev1;
+};
+
+Stage::Stage() : b_(new Buffers()) {}
+Stage::~Stage() { delete b_; }
+const Particle* Stage::out() const { return b_->out.get(); }
+const long* Stage::origin() const { return b_->origin.get(); }
+
+int Stage::decay(const Tables& t, const Config& c, const Source& src, long fixed_bytes, bool keep_list, Stats& st,
+                 long& finals, long& need, std::string& msg) {
+  finals = 0;
+  need = 0;
+  Buffers& B = *b_;
+  const long nb = src.n;
+  if (nb <= 0) return S_OK;
+#define DCHK(x)                                                                       \
+  do {                                                                                \
+    const hipError_t h_ = (x);                                                        \
+    if (h_ != hipSuccess) { msg = std::string(#x) + ": " + hipGetErrorString(h_); return S_DEVICE; } \
+  } while (0)
+  if (!B.ev0) DCHK(B.ev0.create(hipEventDefault));
+  if (!B.ev1) DCHK(B.ev1.create(hipEventDefault));
+  DCHK(alloc(B.tally.reserve(4) && B.rec[0].reserve(nb)));
+  const long budget = std::max(c.sample_bytes, 1L);
+  Args A{};
+  A.T = t.view; A.seed = c.seed; A.tally = B.tally.get();
+  DCHK(hipEventRecord(B.ev0.get(), nullptr));
+  DCHK(hipMemsetAsync(B.tally.get(), 0, 4 * sizeof(unsigned long long), nullptr));
+  if (src.prim) hipLaunchKernelGGL(k_dl_init, dim3(blocks(nb)), dim3(kBlock), 0, 0, src.d, src.prim, nb, src.origin0, B.rec[0].get());
+  else hipLaunchKernelGGL(k_dl_init_batch, dim3(blocks(nb)), dim3(kBlock), 0, 0, src.d, nb, src.origin0, src.bounds, src.nev, src.first, (unsigned long long)src.carry, B.rec[0].get());
+  DCHK(hipGetLastError());
+  long cur = nb;
+  int from = 0;
+  bool too_big = false;
+  for (int pass = 0; pass < t.levels && cur > 0; pass++) {     // cur = 0: every daughter was dropped
+    DCHK(alloc(B.counts.reserve(cur + 1) && B.pos.reserve(cur + 1)));
+    DCHK(hipMemsetAsync(B.counts.get() + cur, 0, sizeof(int), nullptr));
+    A.pass = pass; A.n = cur; A.in = B.rec[from].get(); A.counts = B.counts.get(); A.pos = B.pos.get();
+    hipLaunchKernelGGL(k_dl_count, dim3(blocks(cur)), dim3(kBlock), 0, 0, A);
+    DCHK(hipGetLastError());
+    DCHK(scan(B.counts.get(), B.pos.get(), cur + 1, B.tmp));
+    long total = 0;
+    DCHK(hipMemcpy(&total, B.pos.get() + cur, sizeof(long), hipMemcpyDeviceToHost));
+    need = fixed_bytes + std::max(cur, total) * kRecBytes;
+    if (need > budget || total + 1 >= 0x7fffffffL) { too_big = true; break; }
+    DCHK(alloc(B.rec[1 - from].reserve(total)));
+    A.total = total; A.out = B.rec[1 - from].get();
+    hipLaunchKernelGGL(k_dl_emit, dim3(blocks(cur)), dim3(kBlock), 0, 0, A);
+    DCHK(hipGetLastError());
+    from = 1 - from;
+    cur = total;
+  }
+  if (t.levels == 0) { need = fixed_bytes + cur * kRecBytes; too_big = need > budget; }
+  if (!too_big && cur > 0) {
+    const Rec* r = B.rec[from].get();
+    const sampler::Bins bins = c.bins ? *c.bins : sampler::Bins{};
+    if (keep_list) {
+      DCHK(alloc(B.out.reserve(cur) && B.origin.reserve(cur)));
+      if (c.bins) hipLaunchKernelGGL((k_dl_final<true, true>), dim3(blocks(cur)), dim3(kBlock), 0, 0, r, cur, B.out.get(), B.origin.get(), bins, t.view.npart, c.hist);
+      else hipLaunchKernelGGL((k_dl_final<true, false>), dim3(blocks(cur)), dim3(kBlock), 0, 0, r, cur, B.out.get(), B.origin.get(), bins, t.view.npart, c.hist);
+    } else if (c.bins) {
+      hipLaunchKernelGGL((k_dl_final<false, true>), dim3(blocks(cur)), dim3(kBlock), 0, 0, r, cur, (Particle*)nullptr, (long*)nullptr, bins, t.view.npart, c.hist);
+    }
+    DCHK(hipGetLastError());
+  }
+  // the device time of an attempt that was too big counts too: the work was done
+  DCHK(hipEventRecord(B.ev1.get(), nullptr));
+  DCHK(hipEventSynchronize(B.ev1.get()));
+  float ms = 0.0f;
+  DCHK(hipEventElapsedTime(&ms, B.ev0.get(), B.ev1.get()));
+  st.ms_total += ms;
+  if (too_big) return S_BUDGET;
+  unsigned long long tl[4] = {0};
+  DCHK(hipMemcpy(tl, B.tally.get(), sizeof(tl), hipMemcpyDeviceToHost));
+#undef DCHK
+  st.decays += (long)tl[0]; st.undecayed += (long)tl[1]; st.dropped_daughters += (long)tl[2]; st.capped += (long)tl[3];
+  st.final_particles += cur;
+  st.batches++;
+  finals = cur;
+  return S_OK;
+}
+
+std::string too_big_message(long primary, long need, long budget) {
+  return "primary " + std::to_string(primary) + " alone needs " + std::to_string(need) +
+         " bytes for its decay products: more than the \"sample_bytes\" bound of " + std::to_string(budget) +
+         "; raise it with is3d_set_tuning";
+}
+
+int download(const Stage& S, long finals, std::vector<Particle>& out, std::vector<long>& origin, Stats& st, std::string& msg) {
+  if (finals <= 0) return S_OK;
+  const size_t at = out.size();
+  out.resize(at + (size_t)finals);
+  origin.resize(at + (size_t)finals);
+  hipError_t h = hipMemcpy(out.data() + at, S.out(), (size_t)finals * sizeof(Particle), hipMemcpyDeviceToHost);
+  if (h == hipSuccess) h = hipMemcpy(origin.data() + at, S.origin(), (size_t)finals * sizeof(long), hipMemcpyDeviceToHost);
+  if (h != hipSuccess) { msg = std::string("download of the decayed records: ") + hipGetErrorString(h); return S_DEVICE; }
+  st.list_d2h += finals * (long)(sizeof(Particle) + sizeof(long));
+  return S_OK;
+}
+
+// the input stage of a host list: each sub-range is uploaded (again after a halving) and handed to the shared stage
 int run(const Tables& t, const Config& c, long n, const Particle* in, const uint32_t* prim, std::vector<Particle>& out,
         std::vector<long>& origin, Stats& st, std::string& msg) {
   out.clear();
@@ -162,100 +299,31 @@ int run(const Tables& t, const Config& c, long n, const Particle* in, const uint
   st.primaries = n;
   st.passes = t.levels;
   if (n <= 0) return S_OK;
-#define DCHK(x)                                                                       \
-  do {                                                                                \
-    const hipError_t h_ = (x);                                                        \
-    if (h_ != hipSuccess) { msg = std::string(#x) + ": " + hipGetErrorString(h_); return S_DEVICE; } \
-  } while (0)
-  DevBuf<Particle> d_in, d_out;
+  DevBuf<Particle> d_in;
   DevBuf<uint32_t> d_prim;
-  DevBuf<Rec> rec[2];
-  DevBuf<int> counts;
-  DevBuf<long> pos, d_origin;
-  DevBuf<unsigned long long> tally;
-  DevBuf<char> tmp;
-  DevEvent ev0, ev1;
-  DCHK(ev0.create(hipEventDefault));
-  DCHK(ev1.create(hipEventDefault));
-  DCHK(alloc(tally.reserve(4)));
+  Stage S;
   const long budget = std::max(c.sample_bytes, 1L);
-  // a first guess of three final records per primary; a batch whose passes show more is halved
-  long nb = std::max(1L, std::min(budget / (kPrimBytes + 3 * kRecBytes), 0x3ffffff0L));
-  Args A{};
-  A.T = t.view; A.seed = c.seed; A.tally = tally.get();
-  long i0 = 0;
-  while (i0 < n) {
-    nb = std::min(nb, n - i0);
-    for (;;) {
-      DCHK(alloc(d_in.reserve(nb) && d_prim.reserve(nb) && rec[0].reserve(nb)));
-      DCHK(hipMemcpy(d_in.get(), in + i0, (size_t)nb * sizeof(Particle), hipMemcpyHostToDevice));
-      DCHK(hipMemcpy(d_prim.get(), prim + i0, (size_t)nb * sizeof(uint32_t), hipMemcpyHostToDevice));
-      DCHK(hipEventRecord(ev0.get(), nullptr));
-      DCHK(hipMemsetAsync(tally.get(), 0, 4 * sizeof(unsigned long long), nullptr));
-      hipLaunchKernelGGL(k_dl_init, dim3(blocks(nb)), dim3(kBlock), 0, 0, (const Particle*)d_in.get(), (const uint32_t*)d_prim.get(), nb, i0, rec[0].get());
-      DCHK(hipGetLastError());
-      long cur = nb, need = 0;
-      int src = 0;
-      bool too_big = false;
-      for (int pass = 0; pass < t.levels && cur > 0; pass++) {     // cur = 0: every daughter was dropped
-        DCHK(alloc(counts.reserve(cur + 1) && pos.reserve(cur + 1)));
-        DCHK(hipMemsetAsync(counts.get() + cur, 0, sizeof(int), nullptr));
-        A.pass = pass; A.n = cur; A.in = rec[src].get(); A.counts = counts.get(); A.pos = pos.get();
-        hipLaunchKernelGGL(k_dl_count, dim3(blocks(cur)), dim3(kBlock), 0, 0, A);
-        DCHK(hipGetLastError());
-        DCHK(scan(counts.get(), pos.get(), cur + 1, tmp));
-        long total = 0;
-        DCHK(hipMemcpy(&total, pos.get() + cur, sizeof(long), hipMemcpyDeviceToHost));
-        need = nb * kPrimBytes + std::max(cur, total) * kRecBytes;
-        if (need > budget || total + 1 >= 0x7fffffffL) { too_big = true; break; }
-        DCHK(alloc(rec[1 - src].reserve(total)));
-        A.total = total; A.out = rec[1 - src].get();
-        hipLaunchKernelGGL(k_dl_emit, dim3(blocks(cur)), dim3(kBlock), 0, 0, A);
-        DCHK(hipGetLastError());
-        src = 1 - src;
-        cur = total;
-      }
-      if (t.levels == 0) { need = nb * kPrimBytes + cur * kRecBytes; too_big = need > budget; }
-      if (too_big) {            // the attempt's device time counts: the work was done
-        DCHK(hipEventRecord(ev1.get(), nullptr));
-        DCHK(hipEventSynchronize(ev1.get()));
-        float lost = 0.0f;
-        DCHK(hipEventElapsedTime(&lost, ev0.get(), ev1.get()));
-        st.ms_total += lost;
-        if (nb > 1) { nb /= 2; continue; }
-        msg = "primary " + std::to_string(i0) + " alone needs " + std::to_string(need) +
-              " bytes for its decay products: more than the \"sample_bytes\" bound of " + std::to_string(budget) +
-              "; raise it with is3d_set_tuning";
-        return S_BUDGET;
-      }
-      if (cur > 0) {
-        DCHK(alloc(d_out.reserve(cur) && d_origin.reserve(cur)));
-        if (c.bins) hipLaunchKernelGGL(k_dl_final<true>, dim3(blocks(cur)), dim3(kBlock), 0, 0, (const Rec*)rec[src].get(), cur, d_out.get(), d_origin.get(), *c.bins, t.view.npart, c.hist);
-        else hipLaunchKernelGGL(k_dl_final<false>, dim3(blocks(cur)), dim3(kBlock), 0, 0, (const Rec*)rec[src].get(), cur, d_out.get(), d_origin.get(), sampler::Bins{}, t.view.npart, (unsigned long long*)nullptr);
-        DCHK(hipGetLastError());
-      }
-      DCHK(hipEventRecord(ev1.get(), nullptr));
-      DCHK(hipEventSynchronize(ev1.get()));
-      float ms = 0.0f;
-      DCHK(hipEventElapsedTime(&ms, ev0.get(), ev1.get()));
-      st.ms_total += ms;
-      unsigned long long tl[4] = {0};
-      DCHK(hipMemcpy(tl, tally.get(), sizeof(tl), hipMemcpyDeviceToHost));
-      st.decays += (long)tl[0]; st.undecayed += (long)tl[1]; st.dropped_daughters += (long)tl[2]; st.capped += (long)tl[3];
-      if (cur > 0) {
-        const size_t at = out.size();
-        out.resize(at + (size_t)cur);
-        origin.resize(at + (size_t)cur);
-        DCHK(hipMemcpy(out.data() + at, d_out.get(), (size_t)cur * sizeof(Particle), hipMemcpyDeviceToHost));
-        DCHK(hipMemcpy(origin.data() + at, d_origin.get(), (size_t)cur * sizeof(long), hipMemcpyDeviceToHost));
-      }
-      st.batches++;
-      break;
+  sdp::SubRanges R(n, sdp::first_guess(budget, kPrimBytes, kRecBytes));
+  while (!R.done()) {
+    const long i0 = R.at, nb = R.len;
+    hipError_t h = alloc(d_in.reserve(nb) && d_prim.reserve(nb));
+    if (h == hipSuccess) h = hipMemcpy(d_in.get(), in + i0, (size_t)nb * sizeof(Particle), hipMemcpyHostToDevice);
+    if (h == hipSuccess) h = hipMemcpy(d_prim.get(), prim + i0, (size_t)nb * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (h != hipSuccess) { msg = std::string("upload of the primaries: ") + hipGetErrorString(h); return S_DEVICE; }
+    st.list_h2d += nb * kPrimBytes;
+    Source src;
+    src.d = d_in.get(); src.n = nb; src.origin0 = i0; src.prim = d_prim.get();
+    long finals = 0, need = 0;
+    int s = S.decay(t, c, src, nb * kPrimBytes, true, st, finals, need, msg);
+    if (s == S_BUDGET) {
+      if (R.halve()) continue;
+      msg = too_big_message(i0, need, budget);
+      return S_BUDGET;
     }
-    i0 += nb;
+    if (s == S_OK) s = download(S, finals, out, origin, st, msg);
+    if (s != S_OK) return s;
+    R.accept();
   }
-#undef DCHK
-  st.final_particles = (long)out.size();
   return S_OK;
 }
 

@@ -256,6 +256,9 @@ struct is3d_engine {
     bool have_bins = false;
     is3d::DevBuf<unsigned long long> d_hist;
     is3d::SampledList list;
+    // bytes of particle records, stream keys and origins the last sampling or list-decay call copied to / from the
+    // device ("list_h2d_bytes" / "list_d2h_bytes"), summed where the copies are made
+    long list_h2d = 0, list_d2h = 0;
   } smp;
 
   // Monte Carlo decays of a particle list (decay_list.hip): the plan's tables on the device (D_DECAY_LIST)

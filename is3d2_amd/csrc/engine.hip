@@ -161,6 +161,8 @@ extern "C" long is3d_get_tuning(const is3d_engine* e, const char* key) {
   if (!std::strcmp(key, "slabs")) return e->ws.last_nslab;
   if (!std::strcmp(key, "sample_bytes")) return e->smp.sample_bytes;
   if (!std::strcmp(key, "sample_batches")) return e->smp.list.stats.batches;
+  if (!std::strcmp(key, "list_h2d_bytes")) return e->smp.list_h2d;
+  if (!std::strcmp(key, "list_d2h_bytes")) return e->smp.list_d2h;
   return -1;
 }
 

@@ -16,6 +16,7 @@
 #include "kernels.h"
 #include "group.h"
 #include "engine.h"
+#include "sample_decay_plan.h"
 
 using namespace is3d;
 using namespace is3d::kern;
@@ -118,14 +119,133 @@ static int hist_end(is3d_engine* e, const HistRun& H, SampledList& to) {
   return IS3D_OK;
 }
 
+// the plan's Monte Carlo tables on the device, rebuilt when the channels or the species changed
+static int decay_tables(is3d_engine* e, const std::string& w) {
+  if (!e->is_stale(D_DECAY_LIST)) return IS3D_OK;
+  const std::string m = is3d::decay_list::tables_build(e->dl.tables, e->fd.plan, e->in.mass);
+  if (!m.empty()) return e->fail(IS3D_ERR_DEVICE, w + m);
+  e->rebuilt(D_DECAY_LIST);
+  return IS3D_OK;
+}
+
+// is3d_sample_decayed: what the list decays need next to the sampler's arguments
+struct FusedDecay {
+  long seed;
+  int list, bin;
+};
+
+// The body of is3d_sample_decayed once sample_any has checked the arguments and filled the sampler's Config: every
+// compacted batch of the sampler is decayed where it lies.  The sampler plans its batches within half
+// of "sample_bytes"; the decay stage's records take what a batch leaves of the whole bound, in sub-ranges of the
+// batch when they need more.  Neither bound changes a byte of the result.
+static int sample_decayed_batches(is3d_engine* e, is3d::sampler::Config c, bool famod, const FusedDecay& f) {
+  namespace dl = is3d::decay_list;
+  namespace sm = is3d::sampler;
+  const std::string w = "is3d_sample_decayed: ";
+  SampledList& out = e->smp.list;
+  int rc = decay_tables(e, w);
+  if (rc) return rc;
+  const long bound = std::max(e->smp.sample_bytes, 1L);
+  c.sample_bytes = std::max(bound / 2, 1L);
+  c.bound_note = " (the sampler's half of the bound, the other is the decays')";
+  dl::Config dc;
+  dc.seed = (uint64_t)f.seed;
+  dc.sample_bytes = bound;
+  HistRun H;
+  if (f.bin) {
+    rc = hist_begin(e, H, w + "hipMalloc(histogram) failed");
+    if (rc) return rc;
+    dc.bins = &H.bins; dc.hist = H.d;
+  }
+  SampledList d;      // the decayed list, built beside the engine's
+  std::vector<long> prim_off((size_t)c.n_events + 1, 0);     // the primaries' offsets: the list the two calls would hold
+  dl::Stats ds;
+  ds.passes = e->dl.tables.levels;
+  dl::Stage stage;
+  DevBuf<long> d_bounds;
+  std::vector<long> bounds;
+  sdp::Carry carry;
+  long running = 0;     // primaries of the batches before this one: the origin of its first record
+  const sm::Consumer consume = [&](const sm::Batch& b, std::string& m) -> int {
+    bounds.assign((size_t)b.nev + 1, 0);
+    hipError_t h = d_bounds.reserve(b.nev + 1) ? hipSuccess : hipErrorOutOfMemory;
+    if (h == hipSuccess) h = dl::batch_bounds(b.slots, b.pos, b.nev, b.c1 - b.c0, d_bounds.get());
+    if (h == hipSuccess) h = hipMemcpy(bounds.data(), d_bounds.get(), bounds.size() * sizeof(long), hipMemcpyDeviceToHost);
+    if (h != hipSuccess) { m = std::string("the event bounds of a batch: ") + hipGetErrorString(h); return sm::S_DEVICE; }
+    const uint64_t cy = carry.before(b.e0, b.nev);
+    for (long k = 0; k < b.nev; k++) {
+      const long cnt = bounds[(size_t)k + 1] - bounds[(size_t)k];
+      if (!sdp::event_fits(k == 0 ? cy : 0ull, cnt)) { m = "event " + std::to_string(b.e0 + k) + " has 2^32 or more primaries"; return sm::S_BUDGET; }
+      prim_off[(size_t)(b.e0 + k) + 1] += cnt;
+    }
+    sdp::SubRanges R(b.kept, sdp::first_guess(bound - b.batch_bytes, 0, dl::kRecBytes));
+    while (!R.done()) {
+      dl::Source src;
+      src.d = b.d + R.at; src.n = R.len; src.origin0 = running + R.at;
+      src.bounds = d_bounds.get(); src.nev = b.nev; src.first = R.at; src.carry = cy;
+      long finals = 0, need = 0;
+      int s = stage.decay(e->dl.tables, dc, src, b.batch_bytes, f.list != 0, ds, finals, need, m);
+      if (s == dl::S_BUDGET) {
+        if (R.halve()) continue;
+        m = dl::too_big_message(running + R.at, need, bound);
+        return sm::S_BUDGET;
+      }
+      if (s == dl::S_OK && f.list) s = dl::download(stage, finals, d.particles, d.origins, ds, m);
+      if (s != dl::S_OK) return sm::S_DEVICE;
+      R.accept();
+    }
+    carry.after(b.e0, b.nev, b.kept);
+    running += b.kept;
+    return sm::S_OK;
+  };
+  sm::Stats st;
+  int derr = 0;
+  std::string msg;
+  const int s = sm::run(e->smp.tables, c, consume, st, derr, msg);
+  e->smp.list_d2h = ds.list_d2h;
+  if (s == sm::S_DF) return df_error(e, derr, "df coefficient error");
+  if (s == sm::S_DEVICE) return e->fail(IS3D_ERR_DEVICE, w + msg);
+  if (s == sm::S_BUDGET) return e->fail(IS3D_ERR_ARG, w + msg);
+  for (long k = 0; k < c.n_events; k++) prim_off[(size_t)k + 1] += prim_off[(size_t)k];
+  ds.primaries = running;
+  if (f.bin) {
+    rc = hist_end(e, H, d);
+    if (rc) return rc;
+  }
+  // the offsets of the decayed list: origins are non-decreasing, so event k ends where the origins reach its end
+  d.offsets.assign((size_t)c.n_events + 1, 0);
+  size_t j = 0;
+  for (long k = 0; k < c.n_events && f.list; k++) {
+    while (j < d.origins.size() && d.origins[j] < prim_off[(size_t)k + 1]) j++;
+    d.offsets[(size_t)k + 1] = (long)j;
+  }
+  d.decay_stats = is3d_decay_list_stats{ds.primaries, ds.decays, ds.undecayed, ds.dropped_daughters, ds.capped,
+                                      ds.final_particles, ds.passes, ds.batches, ds.ms_total};
+  out.stats = is3d_sample_stats{st.cells, st.breakdown, st.candidates, st.kept, st.proposals, st.acceptances, st.capped,
+                             st.clamped, st.batches};
+  out.commit_sample_decayed(d, famod, f.list != 0, f.bin != 0);
+  return IS3D_OK;
+}
+
 // cell_base: global index of this engine's cell 0 (a shard of a device-list engine holds only its window)
 // famod: the df_mode 5 method (is3d_sample_famod; plasma unused, fast ignored): the Newton prepass under the sampler's
 // chain rule first, then the same sampler with the k_cells / k_sample famod variants reading d_sol
+// fused: is3d_sample_decayed -- the same checks and setup, then the batches are decayed on the device
 static int sample_any(is3d_engine* e, const is3d_sample_params* sp, const double* plasma, long cell_base, int binned,
-                      bool famod) {
+                      bool famod, const FusedDecay* fused = nullptr) {
   if (!e || e->grp) return IS3D_ERR_ARG;
   SampledList& out = e->smp.list;
   out.begin_sample();
+  e->smp.list_h2d = e->smp.list_d2h = 0;
+  if (fused) {
+    const std::string w = "is3d_sample_decayed: ";
+    if (!fused->list && !fused->bin) return e->fail(IS3D_ERR_ARG, w + "list = 0 and bin = 0 leave nothing to return");
+    if (!e->have_decays()) return e->fail(IS3D_ERR_STATE, w + "no decay channels set (is3d_set_decays)");
+    if (fused->bin && !e->smp.have_bins) return e->fail(IS3D_ERR_STATE, w + "is3d_set_sample_bins not called");
+    if (fused->seed < 0) return e->fail(IS3D_ERR_ARG, w + "the seed must be non-negative");
+    const std::string plan_err = is3d::decay_mc::check_plan(e->fd.plan);
+    if (!plan_err.empty()) return e->fail(IS3D_ERR_ARG, w + plan_err);
+  }
   if (!sp || (!famod && !plasma)) return e->fail(IS3D_ERR_ARG, "is3d_sample: null argument");
   if (!famod && e->in.have_params && e->in.p.df_mode == PTMA)
     return e->fail(IS3D_ERR_UNSUPPORTED, "is3d_sample: df_mode 5 has its own method (sample_dN_pTdpTdphidy_famod): call is3d_sample_famod");
@@ -183,6 +303,7 @@ static int sample_any(is3d_engine* e, const is3d_sample_params* sp, const double
   } else if (famod) {
     out.famod_stats = is3d_sample_famod_stats{};
   }
+  if (fused) return sample_decayed_batches(e, c, famod, *fused);
   HistRun H;
   if (binned) {
     rc = hist_begin(e, H, "hipMalloc(sampler histogram) failed");
@@ -193,6 +314,7 @@ static int sample_any(is3d_engine* e, const is3d_sample_params* sp, const double
   int derr = 0;
   std::string msg;
   const int s = is3d::sampler::run(e->smp.tables, c, out.particles, out.offsets, st, derr, msg);
+  e->smp.list_d2h = st.list_d2h;
   if (s == is3d::sampler::S_DF) return df_error(e, derr, "df coefficient error");
   if (s == is3d::sampler::S_DEVICE) return e->fail(IS3D_ERR_DEVICE, "is3d_sample: " + msg);
   if (s == is3d::sampler::S_BUDGET) return e->fail(IS3D_ERR_ARG, "is3d_sample: " + msg);
@@ -226,6 +348,15 @@ extern "C" int is3d_get_sample_famod_stats(const is3d_engine* e, is3d_sample_fam
 extern "C" int is3d_sample(is3d_engine* e, const is3d_sample_params* sp, const double* plasma) {
   if (e && e->grp) return is3d::group_sample(e->grp, sp, plasma, 0);
   return is3d_internal_sample(e, sp, plasma, 0, 0);
+}
+
+extern "C" int is3d_sample_decayed(is3d_engine* e, const is3d_sample_params* sp, const double* plasma, long decay_seed,
+                                   int list, int bin) {
+  if (e && e->grp) return is3d::group_sample_decayed(e->grp, sp, plasma, decay_seed, list, bin);
+  if (!e) return IS3D_ERR_ARG;
+  const FusedDecay f{decay_seed, list ? 1 : 0, bin ? 1 : 0};
+  const bool famod = e->in.have_params && e->in.p.df_mode == PTMA;
+  return sample_any(e, sp, famod ? nullptr : plasma, 0, 0, famod, &f);
 }
 
 extern "C" int is3d_set_sample_bins(is3d_engine* e, const is3d_sample_bins* b) {
@@ -328,11 +459,9 @@ static int decay_list_any(is3d_engine* e, long seed, int n_events, const long* o
     }
   }
   HIPCHK(e, hipSetDevice(e->device));
-  if (e->is_stale(D_DECAY_LIST)) {
-    const std::string m = is3d::decay_list::tables_build(e->dl.tables, e->fd.plan, e->in.mass);
-    if (!m.empty()) return e->fail(IS3D_ERR_DEVICE, w + m);
-    e->rebuilt(D_DECAY_LIST);
-  }
+  e->smp.list_h2d = e->smp.list_d2h = 0;
+  const int trc = decay_tables(e, w);
+  if (trc) return trc;
   is3d::decay_list::Config c;
   c.seed = (uint64_t)seed;
   c.sample_bytes = e->smp.sample_bytes;
@@ -348,6 +477,8 @@ static int decay_list_any(is3d_engine* e, long seed, int n_events, const long* o
   std::string msg;
   const int s = is3d::decay_list::run(e->dl.tables, c, n, reinterpret_cast<const is3d::sampler::Particle*>(in) + i0, prim.data(),
                                       d.particles, origin, st, msg);
+  e->smp.list_h2d = st.list_h2d;
+  e->smp.list_d2h = st.list_d2h;
   if (s == is3d::decay_list::S_DEVICE) return e->fail(IS3D_ERR_DEVICE, w + msg);
   if (s == is3d::decay_list::S_BUDGET) return e->fail(IS3D_ERR_ARG, w + msg);
   if (bin) {

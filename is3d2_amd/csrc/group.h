@@ -77,6 +77,9 @@ int group_get_decay_stats(const Group* g, is3d_decay_stats* out);
 // decayed list, origins and stats in place of it
 int group_decay_particles(Group* g, long seed, int n_events, const long* offsets, const is3d_particle* in, int bin);
 int group_decay_sampled(Group* g, long seed, int bin);
+// is3d_sample_decayed: group_sample / group_sample_famod, then the merged list decayed on devices[0] (decaying per shard
+// is out of scope: the stream key of a primary depends on the other shards' counts)
+int group_sample_decayed(Group* g, const is3d_sample_params* p, const double* plasma, long decay_seed, int list, int bin);
 }  // namespace is3d
 
 // engine internals the group uses on its shard engines (not part of the public ABI)

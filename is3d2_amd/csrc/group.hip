@@ -68,6 +68,7 @@ struct Group {
   // particle sampler: the shards' lists of the last group_sample merged per event, their stats and integer histograms
   // summed; after a list decay, shard 0's decayed list
   SampledList list;
+  long list_h2d = 0, list_d2h = 0;    // "list_h2d_bytes" / "list_d2h_bytes" of the last sampling or list-decay call, all shards
   std::string err;
   int fail(int code, const std::string& m) { err = m; return code; }
   int shard_fail(int k, int rc) {
@@ -179,6 +180,8 @@ int group_set_tuning(Group* g, const char* key, long value) {
   return each(g, [&](is3d_engine* e) { return is3d_set_tuning(e, key, value); });
 }
 long group_get_tuning(const Group* g, const char* key) {
+  if (!std::strcmp(key, "list_h2d_bytes")) return g->list_h2d;
+  if (!std::strcmp(key, "list_d2h_bytes")) return g->list_d2h;
   if (std::strcmp(key, "phitab_chunks")) return is3d_get_tuning(g->sh[0], key);
   long m = 0;
   for (auto* e : g->sh) m = std::max(m, is3d_get_tuning(e, key));
@@ -501,6 +504,8 @@ int group_get_decay_stats(const Group* g, is3d_decay_stats* out) { return is3d_g
 // bin = 1, the histogram (the group's sample stats stay)
 static int decay_on_shard0(Group* g, long seed, int n_events, const long* offsets, const is3d_particle* in, int bin) {
   const int rc = is3d_decay_particles(g->sh[0], seed, n_events, offsets, in, bin);
+  g->list_h2d = is3d_get_tuning(g->sh[0], "list_h2d_bytes");
+  g->list_d2h = is3d_get_tuning(g->sh[0], "list_d2h_bytes");
   if (rc) return g->shard_fail(0, rc);
   SampledList d = is3d_internal_sampled_list(g->sh[0]);
   g->list.replace_decayed(d, bin != 0);
@@ -686,6 +691,7 @@ const SampledList& group_list(const Group* g) { return g->list; }
 static int sample_shards(Group* g, const is3d_sample_params* p, const double* plasma, int binned, bool famod) {
   SampledList& out = g->list;
   out.begin_sample();
+  g->list_h2d = g->list_d2h = 0;
   if (!p || (!famod && !plasma)) return g->fail(IS3D_ERR_ARG, "is3d_sample: null argument");
   if (famod && (binned < 0 || binned > 2)) return g->fail(IS3D_ERR_ARG, "is3d_sample_famod: binned must be 0, 1 or 2");
   if (stale_split(g)) return g->fail(IS3D_ERR_STATE, kStaleSplit);
@@ -695,6 +701,7 @@ static int sample_shards(Group* g, const is3d_sample_params* p, const double* pl
     const long base = g->full ? 0 : (k < (int)g->lo.size() ? g->lo[k] : 0);
     return famod ? is3d_internal_sample_famod(g->sh[k], p, base, binned) : is3d_internal_sample(g->sh[k], p, plasma, base, binned);
   });
+  for (int k = 0; k < K; k++) g->list_d2h += is3d_get_tuning(g->sh[k], "list_d2h_bytes");
   if (rc) return rc;
   std::vector<const SampledList*> sh(K);
   for (int k = 0; k < K; k++) sh[k] = &is3d_internal_sampled_list(g->sh[k]);
@@ -742,6 +749,30 @@ int group_sample(Group* g, const is3d_sample_params* p, const double* plasma, in
   return sample_shards(g, p, plasma, binned, false);
 }
 int group_sample_famod(Group* g, const is3d_sample_params* p, int binned) { return sample_shards(g, p, nullptr, binned, true); }
+
+// is3d_sample_decayed on a device list: the present sequence underneath -- the shards sample, the merged list decays on
+// devices[0] -- so the bytes are the one-device call's.  (The decays cannot run per shard: a primary's index inside its
+// event, the stream key, depends on the other shards' counts.)  list = 0: the merged list is dropped after binning.
+int group_sample_decayed(Group* g, const is3d_sample_params* p, const double* plasma, long decay_seed, int list, int bin) {
+  g->list.begin_sample();
+  if (!list && !bin) return g->fail(IS3D_ERR_ARG, "is3d_sample_decayed: list = 0 and bin = 0 leave nothing to return");
+  const bool famod = g->have_params && g->p.df_mode == 5;
+  int rc = sample_shards(g, p, famod ? nullptr : plasma, 0, famod);
+  if (rc) return rc;
+  const long d2h = g->list_d2h;
+  const SampledList& l = g->list;
+  rc = decay_on_shard0(g, decay_seed, (int)l.offsets.size() - 1, l.offsets.data(),
+                       reinterpret_cast<const is3d_particle*>(l.particles.data()), bin ? 1 : 0);
+  g->list_d2h += d2h;
+  if (rc) { g->list.begin_sample(); return rc; }
+  if (!list) {
+    SampledList d;
+    d.offsets.assign(g->list.offsets.size(), 0);
+    d.decay_stats = g->list.decay_stats;
+    g->list.replace_decayed(d, false);
+  }
+  return IS3D_OK;
+}
 
 int group_get_jonah_table(const Group* g, double* l2, double* z, double* bp, double* bpmax) {
   return is3d_get_jonah_table(g->sh[0], l2, z, bp, bpmax);

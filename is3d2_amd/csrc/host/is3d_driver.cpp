@@ -199,16 +199,15 @@ void EmissionFunctionArray::run_sharded(const RunOptions& opt, int operation) {
       sp.y_cut = p_.get("y_cut", 0.5);
       // df_mode 5 has a method of its own (EmissionFunction.cpp:1255-1275): sample_dN_pTdpTdphidy_famod
       const bool famod = prm.df_mode == 5;
-      // do_resonance_decays = 1: the sampled list is decayed down its chains (is3d_decay_sampled, the sampler's seed)
-      // before anything reads it, so the lists, the offsets and the binned files carry the final hadrons
+      // do_resonance_decays = 1: the sampled hadrons are decayed down their chains on the device, batch by batch
+      // (is3d_sample_decayed, the sampler's seed), so the lists, the offsets and the binned files carry the final hadrons
       const bool decays = (int)p_.get("do_resonance_decays", 0.0) == 1;
       if (decays) set_or_throw(e, is3d_set_decays(e, (int)decays_.size(), decays_.data()));
       if (operation == 4) {      // test_sampler = 1: binned only, no list (EmissionFunction.cpp:1279-1291)
         sbins_ = read_sample_bins(p_);
         set_or_throw(e, is3d_set_sample_bins(e, &sbins_));
-        if (decays) {            // the decays need the list: it is kept, decayed and binned, and not written
-          set_or_throw(e, famod ? is3d_sample_famod(e, &sp, 2) : is3d_sample_binned(e, &sp, plasma, 1));
-          set_or_throw(e, is3d_decay_sampled(e, sample_seed_, 1));
+        if (decays) {            // the final hadrons are binned where they are made: no list reaches the host
+          set_or_throw(e, is3d_sample_decayed(e, &sp, plasma, sample_seed_, 0, 1));
         } else {
           set_or_throw(e, famod ? is3d_sample_famod(e, &sp, 1) : is3d_sample_binned(e, &sp, plasma, 0));
         }
@@ -218,8 +217,8 @@ void EmissionFunctionArray::run_sharded(const RunOptions& opt, int operation) {
         hist_vn_.assign((size_t)nv, 0.0);
         set_or_throw(e, is3d_get_sample_hist(e, hist_counts_.data(), hist_vn_.data()));
       } else {
-        set_or_throw(e, famod ? is3d_sample_famod(e, &sp, 0) : is3d_sample(e, &sp, plasma));
-        if (decays) set_or_throw(e, is3d_decay_sampled(e, sample_seed_, 0));
+        if (decays) set_or_throw(e, is3d_sample_decayed(e, &sp, plasma, sample_seed_, 1, 0));
+        else set_or_throw(e, famod ? is3d_sample_famod(e, &sp, 0) : is3d_sample(e, &sp, plasma));
       }
       famod_sampled_ = famod;
       if (famod) set_or_throw(e, is3d_get_sample_famod_stats(e, &famod_stats_));
@@ -234,11 +233,6 @@ void EmissionFunctionArray::run_sharded(const RunOptions& opt, int operation) {
         origins_.assign(records_.size(), 0);
         set_or_throw(e, is3d_get_particle_origins(e, 0, (long)origins_.size(), origins_.data()));
         set_or_throw(e, is3d_get_decay_list_stats(e, &decay_list_stats_));
-        if (operation == 4) {      // test_sampler = 1 never lists: the decayed list was binned and is dropped
-          records_.clear();
-          origins_.clear();
-          sample_offsets_.assign((size_t)sample_events_ + 1, 0);
-        }
       }
     } else if (operation == 0) {
       set_or_throw(e, is3d_set_momentum_weights(e, pTw.data(), phiw.data()));

@@ -99,8 +99,8 @@ class EmissionFunctionArray {
   // engine's bookkeeping (zero when the key is 0 or absent)
   const std::vector<is3d_decay_channel>& decay_channels() const { return decays_; }
   const is3d_decay_stats& decay_stats() const { return decay_stats_; }
-  // do_resonance_decays = 1 with operation = 2: the sampled list is decayed by is3d_decay_sampled (the sampler's seed)
-  // right after sampling; sampled(), sample_offsets() and sampled_records() then hold the final hadrons,
+  // do_resonance_decays = 1 with operation = 2: the sampled hadrons are decayed on the device as they are sampled
+  // (is3d_sample_decayed, the sampler's seed); sampled(), sample_offsets() and sampled_records() then hold the final hadrons,
   // sample_origins() the index in the sampled list of the primary each descends from and decay_list_stats() the
   // engine's counters (empty / zero when the key is 0 or absent).  With test_sampler = 1 the final hadrons are binned
   const std::vector<long>& sample_origins() const { return origins_; }

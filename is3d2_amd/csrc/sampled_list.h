@@ -56,6 +56,20 @@ struct SampledList {
     sampled = true;
     decayed = true;
   }
+  // is3d_sample_decayed has succeeded (after begin_sample; stats and famod_stats are filled in): d holds the decay stats
+  // and, with_list, the decayed list with its offsets and origins -- the state after a sample call and is3d_decay_sampled.
+  // Without a list (binned only) the count and the offsets are zero and there is no origin to read, as after a
+  // binned-only sample, while both stats are the true ones.  with_hist: d's histogram of the final hadrons
+  void commit_sample_decayed(SampledList& d, bool from_famod, bool with_list, bool with_hist) {
+    const size_t nev1 = d.offsets.size();
+    if (!with_list) {
+      d.particles.clear();
+      d.origins.clear();
+      d.offsets.assign(nev1, 0);
+    }
+    commit_sample(from_famod, false);
+    replace_decayed(d, with_hist);
+  }
   // is3d_decay_sampled's input: a binned-only call counted particles and kept none
   bool has_list() const { return sampled && !offsets.empty() && !(particles.empty() && stats.kept > 0); }
 

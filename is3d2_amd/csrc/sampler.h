@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -40,6 +41,7 @@ struct Config {
   long n_events = 1;
   const double* dens = nullptr;    // fast = 1: [3][npart] Plasma-average densities (device)
   long sample_bytes = 0;           // bound on the working buffers of one batch
+  const char* bound_note = "";     // appended to the message of a batch that cannot fit (a caller that passes a share)
   // test_sampler = 1: kept particles are also binned into hist (device, hist_counts + hist_vn 8-byte words that the
   // caller zeroed; the vn words in their integer form).  keep_list = false: binned only -- no candidate slots, no
   // compaction and no list; a batch then costs only its (event, cell) counts.
@@ -51,9 +53,24 @@ struct Config {
 struct Stats {
   long cells = 0, breakdown = 0, candidates = 0, kept = 0, proposals = 0, acceptances = 0, capped = 0, clamped = 0,
        batches = 0;
+  long list_d2h = 0;     // bytes of particle records copied to the host
 };
 
 enum Status : int { S_OK = 0, S_DEVICE = 1, S_DF = 2, S_BUDGET = 3 };
+
+// One compacted batch on the device, as its consumer sees it on the null stream right after k_compact: the kept
+// particles of events [e0, e0 + nev) over cells [c0, c1) (held-surface indices; nev = 1 when the window is a part of
+// the call's), events contiguous.  slots / pos: the two exclusive sums of sample_decay_plan.h (device), and
+// batch_bytes: what the sampler's pair and candidate buffers of this batch hold.  All of it is valid until the
+// consumer returns.
+struct Batch {
+  const Particle* d = nullptr;
+  long kept = 0, e0 = 0, nev = 0, c0 = 0, c1 = 0;
+  const long *slots = nullptr, *pos = nullptr;
+  long batch_bytes = 0;
+};
+// returns a Status (S_OK to go on); msg says what went wrong otherwise
+using Consumer = std::function<int(const Batch&, std::string& msg)>;
 
 // Samples n_events events of the window.  parts: kept particles, events contiguous, ordered by (cell, candidate)
 // within an event (the reference's loop order); offsets: n_events + 1 (a binned-only call leaves parts empty and the
@@ -61,6 +78,10 @@ enum Status : int { S_OK = 0, S_DEVICE = 1, S_DF = 2, S_BUDGET = 3 };
 // DfErr; msg says what went wrong otherwise.
 int run(const Tables& t, const Config& c, std::vector<Particle>& parts, std::vector<long>& offsets, Stats& st,
         int& df_err, std::string& msg);
+
+// The same with every compacted batch that kept something handed to `consume` instead of the host list (the list
+// form above is the consumer that downloads it).  st.kept is the sum of the batches'; binned-only calls have no batches.
+int run(const Tables& t, const Config& c, const Consumer& consume, Stats& st, int& df_err, std::string& msg);
 
 // test hook: the first n uniforms of stream (seed, purpose, cell, event, candidate), generated on the device
 hipError_t uniforms(uint64_t seed, int purpose, long cell, long event, long candidate, int n, double* host_out);

@@ -296,6 +296,23 @@ int run(const Tables& t, const Config& c, std::vector<Particle>& parts, std::vec
         int& df_err, std::string& msg) {
   parts.clear();
   offsets.assign((size_t)c.n_events + 1, 0);
+  long copied = 0;
+  const int s = run(t, c, [&](const Batch& b, std::string& m) -> int {
+    const size_t at = parts.size();
+    parts.resize(at + (size_t)b.kept);
+    const hipError_t h = hipMemcpy(parts.data() + at, b.d, (size_t)b.kept * sizeof(Particle), hipMemcpyDeviceToHost);
+    if (h != hipSuccess) { m = std::string("download of a batch: ") + hipGetErrorString(h); return S_DEVICE; }
+    copied += b.kept * (long)sizeof(Particle);
+    return S_OK;
+  }, st, df_err, msg);
+  st.list_d2h = copied;
+  if (s != S_OK) return s;
+  for (const Particle& p : parts) offsets[(size_t)p.event + 1]++;
+  for (long e = 0; e < c.n_events; e++) offsets[e + 1] += offsets[e];
+  return S_OK;
+}
+
+int run(const Tables& t, const Config& c, const Consumer& consume, Stats& st, int& df_err, std::string& msg) {
   st = Stats{};
   df_err = 0;
   const long nw = c.hi - c.lo;
@@ -385,7 +402,8 @@ int run(const Tables& t, const Config& c, std::vector<Particle>& parts, std::vec
         if (ncb > 1) { b = a + ncb / 2; continue; }
         msg = "cell " + std::to_string(c.cell_base + c.lo + a) + " of event " + std::to_string(e0) + " alone draws " +
               std::to_string(total) + " candidates (" + std::to_string(total * kCandBytes) +
-              " bytes): more than the \"sample_bytes\" bound of " + std::to_string(budget) + "; raise it with is3d_set_tuning";
+              " bytes): more than the \"sample_bytes\" bound of " + std::to_string(budget) + c.bound_note +
+              "; raise it with is3d_set_tuning";
         return S_BUDGET;
       }
       st.batches++;
@@ -405,9 +423,13 @@ int run(const Tables& t, const Config& c, std::vector<Particle>& parts, std::vec
         if (kept > 0) {
           hipLaunchKernelGGL(k_compact, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, 0, B.cand.get(), B.flags.get(), B.pos.get(), total, B.out.get());
           SCHK(hipGetLastError());
-          const size_t at = parts.size();
-          parts.resize(at + (size_t)kept);
-          SCHK(hipMemcpy(parts.data() + at, B.out.get(), (size_t)kept * sizeof(Particle), hipMemcpyDeviceToHost));
+          Batch bt;
+          bt.d = B.out.get(); bt.kept = kept; bt.e0 = e0; bt.nev = nev; bt.c0 = A.c0; bt.c1 = A.c1;
+          bt.slots = B.slots.get(); bt.pos = B.pos.get();
+          bt.batch_bytes = (np - 1) * kPairBytes + total * kCandBytes;
+          const int cs = consume(bt, msg);
+          if (cs != S_OK) return cs;
+          st.kept += kept;
         }
       }
       break;
@@ -419,10 +441,7 @@ int run(const Tables& t, const Config& c, std::vector<Particle>& parts, std::vec
   if (hipMemcpy(tally, B.tally.get(), sizeof(tally), hipMemcpyDeviceToHost) != hipSuccess) { msg = "reading the sampler tallies failed"; return S_DEVICE; }
   st.breakdown = (long)tally[0]; st.proposals = (long)tally[1]; st.acceptances = (long)tally[2];
   st.capped = (long)(tally[3] + tally[5]); st.clamped = (long)tally[4];
-  st.kept = (long)parts.size();
   if (binned_only) { st.kept = (long)tally[6]; st.candidates = (long)tally[7]; }
-  for (const Particle& p : parts) offsets[(size_t)p.event + 1]++;
-  for (long e = 0; e < c.n_events; e++) offsets[e + 1] += offsets[e];
   return S_OK;
 }
 

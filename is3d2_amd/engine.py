@@ -477,6 +477,27 @@ class Engine:
         self._chk(self.lib.is3d_sample_offsets(self._e, offsets.ctypes.data_as(C.POINTER(C.c_long))))
         return parts, offsets, origins, self.decay_list_stats()
 
+    def sample_decayed(self, seed, n_events, decay_seed, y_cut=0.5, fast=0, plasma=None, keep_list=True, binned=False):
+        """sample() (df_mode 5: sample_famod(); plasma and fast are then unused) and decay_sampled(decay_seed, binned)
+        in one device-resident pass (is3d_sample_decayed): the sampler's batches are decayed where
+        they lie and no primary crosses to the host.  Returns (particles, offsets, origins, stats) with the bytes of
+        the two calls.  keep_list = False (with binned = True): only sample_hist() is filled; particles and origins
+        are empty and the offsets zero.  sample_stats() holds the sampler's stats."""
+        pl = None if plasma is None else _arr(plasma)
+        sp = _lib.SampleParams(int(seed), int(n_events), int(fast), float(y_cut))
+        self._chk(self.lib.is3d_sample_decayed(self._e, C.byref(sp), None if pl is None else _dp(pl), int(decay_seed),
+                                               int(bool(keep_list)), int(bool(binned))))
+        self._list_events = int(n_events)
+        parts, origins = self._decayed_list()
+        offsets = np.zeros(self._list_events + 1, dtype=np.int64)
+        self._chk(self.lib.is3d_sample_offsets(self._e, offsets.ctypes.data_as(C.POINTER(C.c_long))))
+        return parts, offsets, origins, self.decay_list_stats()
+
+    def list_transfer_bytes(self):
+        """(host-to-device, device-to-host) bytes of particle records, stream keys and origins that the last sampling or
+        list-decay call copied: the "list_h2d_bytes" / "list_d2h_bytes" tuning keys."""
+        return self.get_tuning("list_h2d_bytes"), self.get_tuning("list_d2h_bytes")
+
     def decay_particles(self, particles, offsets, seed, binned=False):
         """decay_sampled() for a caller's list: particles (PARTICLE_DTYPE) with events contiguous, offsets[n_events
         + 1] into it (offsets[0] may be > 0: a sub-range of events), the records' event field non-decreasing.
