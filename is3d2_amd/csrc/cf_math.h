@@ -1139,7 +1139,7 @@ IS3D_HD bool sep_slow_cell(const double* R, double pT_max, double b_max) {
 
 IS3D_HD void sep_setup(int flavor, const double* R, const double* Y, double mT, double mT2, double m2, double mTb,
                        double pT, double sign, double baryon, const double* etab, SepLane& L, int allow_tail = 0,
-                       int allow_near = 0, bool inv_a = false) {
+                       int allow_near = 0, bool inv_a = false, int yw = Y_W) {
   L.sign = sign;
   L.x = fma(mT, Y[Y_AT], -baryon * R[R_CHEM]);
   const double zb = pT * R[R_ZB];                 // >= max_j |pT B_j / T|
@@ -1186,7 +1186,7 @@ IS3D_HD void sep_setup(int flavor, const double* R, const double* Y, double mT, 
   }
   const double esc = ldexp(1.0, -k);
   L.ssc = sign * esc;
-  L.escw = esc * Y[Y_W];
+  L.escw = esc * Y[yw];           // (yw: the row's w_eta slot; k_ytab's rows keep it at kYW_TS)
   if (!L.fast) { L.Zc = R[R_UX] * R[R_INVT]; L.Zs = R[R_UY] * R[R_INVT]; } else { L.Zc = L.Zs = 0.0; }
   L.D0 = esc * (mT * Y[Y_D]); L.Dc = esc * Y[Y_WDX]; L.Ds = esc * Y[Y_WDY];
   // fast lanes carry the delta-f coefficients pre-multiplied by a (see sep_fast_tail)

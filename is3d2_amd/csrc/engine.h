@@ -190,7 +190,8 @@ struct is3d_engine {
     is3d::DevBuf<double> d_chain;     // PTMA warm-start chain segments (k_chain_pass)
     is3d::DevBuf<double> d_rec, d_aux, d_sol, d_renorm, d_slab, d_out;
     is3d::DevBuf<int> d_fb;           // modified modes: [0] fallback cell count, [1..] k_fbwrite's cell list
-    is3d::DevBuf<double> d_phtab;     // F_TS launches: k_phitab's per-(cell, pT, phi) rows of one chunk of cells
+    // F_TS launches: k_phitab's per-(cell, pT, phi) rows of one chunk of cells and, behind them, k_ytab's y-term rows
+    is3d::DevBuf<double> d_phtab;
     is3d::DevBuf<double> d_phtab2;    // ... and of the next chunk, integrated on the side stream meanwhile
     // the streams and events of the chunked F_TS launches are made by the first launch that needs them
     is3d::DevStream side;             // F_TS chunks alternate between the launch stream and this one

@@ -368,9 +368,10 @@ static SpectraPlan spectra_plan(const is3d_engine* e, bool allow_ts = true) {
     const size_t etab = kExpTabN;
     const size_t bprows = modmain ? 0 : 1;
     if (ts_ok()) {
-      // records x 3, trig + {pc, ps}, grid, y-term rows x 2, exp table, T1 rows [tile][qrows][KJ + 2] (+ 1: alignment)
+      // records x 3, trig + {pc, ps}, grid, y-term rows x 2 (k_ytab's, kYRowTS), exp table, T1 rows
+      // [tile][qrows][KJ + 2] (+ 1: alignment)
       return sizeof(double) * (3 * tile * NREC + 4 * nphp + (size_t)(nk + 2 * nl) +
-                               2 * tile * std::min(qrows, P.nq) * kYRow + kExpTabN + tile * qrows * (P.KJ + 2) + 1 +
+                               2 * tile * std::min(qrows, P.nq) * kYRowTS + kExpTabN + tile * qrows * (P.KJ + 2) + 1 +
                                128);     // + 128: the landing rows of the k_phitab L2 prefetch
     }
     // pipelined launches (F_TB, the modified path's 16-cell tiles): 3 record tiles, 2 table buffers
@@ -954,7 +955,7 @@ struct IntegralPlan {
   // F_TS table chunks: spc splits per chunk, nchunk chunks; fold: each chunk's slabs are folded into one accumulator
   // slab as soon as the chunk is integrated (3+1D, several chunks), so the slabs take 1 + 2 spc output sizes of HBM
   // instead of nsplit (config 4: 947 -> 67 slabs, 47 -> 3.4 GB)
-  long spc = 0, nchunk = 0, rw = 0;
+  long spc = 0, nchunk = 0, rw = 0, tabw = 0;
   bool fold = false;
   long slabs() const { return fold ? 1 + 2 * spc : nsplit + nsplit_fb; }
 };
@@ -965,7 +966,9 @@ struct IntegralPlan {
 static void ts_chunking(is3d_engine* e, IntegralPlan& I) {
   const int npT = (int)e->in.pT.size();
   I.rw = phitab_row(e->in.p.df_mode, I.P.KJ, I.P.by != 0);
-  const long per_split = I.cps * (long)npT * I.rw;
+  // doubles per cell of a chunk's table buffer: k_phitab's rows of every pT and, behind them, k_ytab's y-term rows
+  I.tabw = (long)npT * I.rw + (long)I.P.nq * kYRowTS;
+  const long per_split = I.cps * I.tabw;
   const long whole = per_split * I.nsplit * 8;          // bytes of the whole surface's rows
   long one = e->ws.phitab_one, chunk = e->ws.phitab_chunk;
   {
@@ -1081,9 +1084,9 @@ static int enqueue_spectra(is3d_engine* e, const IntegralPlan& I, const double* 
     const long rw = I.rw, spc = I.spc, nchunk = I.nchunk;
     const long phn = spc * cps;
     e->ws.last_nchunk = nchunk;
-    if (!e->ws.d_phtab.reserve(phn * npT * rw)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(phi tables) failed");
+    if (!e->ws.d_phtab.reserve(phn * I.tabw)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(phi tables) failed");
     if (nchunk > 1) {
-      if (!e->ws.d_phtab2.reserve(phn * npT * rw)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(phi tables) failed");
+      if (!e->ws.d_phtab2.reserve(phn * I.tabw)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(phi tables) failed");
       if (!e->ws.side) HIPCHK(e, e->ws.side.create(hipStreamNonBlocking));
       if (!e->ws.fork) HIPCHK(e, e->ws.fork.create(hipEventDisableTiming));
       if (!e->ws.join) HIPCHK(e, e->ws.join.create(hipEventDisableTiming));
@@ -1107,13 +1110,19 @@ static int enqueue_spectra(is3d_engine* e, const IntegralPlan& I, const double* 
       ta.rec = rec_w; ta.c0 = c0; ta.nc = ncc; ta.pT = e->tbl.d_pT; ta.cphi = e->tbl.d_cphi; ta.sphi = e->tbl.d_sphi;
       ta.npT = npT; ta.nphi = nphi; ta.nphp = KJ; ta.tab = tab; ta.phn = phn; ta.by = P.by != 0;
       ta.gate = gate; ta.gate_want = want;
+      // the chunk's y-term rows (k_ytab), behind its phi rows in the same buffer: k_spectra finds them at
+      // phtab + npT phn rw
+      YTabArgs ya{};
+      ya.rec = rec_w; ya.c0 = c0; ya.nc = ncc; ya.yv = e->tbl.d_y; ya.etav = e->tbl.d_eta; ya.etaw = e->tbl.d_etaw;
+      ya.nk = nk; ya.nl = nl; ya.dim = dim; ya.op = sa.op; ya.tab = tab + phn * npT * rw;
+      ya.gate = gate; ya.gate_want = want;
       SpecArgs sc = sa;
       sc.split0 = (int)s0; sc.nsplit = (int)ns; sc.phtab = tab; sc.phn = phn; sc.phc0 = c0; sc.phrow = (int)rw;
       double* buf = e->ws.d_slab.get() + (1 + (ic & 1) * spc) * I.sstride;
       if (I.fold) { sc.slab = buf; sc.slab0 = (int)s0; }
       const dim3 grid((unsigned)(wgs * ns));
-      if (mode == GRAD) launch_phitab<GRAD>(cs, ta);
-      else launch_phitab<CE>(cs, ta);
+      if (mode == GRAD) { launch_phitab<GRAD>(cs, ta); launch_ytab<GRAD>(cs, ya); }
+      else { launch_phitab<CE>(cs, ta); launch_ytab<CE>(cs, ya); }
       // a folded chunk reusing slab buffer ic & 1 waits for the fold of chunk ic - 2, which emptied it
       if (I.fold && ic >= 2) HIPCHK(e, hipStreamWaitEvent(cs, e->ws.ev_fold[ic & 1].get(), 0));
       if (mode == GRAD) launch_spectra<GRAD>(grid, shmem, cs, sc, kflags, KJ);

@@ -57,6 +57,51 @@ __global__ __launch_bounds__(256) void k_prep(PrepArgs A) {
   for (int f = 0; f < NREC; f++) A.rec[c * NREC + f] = R[f];
 }
 
+// k_ytab: the y-term rows of one chunk of cells for the F_TS k_spectra launches, rows [cell - c0][q][kYRowTS], one
+// thread per (cell, q).  yterms() depends on (cell, q) only; built inside k_spectra, every workgroup's wave 0 rebuilt
+// its 2-3 q rows for each of the pT values and lane groups (~110 evaluations per (cell, q) at 48 pT x 193 classes x 21 y).
+// The same call as k_spectra's other launches make (tables_ab): 3+1D q = y index and eta from the record, 2+1D
+// q = y x eta node.  Rows of skipped cells (R_KIND == 0) are copied but never used: zeros.
+struct YTabArgs {
+  const double* rec; long c0, nc;           // records of the launch window, first cell and cells of the chunk
+  const double *yv, *etav, *etaw;
+  int nk, nl, dim, op;
+  double* tab;                              // [nc][nk nl][kYRowTS]
+  const unsigned long long* gate; int gate_want;   // as SpecArgs
+};
+
+template <int MODE>
+__global__ __launch_bounds__(256) void k_ytab(YTabArgs A) {
+  if (gate_closed(A.gate, A.gate_want)) return;
+  const int nq = A.nk * A.nl;
+  const long total = A.nc * nq;
+  for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+    const long c = idx / nq;
+    const int q = (int)(idx % nq), kk = q / A.nl, l = q % A.nl;
+    const double* R = A.rec + (A.c0 + c) * NREC;
+    double Y[NYT];
+#pragma unroll
+    for (int f = 0; f < NYT; f++) Y[f] = 0.0;
+    if (R[R_KIND] != 0.0) {
+      const double y = (A.dim == 3) ? A.yv[kk] : 0.0;
+      const double eta = (A.dim == 3) ? R[R_ETA] : A.etav[l];
+      const double w = (A.dim == 3) ? 1.0 : A.etaw[l];
+      yterms(MODE, A.op, R, y, eta, w, Y, true, false);
+    }
+    double* row = A.tab + idx * kYRowTS;
+#pragma unroll
+    for (int f = 0; f < kYW_TS; f++) row[f] = Y[f];
+    row[kYW_TS] = Y[Y_W];
+  }
+}
+
+template <int MODE>
+void launch_ytab(hipStream_t st, const YTabArgs& a) {
+  const long total = a.nc * a.nk * a.nl;
+  const long blocks = std::max(1L, std::min((total + 255) / 256, 256L * 32));
+  hipLaunchKernelGGL((k_ytab<MODE>), dim3((unsigned)blocks), dim3(256), 0, st, a);
+}
+
 // sum over the W wavefronts of a workgroup (W x 64 lanes share one cell's Newton terms): each wave's sums, then the
 // W partials from LDS in wave order (every lane gets the same bits), two barriers per red_all call of up to kRedN
 // values

@@ -132,6 +132,12 @@ constexpr int kYRow = NYT | 1;
 // per-lane y-term rows of the F_LY / F_FB launches: without the Y_MU2 / Y_MU slots (17 doubles, odd): the
 // 256 rows are LDS the launch's occupancy depends on, and each lane's row serves one lane only
 constexpr int kYRowLY = Y_MU2 | 1;
+// y-term rows of the F_TS launches: built once per pass by k_ytab (engine_kernels.h), rows [cell][q][kYRowTS] in HBM,
+// and copied into LDS as they are.  Only the slots the F_TS lanes and the T1 build read: Y_AT .. Y_L1 at their YT
+// index and w_eta (Y_W) at kYW_TS; 11 doubles, odd as kYRow
+constexpr int kYW_TS = Y_L1 + 1;
+constexpr int kYRowTS = kYW_TS + 1;
+static_assert(Y_AT == 0 && Y_L1 == 9 && (kYRowTS & 1), "F_TS y-term row: the separable slots lead the YT enum");
 
 // ------------------------------------------------------------------------------------------
 // spectra kernel
@@ -587,7 +593,9 @@ __global__ __launch_bounds__(kBlock, (spectra_waves_f<MODE, FLAGS>())) void k_sp
   constexpr int kET = kExpTabN;     // exp table entries at LDS offset 0 (the modified lanes share the table)
   // y-term rows per cell: per row, or per q once the rows cover every q (nyr below): min(nqm, nq);
   // LY launches: one y-term row per lane instead ([kBlock][kYRowLY], single; odd row stride: no conflicts)
-  const long ysz = LY ? (long)kBlock * kYRowLY : (long)kTile * min(nqm, A.nq) * kYRow;
+  // F_TS: k_ytab's rows (kYRowTS doubles), copied in from HBM
+  constexpr int YR = TS ? kYRowTS : kYRow;
+  const long ysz = LY ? (long)kBlock * kYRowLY : (long)kTile * min(nqm, A.nq) * YR;
   // the exp table first: at LDS offset 0 its address is the table index alone (no base register, which
   // the modified loop otherwise re-read from an SGPR spill lane at every point)
   double* s_etab = smem;                                  // [kET] 2^(j/kET)
@@ -598,7 +606,7 @@ __global__ __launch_bounds__(kBlock, (spectra_waves_f<MODE, FLAGS>())) void k_sp
   // Grad / RTA-CE: [kTabBufs][kTile][nphp] PD table; modified path: {PDm, Qv} pairs (s_mw)
   double* s_qv = (double*)(s_bp + kTabBufs * bpa);
   double* s_grid = s_qv + kTabBufs * qvsz;                // y[nk] | eta[nl] | eta_w[nl]
-  double* s_y = s_grid + A.nk + 2 * A.nl;                 // [kTabBufs (LY: 1)][kTile][min(nqm, nq)][kYRow]
+  double* s_y = s_grid + A.nk + 2 * A.nl;                 // [kTabBufs (LY: 1)][kTile][min(nqm, nq)][YR]
   // TB: [kTile][nqm][prow] {PD, T1}, 16-byte aligned for ds_read_b128 (s_grid's nk + 2 nl doubles
   // can leave the y-term rows' end at an odd double; misaligned dbl2 reads ran the kernel 3.5x slower)
   dbl2* s_pt = (dbl2*)(smem + (((s_y + (LY ? 1 : kTabBufs) * ysz) - smem + 1) & ~1L));
@@ -744,7 +752,8 @@ __global__ __launch_bounds__(kBlock, (spectra_waves_f<MODE, FLAGS>())) void k_sp
         pe[t * nphp + j] = e;
       }
     }
-    for (int idx = tid; idx < (LY ? 0 : ntx * nyr); idx += kBlock) {
+    // (none in F_TS launches: their rows come from k_ytab's table, fetch_y below)
+    for (int idx = tid; idx < (LY || TS ? 0 : ntx * nyr); idx += kBlock) {
       const int t = idx / nyr, qq = idx % nyr, q = allq ? qq : (int)((r0 + qq) % A.nq);
       const double* R = s_rec + t * NREC;
       if (R[R_KIND] != 0.0) {
@@ -783,12 +792,17 @@ __global__ __launch_bounds__(kBlock, (spectra_waves_f<MODE, FLAGS>())) void k_sp
     // the separable launches keep their round-5 index arithmetic (integer divisions): with tab_index the F_TS kernels
     // compiled to the same loops but ran 1-1.5% slower (profiles/round6_r6j_ab_bisect.log)
     if constexpr (TS) {
-      // T1 = SC1 pc + SS1 ps per (cell, q row, phi) (one phi block: phi slot jj)
-      for (int idx = tid; idx < ntx * nqw * KJ; idx += kBlock) {
-        const int jj = idx % KJ, r = idx / KJ, qq = r % nqw, t = r / nqw;
-        const double* Y = yb + ((long)t * nyr + (allq ? (int)((r0 + qq) % A.nq) : qq)) * kYRow;
+      // T1 = SC1 pc + SS1 ps per (cell, q row, phi) (one phi block: phi slot jj).  The T1 rows and the y-term rows
+      // share the index r = t nqw + qq, so a thread keeps its phi slot and walks the rows by a constant stride: no
+      // index division (KJ = 24: ten rows at a time, sixteen threads idle)
+      constexpr int NS = kBlock / KJ;
+      if (tid < NS * KJ) {
+        const int jj = tid % KJ;
         const dbl2 c = s_cs[jj];
-        s_t1[((long)t * nqw + qq) * prow2 + jj] = fma(Y[Y_SC1], c.x, Y[Y_SS1] * c.y);
+        for (int r = tid / KJ; r < ntx * nqw; r += NS) {
+          const double* Y = yb + r * kYRowTS;
+          s_t1[r * prow2 + jj] = fma(Y[Y_SC1], c.x, Y[Y_SS1] * c.y);
+        }
       }
     } else if constexpr (TB) {
       // {PD, T1 = SC1 pc + SS1 ps} per (cell, q, phi) (rows of skipped cells are never read)
@@ -818,7 +832,29 @@ __global__ __launch_bounds__(kBlock, (spectra_waves_f<MODE, FLAGS>())) void k_sp
   auto tile_cb = [&](int i) { return c_begin + (long)i * kTile; };
   auto tile_nt = [&](int i) { return (int)min((long)kTile, c_end - tile_cb(i)); };
   auto recbuf = [&](int i) { return s_recb + (i % kRecBufs) * recsz; };
+  // F_TS: the y-term rows of tile i from k_ytab's table (behind this chunk's k_phitab rows: [cell - phc0][nq][kYRowTS])
+  // into y-term buffer i & 1 by LDS-DMA, as fetch_tile.  With one phi block a row is a q, so a cell's rows r0 .. r0 +
+  // nqw - 1 are one contiguous segment, which lands as the [nqw][kYRowTS] block of the cell; a wavefront copies a
+  // cell's segment dword by dword (rows of an odd number of doubles are 8-byte aligned only)
+  auto fetch_y = [&](int i) __attribute__((always_inline)) {
+    if constexpr (TS) {
+      constexpr int RW = phitab_row(MODE, KJ, (FLAGS & F_BY) != 0);
+      const float* ytab = (const float*)(A.phtab + (long)A.npT * A.phn * RW);
+      float* yb = (float*)(s_y + (i & 1) * ysz);
+      const long cb = tile_cb(i);
+      const int ntx = tile_nt(i), seg = 2 * kYRowTS * nqw, lane = tid & 63;
+      for (int t = __builtin_amdgcn_readfirstlane(tid >> 6); t < ntx; t += kBlock / 64) {
+        const float* src = ytab + ((cb + t - A.phc0) * A.nq + r0) * (2 * kYRowTS);
+        for (int b = 0; b < seg; b += 64) {
+          if (b + lane < seg)
+            __builtin_amdgcn_global_load_lds((const void*)(src + b + lane),
+                                             (__attribute__((address_space(3))) void*)(yb + t * seg + b), 4, 0, 0);
+        }
+      }
+    }
+  };
   for (int i = 0; i < min(ntiles, kRecBufs - 1); i++) fetch_tile<kTile>(A.rec, tile_cb(i), c_end, recbuf(i), fbl);
+  if (ntiles > 0) fetch_y(0);
   if (PIPE && ntiles > 0) {
     wait_fetch();
     lds_barrier();     // tiles 0 and 1, the trig / grid / exp tables visible
@@ -831,6 +867,8 @@ __global__ __launch_bounds__(kBlock, (spectra_waves_f<MODE, FLAGS>())) void k_sp
     wait_fetch();
     lds_barrier();     // X: this tile's records (and, pipelined, its A / B tables) visible; the last tile is done
     if (i + kRecBufs - 1 < ntiles) fetch_tile<kTile>(A.rec, tile_cb(i + kRecBufs - 1), c_end, recbuf(i + kRecBufs - 1), fbl);
+    // (y-term buffer (i + 1) & 1 was last read by the lanes of tile i - 1, before barrier X)
+    if (i + 1 < ntiles) fetch_y(i + 1);
     constexpr int PFD = (MODE == GRAD) ? IS3D_TS_PF_DIST_GRAD : IS3D_TS_PF_DIST_CE;
     if (i + PFD < ntiles) {
       if constexpr (TS) {
@@ -883,7 +921,7 @@ __global__ __launch_bounds__(kBlock, (spectra_waves_f<MODE, FLAGS>())) void k_sp
         const long tro = ((long)lp * kTile + t) * nphp + j0;
         const dbl2* BP = bpt + tro;
         const dbl2* CSl = s_cs + lp * nphp + j0;
-        const double* Y = yb + ((long)t * nyr + yrow) * kYRow;
+        const double* Y = yb + ((long)t * nyr + yrow) * YR;
         if constexpr (LY) {        // this lane's own y-terms, in its LDS row
           double* Yl = s_y + (long)tid * kYRowLY;
           const int kk = q / A.nl, l = q % A.nl;
@@ -907,7 +945,7 @@ __global__ __launch_bounds__(kBlock, (spectra_waves_f<MODE, FLAGS>())) void k_sp
           // wavefront: a wave mixing tail and other lanes runs one loop.  Not RTA-CE's F_TB launch: its tail fours
           // were 3% slower (r2d A/B: 697 vs 675 ms)
           sep_setup(sep_flavor(MODE), R, Y, mT, mT2, m2, mTb, pT, sign, baryon, s_etab, L,
-                    ((TB && (MODE == GRAD || TS)) || PDT) ? 2 : 0, NEAR ? 2 : 0);
+                    ((TB && (MODE == GRAD || TS)) || PDT) ? 2 : 0, NEAR ? 2 : 0, false, TS ? kYW_TS : Y_W);
           if (L.skip) continue;
           if constexpr (TS) {
             // this cell's k_phitab row (wave-uniform: ipt, the tile and t are) and the lane's T1 row

@@ -25,7 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def short(name):
-    for k in ("k_spectra", "k_dndx", "k_phitab", "k_reduce", "k_prep", "k_aniso", "k_chain_pass", "k_famod_b", "k_renorm", "k_df_eval"):
+    for k in ("k_spectra", "k_dndx", "k_phitab", "k_ytab", "k_reduce", "k_prep", "k_aniso", "k_chain_pass", "k_famod_b", "k_renorm", "k_df_eval"):
         if k in name:
             return name[name.index(k):].split("(")[0]
     return name.split("(")[0][:60]
