@@ -23,6 +23,8 @@
  *                                     calculate_dN_pTdpTdphidy_famod           (MomentumSpectra.cpp:1517-1621)
  *   is3d_get_cell_yields              dN_dy_cell of each freeze-out cell       (SpacetimeDistribution.cpp:374)
  *   is3d_evaluate_df_coefficients     Deltaf_Data::evaluate_df_coefficients    (DeltafData.cpp:501-519)
+ *   is3d_generate_df_tables           the offline generator of deltaf_coefficients/vh/<list>/<name>.dat
+ *                                     (generate_delta_f_coefficients/<list>/df_vh_dimensionless/src/deltaf_table.cpp)
  *   is3d_surface_averages             ds_max-weighted averages (Plasma)        (readindata.cpp:316-366, iS3D.cpp:184-219)
  *   is3d_total_yield                  calculate_total_yield (operation 2       (ParticleSampler.cpp:447-636,
  *                                     oversampling) + particle densities        DeltafData.cpp:555-690)
@@ -271,6 +273,22 @@ int is3d_get_cell_yields(const is3d_engine *e, double *dN_dy_cell);
  * betabulk betaV betapi lambda z delta_lambda delta_z (evaluated on the GPU). */
 int is3d_evaluate_df_coefficients(is3d_engine *e, double T, double muB, double E, double P,
                                   double bulkPi, double *out15);
+/* The ten delta-f coefficient tables of the PDG list on a (T, muB) grid, computed on the GPU: the reference's offline
+ * generator (generate_delta_f_coefficients/<list>/df_vh_dimensionless: deltaf_table.cpp, thermal_integrands.cpp,
+ * gauss_integration.cpp) with its prefactors, its closing algebra ("update 3/25" bulk form, alphaB form of G, F and
+ * betabulk, hbarc = 0.197327053) and its scaling by powers of T, so that the shipped files are these values rounded to
+ * six decimals.
+ * tables[10][nmuB][nT] in the order of is3d_set_df_tables, from the PDG set with is3d_set_pdg and the
+ * Gauss-Laguerre table set with is3d_set_gauss_laguerre (alpha >= 5: rows 1..4 are used).
+ * Reads engine inputs only: it installs nothing and invalidates nothing; pass the result to is3d_set_df_tables.
+ * A value is a pure function of (PDG list, Gauss-Laguerre table, T, muB): repeats and other grids holding the same
+ * point give the same bits.  A device-list engine runs it on devices[0].
+ * Errors: IS3D_ERR_STATE without a PDG or with fewer than five Gauss-Laguerre rows; IS3D_ERR_ARG for a null pointer,
+ * nT < 1, nmuB < 1, T <= 0 or a grid that is not strictly ascending; IS3D_ERR_DF_RANGE when a value is not finite or
+ * one of the reference's exit(-1) checks fires -- is3d_last_error then holds the reference's message ("Bulk
+ * denominator is zero", "Diffusion denominator is zero", "Shear denominator is zero") and the first (T, muB) it
+ * occurs at, in the reference's loop order; a list without baryons is such a case. */
+int is3d_generate_df_tables(is3d_engine *e, int nT, int nmuB, const double *T, const double *muB, double *tables);
 /* out[5] = T, E, P, muB, nB averages (after the setprecision(15) round trip). */
 int is3d_surface_averages(long n_cells, const is3d_surface *s, int include_baryon, double *out5);
 /* Jonah table the engine built: lambda^2, z, bulkPi/P (301 each) and the max. */

@@ -18,6 +18,7 @@
  *                                                                                        EmissionFunction.cpp:561-609)
  *   is3d_host_read_pdg             PDG_Data::read_resonances                            (readindata.cpp:1217-1252)
  *   is3d_host_read_decays          ... its decay rows, with the antibaryon rule         (readindata.cpp:997-1007, 1035-1056)
+ *   is3d_host_read_df_tables       Deltaf_Data::load_df_coefficient_data of one directory (DeltafData.cpp:65-217)
  *   is3d_host_param                ParameterReader::getVal                             (ParameterReader.cpp:142-155)
  */
 #ifndef IS3D_HOST_H
@@ -27,7 +28,15 @@
 extern "C" {
 #endif
 
-/* do_resonance_decays = 1 in iS3D_parameters.dat with operation = 1: the decay rows of the PDG file are applied to the
+/* generate_df_coefficients = 1 in iS3D_parameters.dat (ours; 0 or absent: nothing changes): deltaf_coefficients/ is not
+ * read; the delta-f tables are generated on the GPU from the run's PDG list (is3d_generate_df_tables, is3d_amd.h) on
+ * the shipped grid -- T 0.1 .. 0.2 GeV in 101 points, muB 0 .. 0.8 GeV in 81 -- or on the grid of the optional keys
+ * df_T_min, df_T_max, df_T_points, df_muB_min, df_muB_max, df_muB_points, and installed.  The Gauss-Laguerre table is
+ * tables/gla_roots_weights_64_points.txt (the generator's own 64-point file, the reference's layout), or, where the
+ * run directory has none, tables/gauss/gla_roots_weights.txt.  = 2: the ten files are also written to
+ * results/deltaf_coefficients/ in the reference's format (six decimals).  Every operation of the run uses the tables.
+ *
+ * do_resonance_decays = 1 in iS3D_parameters.dat with operation = 1: the decay rows of the PDG file are applied to the
  * spectra (is3d_set_decays + is3d_decay_feeddown, include/is3d_amd.h) between the spectra and the writers, so
  * results/continuous and dN_out hold thermal + feed-down, and the channel counts are printed.  With the key 0 or
  * absent, or under another operation, nothing changes.  lightest_particle is read and not used, as in the reference.
@@ -114,6 +123,11 @@ int is3d_host_read_pdg(const char *workdir, int hrg_eos, int capacity, long *mci
  * parent mcid, n_body as written, branching, daughters[n][5]. */
 long is3d_host_read_decays(const char *workdir, int hrg_eos, long capacity, long *parent, int *n_body,
                            double *branching, long *daughters);
+/* The ten delta-f coefficient files c0.dat .. betapi.dat of one directory (a run directory's
+ * deltaf_coefficients/vh/<list>/, results/deltaf_coefficients/, or what hrg.write_df_tables wrote): returns 0 (or -1) and
+ * the grid sizes; T[nT], muB[nmuB], tables[10][nmuB][nT] are optional (capacity = doubles in tables). */
+int is3d_host_read_df_tables(const char *table_dir, int *nT, int *nmuB, long capacity, double *T, double *muB,
+                             double *tables);
 int is3d_host_param(const char *path, const char *key, double *value);
 
 #ifdef __cplusplus

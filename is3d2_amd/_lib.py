@@ -32,7 +32,7 @@ EXPORTS = ["is3d_abi_version", "is3d_build_id", "is3d_create", "is3d_create_devi
            "is3d_calculate_dN_dX_famod",
            "is3d_set_decays", "is3d_decay_feeddown", "is3d_launch_feeddown", "is3d_get_decay_stats",
            "is3d_decay_particles", "is3d_decay_sampled", "is3d_get_particle_origins", "is3d_get_decay_list_stats",
-           "is3d_sample_decayed"]
+           "is3d_sample_decayed", "is3d_generate_df_tables"]
 
 VORTICITY_FIELDS = ["wtx", "wty", "wtn", "wxy", "wxn", "wyn"]
 
@@ -168,6 +168,7 @@ def load():
     lib.is3d_output_size.restype = C.c_long
     lib.is3d_output_size.argtypes = [C.c_void_p]
     lib.is3d_evaluate_df_coefficients.argtypes = [C.c_void_p, d, d, d, d, d, pd]
+    lib.is3d_generate_df_tables.argtypes = [C.c_void_p, C.c_int, C.c_int, pd, pd, pd]
     lib.is3d_surface_averages.argtypes = [C.c_long, P(Surface), C.c_int, pd]
     lib.is3d_get_jonah_table.argtypes = [C.c_void_p, pd, pd, pd, pd]
     lib.is3d_set_momentum_weights.argtypes = [C.c_void_p, pd, pd]

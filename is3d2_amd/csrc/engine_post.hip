@@ -1,12 +1,18 @@
 // engine_post.hip -- what the engine (engine.h) does to or beside the continuous spectra: spin polarization from thermal
-// vorticity and the resonance-decay feed-down.  Host side only: the kernels are in polzn.hip and decay.hip.
+// vorticity, the resonance-decay feed-down and the delta-f coefficient generator.  Host side only: the kernels are in
+// polzn.hip, decay.hip and dfgen.hip.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
+#include <cstdio>
 #include <string>
+#include <vector>
 
 #include "../../include/is3d_amd.h"
 #include "group.h"
 #include "engine.h"
+#include "dfgen.h"
+#include "dfgen_math.h"
 
 using namespace is3d;
 
@@ -160,5 +166,49 @@ extern "C" int is3d_decay_feeddown(is3d_engine* e, double* dN) {
   rc = is3d_finish(e);
   if (rc) return rc;
   HIPCHK(e, hipMemcpy(dN, e->fd.d_io.get(), n * sizeof(double), hipMemcpyDeviceToHost));
+  return IS3D_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// the delta-f coefficient tables of the PDG list (generate_delta_f_coefficients/*/df_vh_dimensionless; dfgen.hip)
+// ------------------------------------------------------------------------------------------
+extern "C" int is3d_generate_df_tables(is3d_engine* e, int nT, int nmuB, const double* T, const double* muB, double* tables) {
+  if (e && e->grp) return is3d::group_generate_df_tables(e->grp, nT, nmuB, T, muB, tables);
+  if (!e) return IS3D_ERR_ARG;
+  if (!T || !muB || !tables) return e->fail(IS3D_ERR_ARG, "df generator: null argument");
+  if (nT < 1 || nmuB < 1) return e->fail(IS3D_ERR_ARG, "df generator: the (T, muB) grid needs at least one point each way");
+  if ((long)nT * nmuB > (1L << 24)) return e->fail(IS3D_ERR_ARG, "df generator: more than 2^24 grid points");
+  for (int i = 0; i < nT; i++)
+    if (!(T[i] > 0.0) || !std::isfinite(T[i])) return e->fail(IS3D_ERR_ARG, "df generator: T must be positive");
+  for (int i = 0; i < nmuB; i++)
+    if (!std::isfinite(muB[i])) return e->fail(IS3D_ERR_ARG, "df generator: muB must be finite");
+  for (int i = 1; i < nT; i++)
+    if (!(T[i] > T[i - 1])) return e->fail(IS3D_ERR_ARG, "df generator: the T grid must be strictly ascending");
+  for (int i = 1; i < nmuB; i++)
+    if (!(muB[i] > muB[i - 1])) return e->fail(IS3D_ERR_ARG, "df generator: the muB grid must be strictly ascending");
+  if (!e->in.have_pdg) return e->fail(IS3D_ERR_STATE, "df generator: is3d_set_pdg not called");
+  if (!e->in.have_gla || e->in.gla_alpha < 1 + dfgen::kFamilies)
+    return e->fail(IS3D_ERR_STATE, "df generator: needs a Gauss-Laguerre table with the rows alpha = 1 .. 4 (is3d_set_gauss_laguerre, alpha >= 5)");
+  const int nh = (int)e->in.pdg_mass.size(), npts = e->in.gla_pts;
+  std::vector<double> had((size_t)dfgen::kHadronStride * nh);
+  for (int h = 0; h < nh; h++) {
+    double* r = &had[(size_t)dfgen::kHadronStride * h];
+    r[0] = e->in.pdg_mass[h]; r[1] = e->in.pdg_degen[h]; r[2] = e->in.pdg_baryon[h]; r[3] = e->in.pdg_sign[h];
+  }
+  // rows 1 .. 4 of the table; the node weights w e^root once, on the host
+  const size_t ngl = (size_t)dfgen::kFamilies * npts;
+  std::vector<double> roots(e->in.gla_r.begin() + npts, e->in.gla_r.begin() + npts + ngl), wts(ngl);
+  for (size_t k = 0; k < ngl; k++) wts[k] = dfgen::node_weight(roots[k], e->in.gla_w[npts + k]);
+  std::vector<int> codes((size_t)nT * nmuB);
+  HIPCHK(e, hipSetDevice(e->device));
+  const std::string msg = dfgen::generate(nh, had.data(), npts, roots.data(), wts.data(), nT, nmuB, T, muB, tables, codes.data());
+  if (!msg.empty()) return e->fail(IS3D_ERR_DEVICE, msg);
+  int code = dfgen::OK;
+  const long at = dfgen::first_error(codes.data(), (long)codes.size(), &code);
+  if (at >= 0) {
+    char where[96];
+    std::snprintf(where, sizeof where, " at T = %.17g GeV, muB = %.17g GeV", T[at % nT], muB[at / nT]);
+    return e->fail(IS3D_ERR_DF_RANGE, std::string(dfgen::message(code)) + where);
+  }
   return IS3D_OK;
 }

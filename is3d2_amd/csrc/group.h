@@ -49,6 +49,7 @@ int group_get_cell_yields(const Group* g, double* dN_dy_cell);
 int group_get_stats(const Group* g, is3d_stats* out);
 long group_output_size(const Group* g);
 int group_evaluate_df_coefficients(Group* g, double T, double muB, double E, double P, double bulkPi, double* out15);
+int group_generate_df_tables(Group* g, int nT, int nmuB, const double* T, const double* muB, double* tables);
 int group_total_yield(Group* g, const double* plasma, double y_cut, double* n_total, double* densities);
 int group_get_jonah_table(const Group* g, double* l2, double* z, double* bp, double* bpmax);
 // spin polarization (mode 5): every shard gets the vorticity of its window, runs polzn.hip's kernels on it, and the

@@ -658,6 +658,11 @@ int group_evaluate_df_coefficients(Group* g, double T, double muB, double E, dou
   return rc ? g->shard_fail(0, rc) : IS3D_OK;
 }
 
+int group_generate_df_tables(Group* g, int nT, int nmuB, const double* T, const double* muB, double* tables) {
+  const int rc = is3d_generate_df_tables(g->sh[0], nT, nmuB, T, muB, tables);
+  return rc ? g->shard_fail(0, rc) : IS3D_OK;
+}
+
 int group_total_yield(Group* g, const double* plasma, double y_cut, double* n_total, double* densities) {
   if (!plasma || !n_total) return g->fail(IS3D_ERR_ARG, "null argument");
   if (stale_split(g)) return g->fail(IS3D_ERR_STATE, kStaleSplit);

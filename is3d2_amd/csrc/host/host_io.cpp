@@ -360,12 +360,11 @@ std::string read_pdg(const std::string& dir, int hrg_eos, std::vector<Particle>&
 // ---------------------------------------------------------------------------------------------
 // delta-f tables, Gauss-Laguerre
 // ---------------------------------------------------------------------------------------------
-std::string read_df_tables(const std::string& dir, int hrg_eos, DfTablesData& d) {
-  const char* sub = hrg_eos == 1 ? "urqmd" : hrg_eos == 2 ? "smash" : hrg_eos == 3 ? "smash_box" : nullptr;
-  if (!sub) return "Error: please choose hrg_eos = (1,2,3)";
-  static const char* names[10] = {"c0", "c1", "c2", "c3", "c4", "F", "G", "betabulk", "betaV", "betapi"};
+static const char* const kDfNames[10] = {"c0", "c1", "c2", "c3", "c4", "F", "G", "betabulk", "betaV", "betapi"};
+
+std::string read_df_table_dir(const std::string& tdir, DfTablesData& d) {
   for (int k = 0; k < 10; k++) {
-    const std::string path = join(dir, std::string("deltaf_coefficients/vh/") + sub + "/" + names[k] + ".dat");
+    const std::string path = join(tdir, std::string(kDfNames[k]) + ".dat");
     std::ifstream f(path);
     if (!f) return "Couldn't open " + path;
     int nT = 0, nmuB = 0;
@@ -384,6 +383,12 @@ std::string read_df_tables(const std::string& dir, int hrg_eos, DfTablesData& d)
       }
   }
   return "";
+}
+
+std::string read_df_tables(const std::string& dir, int hrg_eos, DfTablesData& d) {
+  const char* sub = hrg_eos == 1 ? "urqmd" : hrg_eos == 2 ? "smash" : hrg_eos == 3 ? "smash_box" : nullptr;
+  if (!sub) return "Error: please choose hrg_eos = (1,2,3)";
+  return read_df_table_dir(join(dir, std::string("deltaf_coefficients/vh/") + sub), d);
 }
 
 std::string read_gauss_laguerre(const std::string& path, int& alpha, int& points, std::vector<double>& roots,
@@ -411,6 +416,26 @@ static void mkdirs(const std::string& path) {
     if (path[i] == '/' && cur.size() > 1) mkdir(cur.c_str(), 0755);
   }
   mkdir(path.c_str(), 0755);
+}
+
+std::string write_df_tables(const std::string& dir, const DfTablesData& d) {
+  static const char* labels[10] = {"c0_T4 [fm^3/GeV^3 * GeV^4]", "c1_T3 [fm^3/GeV^2 * GeV^3]", "c2_T4 [fm^3/GeV^3 * GeV^4]",
+                                   "c3_T4 [fm^3/GeV * GeV^4]", "c4_T5 [fm^3/GeV^2 * GeV^5]", "F_over_T [fm^-1 / GeV]", "G [1]",
+                                   "betabulk_over_T4 [fm^-4 / GeV^4]", "betaV_over_T3 [fm^-3 / GeV^3]",
+                                   "betapi_over_T4 [fm^-4 / GeV^4]"};
+  const std::string out = join(dir, "results/deltaf_coefficients");
+  mkdirs(out);
+  for (int k = 0; k < 10; k++) {
+    const std::string path = out + "/" + kDfNames[k] + ".dat";
+    FILE* f = std::fopen(path.c_str(), "w");
+    if (!f) return "cannot write " + path;
+    std::fprintf(f, "%d\n%d\nT [GeV]\t\tmuB [GeV]\t\t%s\n", d.nT, d.nmuB, labels[k]);
+    for (int iB = 0; iB < d.nmuB; iB++)
+      for (int iT = 0; iT < d.nT; iT++)    // fixed << setw(8) << T << muB << value, six decimals
+        std::fprintf(f, "%8.6f\t\t%.6f\t\t%.6f\n", d.T[iT], d.muB[iB], d.tab[((size_t)k * d.nmuB + iB) * d.nT + iT]);
+    std::fclose(f);
+  }
+  return "";
 }
 
 std::string write_polzn_files(const std::string& dir, const PolznView& v) {

@@ -77,6 +77,12 @@ void decode_mcid(long mcid, int& gspin, int& baryon, int& sign, bool& has_antipa
 // c0 c1 c2 c3 c4 F G betabulk betaV betapi from <dir>/deltaf_coefficients/vh/<hrg>/.
 struct DfTablesData { int nT = 0, nmuB = 0; std::vector<double> T, muB, tab; };   // tab[10][nmuB][nT]
 std::string read_df_tables(const std::string& dir, int hrg_eos, DfTablesData& d);
+// ... from the ten files c0.dat .. betapi.dat of one directory
+std::string read_df_table_dir(const std::string& table_dir, DfTablesData& d);
+// generate_df_coefficients = 2: the ten files under <dir>/results/deltaf_coefficients/ in the format of the
+// reference's generator (deltaf_table.cpp:122-133, 240-244: nT, nmuB, the label line, rows "T  muB  value" with muB
+// outer and T inner, fixed with six decimals), which read_df_table_dir and the reference read
+std::string write_df_tables(const std::string& dir, const DfTablesData& d);
 
 // Gauss_Laguerre::load_roots_and_weights (readindata.cpp:26-61)
 std::string read_gauss_laguerre(const std::string& path, int& alpha, int& points, std::vector<double>& roots,

@@ -341,6 +341,42 @@ static std::string path_in(const std::string& dir, const std::string& rel) {
   return (dir.empty() || dir == ".") ? rel : dir + "/" + rel;
 }
 
+// generate_df_coefficients = 1 | 2: the delta-f tables of the run's PDG list from the engine (is3d_generate_df_tables)
+// on the shipped grid (T 0.1 .. 0.2 GeV, 101 points; muB 0 .. 0.8 GeV, 81 points) or the df_T_* / df_muB_* keys', with
+// the 64-point Gauss-Laguerre table tables/gla_roots_weights_64_points.txt (the generator's own), or, where the run
+// directory has none, the run's tables/gauss/gla_roots_weights.txt
+static void generate_df_tables(const std::string& dir, const ParameterReader& prm, const std::vector<Particle>& parts,
+                               const RunOptions& opt, DfTablesData& df) {
+  df.nT = (int)prm.get("df_T_points", 101.0);
+  df.nmuB = (int)prm.get("df_muB_points", 81.0);
+  check(df.nT >= 1 && df.nmuB >= 1, "generate_df_coefficients: df_T_points and df_muB_points must be at least 1");
+  const double T0 = prm.get("df_T_min", 0.1), T1 = prm.get("df_T_max", 0.2);
+  const double B0 = prm.get("df_muB_min", 0.0), B1 = prm.get("df_muB_max", 0.8);
+  // deltaf_table.cpp:58-71
+  const double dT = df.nT > 1 ? (T1 - T0) / (double)(df.nT - 1) : 0.0, dB = df.nmuB > 1 ? (B1 - B0) / (double)(df.nmuB - 1) : 0.0;
+  df.T.assign(df.nT, T0);
+  df.muB.assign(df.nmuB, B0);
+  for (int i = 1; i < df.nT; i++) df.T[i] = T0 + (double)i * dT;
+  for (int i = 1; i < df.nmuB; i++) df.muB[i] = B0 + (double)i * dB;
+  df.tab.assign((size_t)10 * df.nmuB * df.nT, 0.0);
+  int galpha = 0, gpts = 0;
+  std::vector<double> gr, gw;
+  std::string err = read_gauss_laguerre(path_in(dir, "tables/gla_roots_weights_64_points.txt"), galpha, gpts, gr, gw);
+  if (!err.empty()) err = read_gauss_laguerre(path_in(dir, "tables/gauss/gla_roots_weights.txt"), galpha, gpts, gr, gw);
+  check(err.empty(), err);
+  std::vector<double> mass, sign, degen, baryon;
+  for (const auto& q : parts) { mass.push_back(q.mass); sign.push_back(q.sign); degen.push_back(q.gspin); baryon.push_back(q.baryon); }
+  const int dev = opt.devices.empty() ? opt.device : opt.devices[0];
+  is3d_engine* e = is3d_create(dev);
+  if (!e) throw EngineError(IS3D_ERR_DEVICE, "is3d_create on device " + std::to_string(dev) + " failed");
+  int rc = is3d_set_pdg(e, (int)mass.size(), mass.data(), sign.data(), degen.data(), baryon.data());
+  if (!rc) rc = is3d_set_gauss_laguerre(e, galpha, gpts, gr.data(), gw.data());
+  if (!rc) rc = is3d_generate_df_tables(e, df.nT, df.nmuB, df.T.data(), df.muB.data(), df.tab.data());
+  const std::string msg = rc ? std::string("is3d engine: ") + is3d_last_error(e) : "";
+  is3d_destroy(e);
+  if (rc) throw EngineError(rc, msg);
+}
+
 void IS3D::run_particlization(int fo_from_file, const RunOptions& opt) {
   ParameterReader prm;
   check(prm.read_file(path_in(dir_, "iS3D_parameters.dat")), "ParameterReader::readFromFile error: file iS3D_parameters.dat does not exist.");
@@ -368,7 +404,13 @@ void IS3D::run_particlization(int fo_from_file, const RunOptions& opt) {
   check(load_table(path_in(dir_, "PDG/chosen_particles.dat"), chosen), "cannot read PDG/chosen_particles.dat");
   DfTablesData df;          // the polarization alone uses neither the df tables nor the Gauss-Laguerre roots
   if (!opt.polarization_only) {
-    err = read_df_tables(dir_, hrg, df);
+    const int gen = (int)prm.get("generate_df_coefficients", 0.0);
+    if (gen == 1 || gen == 2) {           // deltaf_coefficients/ is not read
+      generate_df_tables(dir_, prm, parts, opt, df);
+      if (gen == 2 && opt.write_files) err = write_df_tables(dir_, df);
+    } else {
+      err = read_df_tables(dir_, hrg, df);
+    }
     check(err.empty(), err);
   }
   check(load_table(path_in(dir_, "tables/momentum/pT_table.dat"), pT), "cannot read tables/momentum/pT_table.dat");
@@ -751,6 +793,20 @@ extern "C" long is3d_host_read_decays(const char* workdir, int hrg_eos, long cap
       }
   }
   return n;
+}
+
+extern "C" int is3d_host_read_df_tables(const char* table_dir, int* nT, int* nmuB, long capacity, double* T, double* muB,
+                                        double* tables) {
+  DfTablesData d;
+  if (!table_dir || !nT || !nmuB || !read_df_table_dir(table_dir, d).empty()) return -1;
+  *nT = d.nT; *nmuB = d.nmuB;
+  if (T && muB && tables) {
+    if ((long)d.tab.size() > capacity) return -1;
+    std::copy(d.T.begin(), d.T.end(), T);
+    std::copy(d.muB.begin(), d.muB.end(), muB);
+    std::copy(d.tab.begin(), d.tab.end(), tables);
+  }
+  return 0;
 }
 
 extern "C" int is3d_host_param(const char* path, const char* key, double* value) {

@@ -345,6 +345,16 @@ class Engine:
         self._chk(self.lib.is3d_evaluate_df_coefficients(self._e, T, muB, E, P, bulkPi, _dp(out)))
         return out
 
+    def generate_df_tables(self, T, muB):
+        """The ten delta-f coefficient tables [10][nmuB][nT] (order of set_df_tables) of the PDG list set with set_pdg
+        on the grid T x muB, computed on the GPU with rows 1-4 of the Gauss-Laguerre table set with
+        set_gauss_laguerre (is3d_generate_df_tables, DESIGN.md 7.9: the reference's offline generator).  Installs
+        nothing: pass the result to set_df_tables."""
+        T, muB = _arr(T), _arr(muB)
+        out = np.zeros((10, len(muB), len(T)))
+        self._chk(self.lib.is3d_generate_df_tables(self._e, len(T), len(muB), _dp(T), _dp(muB), _dp(out)))
+        return out
+
     def total_yield(self, plasma, y_cut=0.5):
         """operation = 2 oversampling estimate (ParticleSampler.cpp:447-636): (Ntotal, densities[3][npart]).
         plasma = (T, E, P, muB, nB) averages; the engine's Gauss-Laguerre table must be the 32-point one."""
@@ -548,10 +558,17 @@ def surface_averages(surf, include_baryon=0):
 # run specifications (inputs shared by the engine, the oracle and the bench)
 # ------------------------------------------------------------------------------------------
 def make_spec(hrg_eos=2, chosen="pikp", pT="pT24", phi="phi24", y="y21", eta="eta24", dimension=2, df_mode=1,
-              gla_points=32, **flags):
+              gla_points=32, df_tables="shipped", df_grid=None, **flags):
     """Everything calculate_spectra needs except the surface: parameters, species, grids,
     Gauss-Laguerre table, delta-f tables.  `chosen` is a key of PDG/chosen_particles_*.dat
-    ('pikp', 'smash', 'urqmd', 'box', 'default') or an explicit MCID list."""
+    ('pikp', 'smash', 'urqmd', 'box', 'default') or an explicit MCID list.
+    df_tables = "generate": build_engine generates the delta-f tables from the spec's PDG list on df_grid = (T, muB)
+    (default: the shipped 101 x 81 grid) with the 64-point Gauss-Laguerre table, installs them and stores them as
+    spec["df"], so that whatever else reads the spec afterwards (the oracle) sees the same tables."""
+    if df_tables not in ("shipped", "generate"):
+        raise ValueError('df_tables must be "shipped" or "generate"')
+    if df_grid is not None and df_tables != "generate":
+        raise ValueError('df_grid needs df_tables="generate"')
     parts = _hrg.pdg_particles(hrg_eos)
     mcids = _hrg.chosen_mcids(chosen) if isinstance(chosen, str) else np.asarray(chosen, dtype=np.int64)
     sp = _hrg.chosen_species(parts, mcids)
@@ -566,8 +583,13 @@ def make_spec(hrg_eos=2, chosen="pikp", pT="pT24", phi="phi24", y="y21", eta="et
     params.update({k: v for k, v in flags.items() if k in _DEFAULTS})
     bins = dict(SPACETIME_BINS)
     bins.update({k: v for k, v in flags.items() if k in SPACETIME_BINS})
-    return dict(params=params, species=sp, pdg=parts, pT=pTv, phi=phiv, y=yv, eta=etav, eta_w=etaw,
+    spec = dict(params=params, species=sp, pdg=parts, pT=pTv, phi=phiv, y=yv, eta=etav, eta_w=etaw,
                 pT_w=pTw, phi_w=phiw, bins=bins, gla=(roots, weights), df=(T, muB, tab), hrg_eos=hrg_eos)
+    if df_tables == "generate":
+        gT, gB = (T, muB) if df_grid is None else (_arr(df_grid[0]), _arr(df_grid[1]))
+        spec["df"] = None                   # filled by the first build_engine
+        spec["df_generate"] = (gT, gB)
+    return spec
 
 
 def build_engine(spec, surf, T_avg=None, device=0, devices=None, species_classes=True):
@@ -584,6 +606,10 @@ def build_engine(spec, surf, T_avg=None, device=0, devices=None, species_classes
     if "pT_w" in spec:
         e.set_momentum_weights(spec["pT_w"], spec["phi_w"])
     e.set_spacetime_bins(**spec.get("bins", {}))
+    if spec.get("df") is None:             # make_spec(df_tables="generate"): from the PDG list, with 64 points
+        gT, gB = spec["df_generate"]
+        e.set_gauss_laguerre(*_data.gauss_laguerre(64))
+        spec["df"] = (gT, gB, e.generate_df_tables(gT, gB))
     e.set_gauss_laguerre(*spec["gla"])
     if T_avg is None:
         T_avg = surface_averages(surf, p["include_baryon"])[0]

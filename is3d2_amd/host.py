@@ -25,6 +25,7 @@ def load():
         lib.is3d_host_read_decays.restype = C.c_long
         lib.is3d_host_read_decays.argtypes = [C.c_char_p, C.c_int, C.c_long, PL, PI, PD, PL]
         lib.is3d_host_param.argtypes = [C.c_char_p, C.c_char_p, PD]
+        lib.is3d_host_read_df_tables.argtypes = [C.c_char_p, PI, PI, C.c_long, PD, PD, PD]
         lib.is3d_host_total_yield.argtypes = [C.c_char_p, C.c_int, C.c_int, PD, PL, C.c_char_p, C.c_int]
         lib.is3d_host_read_vorticity.restype = C.c_long
         lib.is3d_host_read_vorticity.argtypes = [C.c_char_p, C.c_int, C.c_int, PD]
@@ -94,6 +95,19 @@ def read_decays(workdir, hrg_eos):
                               nb.ctypes.data_as(C.POINTER(C.c_int)), br.ctypes.data_as(C.POINTER(C.c_double)),
                               ds.ctypes.data_as(C.POINTER(C.c_long)))
     return dict(row_mcid=mc, row_n_body=nb.astype(np.int64), row_branching=br, row_daughters=ds)
+
+
+def read_df_tables(table_dir):
+    """(T[nT], muB[nmuB], tab[10][nmuB][nT]) of the ten files c0.dat .. betapi.dat in table_dir (the driver's reader)."""
+    lib = load()
+    nT, nB = C.c_int(), C.c_int()
+    if lib.is3d_host_read_df_tables(table_dir.encode(), C.byref(nT), C.byref(nB), 0, None, None, None):
+        raise RuntimeError("df table read failed")
+    T, muB, tab = np.zeros(nT.value), np.zeros(nB.value), np.zeros((10, nB.value, nT.value))
+    PD = C.POINTER(C.c_double)
+    lib.is3d_host_read_df_tables(table_dir.encode(), C.byref(nT), C.byref(nB), tab.size, T.ctypes.data_as(PD),
+                                 muB.ctypes.data_as(PD), tab.ctypes.data_as(PD))
+    return T, muB, tab
 
 
 def param(path, key):

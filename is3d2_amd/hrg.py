@@ -195,3 +195,27 @@ def chosen_species(particles, mcids):
     return dict(mass=particles["mass"][idx].copy(), sign=particles["sign"][idx].copy(),
                 degen=particles["gspin"][idx].copy(), baryon=particles["baryon"][idx].copy(),
                 mcid=particles["mcid"][idx].copy())
+
+
+# the ten delta-f coefficient files of deltaf_coefficients/vh/<list>/ in table order, with the reference's label columns
+DF_FILES = [("c0", "c0_T4 [fm^3/GeV^3 * GeV^4]"), ("c1", "c1_T3 [fm^3/GeV^2 * GeV^3]"), ("c2", "c2_T4 [fm^3/GeV^3 * GeV^4]"),
+            ("c3", "c3_T4 [fm^3/GeV * GeV^4]"), ("c4", "c4_T5 [fm^3/GeV^2 * GeV^5]"), ("F", "F_over_T [fm^-1 / GeV]"),
+            ("G", "G [1]"), ("betabulk", "betabulk_over_T4 [fm^-4 / GeV^4]"), ("betaV", "betaV_over_T3 [fm^-3 / GeV^3]"),
+            ("betapi", "betapi_over_T4 [fm^-4 / GeV^4]")]
+
+
+def write_df_tables(dir, T, muB, tab, digits=6):
+    """Write tab[10][nmuB][nT] (Engine.generate_df_tables, data.df_tables) as the ten files c0.dat .. betapi.dat in
+    `dir`, in the format of the reference's generator (deltaf_table.cpp:122-133, 240-244), which the reference itself
+    and a run directory read: line 1 nT, line 2 nmuB, the label line, then rows "T  muB  value" with muB outer and T
+    inner, fixed with `digits` decimals (the reference: 6; 17 keeps every bit of the grid and of values near 1)."""
+    T, muB = np.asarray(T, dtype=np.float64), np.asarray(muB, dtype=np.float64)
+    tab = np.asarray(tab, dtype=np.float64).reshape(10, len(muB), len(T))
+    os.makedirs(dir, exist_ok=True)
+    row = "%%8.%df\t\t%%.%df\t\t%%.%df\n" % (digits, digits, digits)
+    for k, (name, label) in enumerate(DF_FILES):
+        with open(os.path.join(dir, name + ".dat"), "w") as f:
+            f.write("%d\n%d\nT [GeV]\t\tmuB [GeV]\t\t%s\n" % (len(T), len(muB), label))
+            for iB in range(len(muB)):
+                for iT in range(len(T)):
+                    f.write(row % (T[iT], muB[iB], tab[k, iB, iT]))

@@ -4,7 +4,7 @@ can be exercised anywhere, including on the GPU box where /root/reference is abs
 
 Layout (iS3D.cpp:96-257): iS3D_parameters.dat, input/surface.dat, PDG/<pdg file>,
 PDG/chosen_particles.dat, deltaf_coefficients/vh/<hrg>/*.dat, tables/momentum/{pT,phi,y}_table.dat,
-tables/spacetime_rapidity/eta_table.dat, tables/gauss/gla_roots_weights.txt,
+tables/spacetime_rapidity/eta_table.dat, tables/gauss/gla_roots_weights.txt, tables/gla_roots_weights_64_points.txt,
 tables/thermodynamic/, results/continuous/.
 """
 import os
@@ -96,6 +96,13 @@ def write_run_dir(d, surf, params, hrg_eos=2, chosen="pikp", pT="pT24", phi="phi
     _table(os.path.join(d, "tables/spacetime_rapidity/eta_table.dat"), *data.grid(eta))
     r, w = data.gauss_laguerre(32)
     with open(os.path.join(d, "tables/gauss/gla_roots_weights.txt"), "w") as f:
+        f.write("%d\t%d\n" % r.shape)
+        for a in range(r.shape[0]):
+            for j in range(r.shape[1]):
+                f.write("%d\t%.17g\t%.17g\n" % (a, r[a, j], w[a, j]))
+    # the generator's own 64-point table (generate_df_coefficients; the reference keeps it in tables/)
+    r, w = data.gauss_laguerre(64)
+    with open(os.path.join(d, "tables/gla_roots_weights_64_points.txt"), "w") as f:
         f.write("%d\t%d\n" % r.shape)
         for a in range(r.shape[0]):
             for j in range(r.shape[1]):
