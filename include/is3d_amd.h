@@ -466,6 +466,12 @@ int is3d_get_sample_famod_stats(const is3d_engine *e, is3d_sample_famod_stats *o
  * parent and daughter[] are indices into the chosen species (-1: a daughter that is not chosen receives nothing),
  * masses and widths in GeV (the widths only open closed 2-body channels, the jail file's rule :239-256).  1-body rows
  * (the stability marker) are ignored; rows with >= 4 bodies and closed channels are skipped and counted.
+ * is3d_set_decays4 takes the same table in rows of four daughter slots and replaces the plan exactly as is3d_set_decays
+ * does (same state rules, same errors, same device-list path), but keeps open 4-body channels too: the feed-down of a
+ * slot is the flat four-body marginal of the invariant mass^2 recoiling against it, a 12-node rule like the 3-body
+ * one (decay_math.h), and the list decays below draw flat four-body phase space (decay_mc_math.h).  After it `kept`
+ * includes the open 4-body channels, skipped_many_body counts the rows with >= 5 bodies and a 4-body row that is not
+ * open counts in skipped_closed (the width adjustment stays a 2-body rule).
  * is3d_decay_feeddown updates a host array in the spectra layout [species][pT][phi][y] in place (any such array, not
  * only the last is3d_calculate_spectra result): every species then holds thermal + feed-down; a decaying parent keeps
  * its own spectrum.  is3d_launch_feeddown is the resident form (dev_inout on the engine's GPU, is3d_finish
@@ -480,26 +486,34 @@ typedef struct {
   double branching, mass_parent, width_parent, mass[3], width[3];
 } is3d_decay_channel;
 typedef struct {
+  int parent;
+  int n_body;
+  int daughter[4];                /* chosen index, -1: not a chosen species */
+  double branching, mass_parent, width_parent, mass[4], width[4];
+} is3d_decay_channel4;
+typedef struct {
   long channels;                  /* rows given */
-  long kept;                      /* open 2- and 3-body channels */
-  long skipped_many_body;         /* rows with >= 4 bodies */
-  long skipped_closed;            /* closed 3-body channels, 2-body channels the mass adjustment cannot open */
+  long kept;                      /* open 2- and 3-body channels (is3d_set_decays4: and 4-body channels) */
+  long skipped_many_body;         /* rows with >= 4 bodies (is3d_set_decays4: >= 5 bodies) */
+  long skipped_closed;            /* closed 3-body (and 4-body) channels, 2-body channels the mass adjustment cannot open */
   long adjusted;                  /* 2-body channels the mass adjustment opened (among kept) */
   long levels;                    /* topological levels = launches */
   double branching_skipped;       /* summed branching of the skipped rows (many-body and closed) */
   double ms_total;                /* device time of the last feed-down (HIP events) */
 } is3d_decay_stats;
 int is3d_set_decays(is3d_engine *e, int n, const is3d_decay_channel *channels);
+int is3d_set_decays4(is3d_engine *e, int n, const is3d_decay_channel4 *channels);
 int is3d_decay_feeddown(is3d_engine *e, double *dN_inout);
 int is3d_launch_feeddown(is3d_engine *e, double *dev_inout, void *stream);
 int is3d_get_decay_stats(const is3d_engine *e, is3d_decay_stats *out);
 
 /* do_resonance_decays for operation = 2: Monte Carlo decays of a particle list, the counterpart of the feed-down above
  * with the same channel plan (is3d_set_decays; method in is3d2_amd/csrc/decay_mc_math.h and DESIGN.md 7.7).  Every
- * particle whose species has a kept channel decays down its chains on the GPU: 2-body isotropic, 3-body flat Dalitz;
+ * particle whose species has a kept channel decays down its chains on the GPU: 2-body isotropic, 3-body flat Dalitz,
+ * 4-body (is3d_set_decays4) flat four-body phase space;
  * zero lifetime, so daughters inherit the parent's position and cell; a daughter that is not a chosen species (-1) is
  * dropped and counted.  A particle stays in the list as a residual when the channel draw falls on the branching of
- * skipped rows (counted in undecayed) or a 3-body rejection loop reaches its cap (capped).  Primaries keep their
+ * skipped rows (counted in undecayed) or a 3- or 4-body rejection loop reaches its cap (capped).  Primaries keep their
  * order; each is replaced by its leaves in depth-first daughter-slot order.  The list is a pure function of (seed,
  * input list): bit-identical for every "sample_bytes" batching, and for a sub-range of events decayed alone.
  *
@@ -514,7 +528,7 @@ int is3d_get_decay_stats(const is3d_engine *e, is3d_decay_stats *out);
  * A device-list engine runs the call on devices[0] over the merged list.
  * Errors: IS3D_ERR_STATE without is3d_set_decays, without a sampled list (is3d_decay_sampled), or without bins for
  * bin = 1; IS3D_ERR_ARG for a negative seed, a species index out of range, events that are not contiguous and
- * increasing, a plan of more than 16 levels, an event of 2^32 or more primaries, or a primary whose decay
+ * increasing, a plan of more than 16 levels (15 when it holds a 4-body channel), an event of 2^32 or more primaries, or a primary whose decay
  * products alone exceed the "sample_bytes" bound (with the size needed). */
 typedef struct {
   long primaries, decays, undecayed, dropped_daughters, capped, final_particles, passes, batches;

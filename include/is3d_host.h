@@ -40,6 +40,9 @@ extern "C" {
  * spectra (is3d_set_decays + is3d_decay_feeddown, include/is3d_amd.h) between the spectra and the writers, so
  * results/continuous and dN_out hold thermal + feed-down, and the channel counts are printed.  With the key 0 or
  * absent, or under another operation, nothing changes.  lightest_particle is read and not used, as in the reference.
+ * four_body_decays = 1 (ours; absent or 0: as before) next to it, for operations 1 and 2: the rows are built with four
+ * daughter slots and set with is3d_set_decays4, which keeps the open 4-body channels; the printed line then counts the
+ * rows with 5 or more bodies.
  *
  * Runs the whole workflow on HIP devices [device, device + num_devices) (cells sharded);
  * dN_out (optional, capacity doubles) receives dN/(pT dpT dphi dy)[species][pT][phi][y] (operation 1)

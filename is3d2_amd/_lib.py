@@ -30,7 +30,7 @@ EXPORTS = ["is3d_abi_version", "is3d_build_id", "is3d_create", "is3d_create_devi
            "is3d_sample_uniforms", "is3d_set_sample_bins", "is3d_sample_binned", "is3d_sample_hist_size",
            "is3d_get_sample_hist", "is3d_sample_famod", "is3d_get_sample_famod_stats",
            "is3d_calculate_dN_dX_famod",
-           "is3d_set_decays", "is3d_decay_feeddown", "is3d_launch_feeddown", "is3d_get_decay_stats",
+           "is3d_set_decays", "is3d_set_decays4", "is3d_decay_feeddown", "is3d_launch_feeddown", "is3d_get_decay_stats",
            "is3d_decay_particles", "is3d_decay_sampled", "is3d_get_particle_origins", "is3d_get_decay_list_stats",
            "is3d_sample_decayed", "is3d_generate_df_tables"]
 
@@ -106,6 +106,18 @@ class DecayChannel(C.Structure):
 DECAY_DTYPE = np.dtype([("parent", "<i4"), ("n_body", "<i4"), ("daughter", "<i4", (3,)), ("branching", "<f8"),
                         ("mass_parent", "<f8"), ("width_parent", "<f8"), ("mass", "<f8", (3,)), ("width", "<f8", (3,))],
                        align=True)
+
+
+class DecayChannel4(C.Structure):
+    """is3d_decay_channel4: a decay row with four daughter slots (DECAY4_DTYPE is its numpy form)."""
+    _fields_ = [("parent", C.c_int), ("n_body", C.c_int), ("daughter", C.c_int * 4), ("branching", C.c_double),
+                ("mass_parent", C.c_double), ("width_parent", C.c_double), ("mass", C.c_double * 4),
+                ("width", C.c_double * 4)]
+
+
+DECAY4_DTYPE = np.dtype([("parent", "<i4"), ("n_body", "<i4"), ("daughter", "<i4", (4,)), ("branching", "<f8"),
+                         ("mass_parent", "<f8"), ("width_parent", "<f8"), ("mass", "<f8", (4,)), ("width", "<f8", (4,))],
+                        align=True)
 
 
 class DecayStats(C.Structure):
@@ -207,6 +219,7 @@ def load():
     lib.is3d_sample_hist_size.argtypes = [C.c_void_p, P(C.c_long), P(C.c_long)]
     lib.is3d_get_sample_hist.argtypes = [C.c_void_p, P(C.c_long), pd]
     lib.is3d_set_decays.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    lib.is3d_set_decays4.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     lib.is3d_decay_feeddown.argtypes = [C.c_void_p, pd]
     lib.is3d_launch_feeddown.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     lib.is3d_get_decay_stats.argtypes = [C.c_void_p, P(DecayStats)]

@@ -7,8 +7,9 @@
 //   k_dl_init_batch  the same from a sampler's compacted batch on the device: the key from the batch's event bounds
 //                (k_dl_bounds, sample_decay_plan.h), nothing uploaded (is3d_sample_decayed)
 //   per pass:
-//   k_dl_count   one thread per working record: the channel draw (and a 3-body channel's s23 rejection loop, which
-//                decides whether the decay is capped) -> the number of records the particle becomes
+//   k_dl_count   one thread per working record: the channel draw (and a 3-body channel's s23 or a 4-body channel's
+//                (M234, M34) rejection loop, which decides whether the decay is capped) -> the number of records the
+//                particle becomes
 //   scan         exclusive sum: every record's position after the pass
 //   k_dl_emit    redraws the channel from the reopened stream, does the kinematics and writes the daughters at the
 //                scanned position; a record that does not decay in this pass is copied
@@ -75,8 +76,8 @@ __global__ __launch_bounds__(kBlock) void k_dl_count(Args A) {
   const unsigned long long key = A.in[i].key;
   decay_mc::Stream s;
   int q = -1;
-  double s23 = 0.0;
-  const int oc = decay_mc::node_choice(A.T, sp, A.pass, A.seed, (long)(key >> 32), (long)ev, (long)(key & 0xffffffffull), s, &q, &s23);
+  double wa = 0.0, wb = 0.0;
+  const int oc = decay_mc::node_choice(A.T, sp, A.pass, A.seed, (long)(key >> 32), (long)ev, (long)(key & 0xffffffffull), s, &q, &wa, &wb);
   A.counts[i] = decay_mc::node_count(A.T, oc, q);
 }
 

@@ -22,7 +22,11 @@
 //
 // Every daughter slot that is a chosen species receives its own term (identical daughters one term each); a slot's
 // W2 is that of the OTHER daughter(s) (the jail file takes particle_2's mass for both slots: a slip, not reproduced).
-// Skipped: 1-body rows (the stability marker), >= 4 bodies and closed 3-body channels (counted); a closed 2-body
+// four-body (kept only by is3d_set_decays4): the same sum over the 12 nodes on [(m2 + m3 + m4)^2, (M - m1)^2] with
+//     h(s) = sqrt(lambda(M^2, m1^2, s)) Phi3(s; m2, m3, m4) in place of f(s) (phi3 below: the flat four-body marginal of
+//     the invariant mass^2 recoiling against daughter 1; the kernel sees two-body terms only)
+// Skipped: 1-body rows (the stability marker), >= 4 bodies (is3d_set_decays4: >= 5; a 4-body row that is not open
+// counts as closed) and closed 3-body channels (counted); a closed 2-body
 // channel takes the jail rule (:239-256) M += Gamma_R / 4, m_i -= Gamma_i / 2 until it opens -- skipped and counted
 // when every width is 0, a mass would go negative, or kAdjustCap rounds do not open it (never a loop, never an exit).
 //
@@ -214,7 +218,9 @@ inline Rule make_rule() {
 }
 
 // a kept channel: the row as given (slots past n_body cleared) with the masses the closed-channel rule left it with
-struct Kept { is3d_decay_channel c; double M, m[3]; };
+struct Kept { is3d_decay_channel4 c; double M, m[4]; };
+
+constexpr int kPhi3 = 24;               // Gauss-Legendre points of the inner rule of a 4-body slot (Phi3 below)
 
 // the launch plan: levels of parents, and per level the receivers with their two-body terms in summation order
 struct Plan {
@@ -240,10 +246,45 @@ inline bool open_two_body(double M, double m1, double m2) {
   return e1 * e1 - m1 * m1 > 0.0 && e2 * e2 - m2 * m2 > 0.0;
 }
 
-// the two-body terms of one daughter slot; false (nothing usable pushed) when a term has no p* > 0 or the 3-body
-// weights have no positive norm in floating point
+// the inner rule of a 4-body slot: n-point Gauss-Legendre on [-1, 1]
+struct Inner {
+  std::vector<double> x, w;
+};
+inline Inner make_inner(int n) {
+  Inner in;
+  in.x.resize((size_t)n);
+  in.w.resize((size_t)n);
+  gauss_legendre(n, in.x.data(), in.w.data());
+  return in;
+}
+
+// Phi3(s; a, b, c) = int_t0^t1 dt sqrt(lambda(s, a^2, t) lambda(t, b^2, c^2)) / (s t), t0 = (b + c)^2, t1 = (sqrt s - a)^2:
+// the three-body phase space of invariant mass^2 s up to a constant.  lambda(s, a^2, t) = (t1 - t)((sqrt s + a)^2 - t)
+// and lambda(t, b^2, c^2) = (t - t0)(t - (b - c)^2): the integrand ends in a square root at both ends.  With
+// t = tm - th cos(theta), tm = (t0 + t1) / 2, th = (t1 - t0) / 2: sqrt((t - t0)(t1 - t)) = th sin(theta) and
+// dt = th sin(theta) dtheta, so
+//     Phi3 = th^2 int_0^pi dtheta sin^2(theta) sqrt(((sqrt s + a)^2 - t)(t - (b - c)^2)) / (s t)
+// whose integrand is smooth on [0, pi]: Gauss-Legendre in theta (kPhi3 points; doubling them changes the weights of
+// the UrQMD 4-body rows by less than DESIGN.md 7.6 records)
+inline double phi3(const Inner& in, double s, double a, double b, double c) {
+  const double rs = sqrt(s), t0 = (b + c) * (b + c), t1 = (rs - a) * (rs - a);
+  if (!(rs > a) || !(t1 > t0)) return 0.0;
+  const double tm = 0.5 * (t0 + t1), th = 0.5 * (t1 - t0), up = (rs + a) * (rs + a), dn = (b - c) * (b - c);
+  double sum = 0.0;
+  for (size_t i = 0; i < in.x.size(); i++) {
+    const double theta = 0.5 * kPi * (1.0 + in.x[i]), sn = sin(theta), t = tm - th * cos(theta);
+    const double q = (up - t) * (t - dn);
+    sum += in.w[i] * sn * sn * sqrt(q > 0.0 ? q : 0.0) / (s * t);
+  }
+  return th * th * 0.5 * kPi * sum;
+}
+
+// the two-body terms of one daughter slot; false (nothing usable pushed) when a term has no p* > 0 or the 3- or 4-body
+// weights have no positive norm in floating point.  nother = 3 (needs `in`): the s rule runs over
+// [(ma + mb + mc)^2, (M - m1)^2] with the density h(s) = sqrt(lambda(M^2, m1^2, s)) Phi3(s; ma, mb, mc), the flat
+// four-body marginal of the invariant mass^2 recoiling against the slot's daughter
 inline bool push_terms(std::vector<Sub>& out, const Rule& r, int parent, double b, double M, double m1, int nother,
-                       const double* mo) {
+                       const double* mo, const Inner* in = nullptr) {
   if (nother == 1) {
     Sub s{};
     s.M = M; s.m1 = m1; s.parent = parent;
@@ -254,13 +295,25 @@ inline bool push_terms(std::vector<Sub>& out, const Rule& r, int parent, double 
     out.push_back(s);
     return p2 > 0.0;
   }
-  const double lo = (mo[0] + mo[1]) * (mo[0] + mo[1]), hi = (M - m1) * (M - m1), dm2 = (mo[0] - mo[1]) * (mo[0] - mo[1]);
+  const double hi = (M - m1) * (M - m1);
   double sk[kGL], fk[kGL], norm = 0.0;
-  for (int k = 0; k < kGL; k++) {
-    sk[k] = lo + 0.5 * (hi - lo) * (1.0 + r.x[k]);
-    const double q = ((M + m1) * (M + m1) - sk[k]) * (hi - sk[k]) * (sk[k] - lo) * (sk[k] - dm2);
-    fk[k] = r.w[k] * sqrt(q > 0.0 ? q : 0.0) / sk[k];
-    norm += fk[k];
+  if (nother == 2) {
+    const double lo = (mo[0] + mo[1]) * (mo[0] + mo[1]), dm2 = (mo[0] - mo[1]) * (mo[0] - mo[1]);
+    for (int k = 0; k < kGL; k++) {
+      sk[k] = lo + 0.5 * (hi - lo) * (1.0 + r.x[k]);
+      const double q = ((M + m1) * (M + m1) - sk[k]) * (hi - sk[k]) * (sk[k] - lo) * (sk[k] - dm2);
+      fk[k] = r.w[k] * sqrt(q > 0.0 ? q : 0.0) / sk[k];
+      norm += fk[k];
+    }
+  } else {
+    if (!in) return false;
+    const double lo = (mo[0] + mo[1] + mo[2]) * (mo[0] + mo[1] + mo[2]);
+    for (int k = 0; k < kGL; k++) {
+      sk[k] = lo + 0.5 * (hi - lo) * (1.0 + r.x[k]);
+      const double q = ((M + m1) * (M + m1) - sk[k]) * (hi - sk[k]);
+      fk[k] = r.w[k] * sqrt(q > 0.0 ? q : 0.0) * phi3(*in, sk[k], mo[0], mo[1], mo[2]);
+      norm += fk[k];
+    }
   }
   if (!(norm > 0.0)) return false;
   bool ok = true;
@@ -289,31 +342,49 @@ inline bool open_three_body(const Rule& r, double M, const double* m) {
   return true;
 }
 
+// a four-body channel is open when M > m1 + m2 + m3 + m4 and, in floating point, every slot's s rule has a positive
+// norm and a p* > 0 at every node
+inline bool open_four_body(const Rule& r, const Inner& in, double M, const double* m) {
+  if (!(M > m[0] + m[1] + m[2] + m[3])) return false;
+  std::vector<Sub> tmp;
+  for (int s = 0; s < 4; s++) {
+    const double mo[3] = {m[(s + 1) % 4], m[(s + 2) % 4], m[(s + 3) % 4]};
+    if (!push_terms(tmp, r, 0, 1.0, M, m[s], 3, mo, &in)) return false;
+  }
+  return true;
+}
+
 // Channel table -> plan.  species_mass[npart]: the chosen species' masses (the order of parents within a level).
+// keep_four: open 4-body rows are kept and rows with >= 5 bodies skipped (is3d_set_decays4); without it every row
+// with >= 4 bodies is skipped (is3d_set_decays).  phi3_points: the inner rule of a 4-body slot (kPhi3; a test doubles it).
 // Returns an empty string, or what is wrong with the table (an IS3D_ERR_ARG for the caller).
 inline std::string build_plan(Plan& P, const Rule& r, int npart, const double* species_mass, int n,
-                              const is3d_decay_channel* ch) {
+                              const is3d_decay_channel4* ch, bool keep_four, int phi3_points = kPhi3) {
   P = Plan{};
   P.stats.channels = n;
   std::vector<Kept>& kept = P.kept;
+  const Inner inner = keep_four ? make_inner(phi3_points) : Inner{};
+  const int max_body = keep_four ? 4 : 3;
   for (int i = 0; i < n; i++) {
-    const is3d_decay_channel& c = ch[i];
+    const is3d_decay_channel4& c = ch[i];
     if (c.n_body < 1) return "decay channel " + std::to_string(i) + ": n_body < 1";
     if (c.parent < 0 || c.parent >= npart) return "decay channel " + std::to_string(i) + ": parent index out of range";
-    for (int k = 0; k < std::min(c.n_body, 3); k++)
+    for (int k = 0; k < std::min(c.n_body, max_body); k++)
       if (c.daughter[k] < -1 || c.daughter[k] >= npart)
         return "decay channel " + std::to_string(i) + ": daughter index out of range";
     if (c.n_body == 1) continue;
-    if (c.n_body >= 4) {
+    if (c.n_body > max_body) {
       P.stats.skipped_many_body++;
       P.stats.branching_skipped += c.branching;
       continue;
     }
-    Kept k{c, c.mass_parent, {c.mass[0], c.mass[1], c.n_body == 3 ? c.mass[2] : 0.0}};
+    Kept k{c, c.mass_parent, {c.mass[0], c.mass[1], c.n_body >= 3 ? c.mass[2] : 0.0, c.n_body == 4 ? c.mass[3] : 0.0}};
     // the slots past n_body are the caller's leftovers: they must not reach the canonical order
-    for (int d = c.n_body; d < 3; d++) { k.c.daughter[d] = -1; k.c.mass[d] = 0.0; k.c.width[d] = 0.0; }
+    for (int d = c.n_body; d < 4; d++) { k.c.daughter[d] = -1; k.c.mass[d] = 0.0; k.c.width[d] = 0.0; }
     bool open = true;
-    if (c.n_body == 3) {
+    if (c.n_body == 4) {
+      open = open_four_body(r, inner, k.M, k.m);
+    } else if (c.n_body == 3) {
       open = open_three_body(r, k.M, k.m);
     } else if (!open_two_body(k.M, k.m[0], k.m[1])) {
       const bool can = c.width_parent > 0.0 || c.width[0] > 0.0 || c.width[1] > 0.0;
@@ -343,6 +414,9 @@ inline std::string build_plan(Plan& P, const Rule& r, int npart, const double* s
     if (a.c.branching != b.c.branching) return a.c.branching < b.c.branching;
     if (a.M != b.M) return a.M < b.M;
     for (int k = 0; k < 3; k++) if (a.m[k] != b.m[k]) return a.m[k] < b.m[k];
+    // the fourth slot after every earlier key: plans without a 4-body row keep their order
+    if (a.c.daughter[3] != b.c.daughter[3]) return a.c.daughter[3] < b.c.daughter[3];
+    if (a.m[3] != b.m[3]) return a.m[3] < b.m[3];
     return false;
   };
   std::stable_sort(kept.begin(), kept.end(), key_less);
@@ -394,10 +468,10 @@ inline std::string build_plan(Plan& P, const Rule& r, int npart, const double* s
           const Kept& k = kept[q];
           for (int s = 0; s < k.c.n_body; s++) {
             if (k.c.daughter[s] != d) continue;
-            double mo[2];
+            double mo[3];
             int no = 0;
             for (int o = 0; o < k.c.n_body; o++) if (o != s) mo[no++] = k.m[o];
-            push_terms(P.subs, r, p, k.c.branching, k.M, k.m[s], no, mo);
+            push_terms(P.subs, r, p, k.c.branching, k.M, k.m[s], no, mo, &inner);
             P.slots++;
           }
         }
@@ -409,6 +483,24 @@ inline std::string build_plan(Plan& P, const Rule& r, int npart, const double* s
   }
   P.stats.levels = P.levels();
   return "";
+}
+
+// a row of three daughter slots in the four-slot form (slot 3 empty)
+inline is3d_decay_channel4 widen(const is3d_decay_channel& c) {
+  is3d_decay_channel4 w{};
+  w.parent = c.parent; w.n_body = c.n_body; w.branching = c.branching;
+  w.mass_parent = c.mass_parent; w.width_parent = c.width_parent;
+  for (int k = 0; k < 3; k++) { w.daughter[k] = c.daughter[k]; w.mass[k] = c.mass[k]; w.width[k] = c.width[k]; }
+  w.daughter[3] = -1;
+  return w;
+}
+
+// the plan of is3d_set_decays: rows of three slots, every row with >= 4 bodies skipped
+inline std::string build_plan(Plan& P, const Rule& r, int npart, const double* species_mass, int n,
+                              const is3d_decay_channel* ch) {
+  std::vector<is3d_decay_channel4> wide((size_t)(n > 0 ? n : 0));
+  for (int i = 0; i < n; i++) wide[(size_t)i] = widen(ch[i]);
+  return build_plan(P, r, npart, species_mass, n, wide.data(), false);
 }
 
 // pT > 0 and ascending; phi ascending in [0, 2 pi); y ascending (3+1D)

@@ -236,7 +236,7 @@ struct is3d_engine {
   // resonance-decay feed-down (decay.hip): the channel table as given, its plan (built by is3d_set_decays, D_DECAY_PLAN),
   // the packed tables (D_DECAY_PACK) and the log slabs
   struct Feeddown {
-    std::vector<is3d_decay_channel> ch;
+    std::vector<is3d_decay_channel4> ch;
     bool launched = false;
     is3d::decay::Rule rule{};
     is3d::decay::Plan plan;

@@ -92,21 +92,37 @@ extern "C" int is3d_calculate_polarization(is3d_engine* e, double T_avg, double*
 // ------------------------------------------------------------------------------------------
 // resonance-decay feed-down of the continuous spectra (do_resonance_decays; method in decay_math.h, kernels in decay.hip)
 // ------------------------------------------------------------------------------------------
-extern "C" int is3d_set_decays(is3d_engine* e, int n, const is3d_decay_channel* ch) {
-  if (e && e->grp) return is3d::group_set_decays(e->grp, n, ch);
-  if (!e) return IS3D_ERR_ARG;
-  if (!e->in.have_species || !e->in.have_grid) return e->fail(IS3D_ERR_STATE, "is3d_set_decays: set the species and the momentum grid first");
-  if (n < 0 || (n > 0 && !ch)) return e->fail(IS3D_ERR_ARG, "is3d_set_decays: bad channel table");
+// both entry points: the table in the four-slot form; keep_four: is3d_set_decays4's rule (open 4-body rows are kept)
+static int set_decays(is3d_engine* e, const std::string& who, int n, const is3d_decay_channel4* ch, bool keep_four) {
+  if (!e->in.have_species || !e->in.have_grid) return e->fail(IS3D_ERR_STATE, who + ": set the species and the momentum grid first");
+  if (n < 0 || (n > 0 && !ch)) return e->fail(IS3D_ERR_ARG, who + ": bad channel table");
   e->input_changed(IN_DECAYS);     // no decays are set until this call has succeeded
   std::string msg = is3d::decay::check_grid((int)e->in.pT.size(), e->in.pT.data(), (int)e->in.phi.size(), e->in.phi.data(), 0, nullptr);
-  if (!msg.empty()) return e->fail(IS3D_ERR_ARG, "is3d_set_decays: " + msg);
+  if (!msg.empty()) return e->fail(IS3D_ERR_ARG, who + ": " + msg);
   e->fd.rule = is3d::decay::make_rule();
-  msg = is3d::decay::build_plan(e->fd.plan, e->fd.rule, (int)e->in.mass.size(), e->in.mass.data(), n, ch);
-  if (!msg.empty()) return e->fail(IS3D_ERR_ARG, "is3d_set_decays: " + msg);
+  msg = is3d::decay::build_plan(e->fd.plan, e->fd.rule, (int)e->in.mass.size(), e->in.mass.data(), n, ch, keep_four);
+  if (!msg.empty()) return e->fail(IS3D_ERR_ARG, who + ": " + msg);
   e->fd.ch.assign(ch, ch + n);
   e->fd.stats = e->fd.plan.stats;
   e->rebuilt(D_DECAY_PLAN);
   return IS3D_OK;
+}
+
+extern "C" int is3d_set_decays(is3d_engine* e, int n, const is3d_decay_channel* ch) {
+  if (e && e->grp) return is3d::group_set_decays(e->grp, n, ch);
+  if (!e) return IS3D_ERR_ARG;
+  std::vector<is3d_decay_channel4> wide;
+  if (n > 0 && ch) {
+    wide.resize((size_t)n);
+    for (int i = 0; i < n; i++) wide[(size_t)i] = is3d::decay::widen(ch[i]);
+  }
+  return set_decays(e, "is3d_set_decays", n, ch ? wide.data() : nullptr, false);
+}
+
+extern "C" int is3d_set_decays4(is3d_engine* e, int n, const is3d_decay_channel4* ch) {
+  if (e && e->grp) return is3d::group_set_decays4(e->grp, n, ch);
+  if (!e) return IS3D_ERR_ARG;
+  return set_decays(e, "is3d_set_decays4", n, ch, true);
 }
 
 extern "C" int is3d_get_decay_stats(const is3d_engine* e, is3d_decay_stats* out) {

@@ -71,6 +71,7 @@ const SampledList& group_list(const Group* g);
 // resonance-decay feed-down: runs on devices[0] (shard 0), on the summed spectra; group_finish after
 // group_launch_feeddown finishes that shard alone
 int group_set_decays(Group* g, int n, const is3d_decay_channel* ch);
+int group_set_decays4(Group* g, int n, const is3d_decay_channel4* ch);
 int group_launch_feeddown(Group* g, double* dev_inout, void* stream);
 int group_decay_feeddown(Group* g, double* dN_inout);
 int group_get_decay_stats(const Group* g, is3d_decay_stats* out);

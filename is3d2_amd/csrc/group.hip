@@ -488,6 +488,10 @@ int group_set_decays(Group* g, int n, const is3d_decay_channel* ch) {
   const int rc = is3d_set_decays(g->sh[0], n, ch);
   return rc ? g->shard_fail(0, rc) : IS3D_OK;
 }
+int group_set_decays4(Group* g, int n, const is3d_decay_channel4* ch) {
+  const int rc = is3d_set_decays4(g->sh[0], n, ch);
+  return rc ? g->shard_fail(0, rc) : IS3D_OK;
+}
 int group_launch_feeddown(Group* g, double* dev_inout, void* stream) {
   const int rc = is3d_launch_feeddown(g->sh[0], dev_inout, stream);
   if (rc) return g->shard_fail(0, rc);

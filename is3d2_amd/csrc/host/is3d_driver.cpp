@@ -57,8 +57,10 @@ EmissionFunctionArray::EmissionFunctionArray(const ParameterReader& params, cons
   // -1 for a daughter that is not chosen), masses and widths from the PDG list; |n_body| (the UrQMD table flags some
   // rows with a negative count); lightest_particle is read and not used, as in the reference.  Operations 1
   // (the feed-down of the spectra) and 2 (the Monte Carlo decays of the sampled list) use the table: under operation 0
-  // the key changes nothing, so a row it could not resolve must not fail the run
+  // the key changes nothing, so a row it could not resolve must not fail the run.  four_body_decays = 1 (ours; absent
+  // or 0: as before) builds the rows with four daughter slots for is3d_set_decays4, which keeps the open 4-body channels
   const int op_key = (int)p_.get("operation", 1.0);
+  const bool four_body = (int)p_.get("four_body_decays", 0.0) == 1;
   if ((int)p_.get("do_resonance_decays", 0.0) == 1 && (op_key == 1 || op_key == 2)) {
     auto find = [&](long mc) {
       for (size_t n = 0; n < particles.size(); n++) if (particles[n].mcid == mc) return (int)n;
@@ -83,9 +85,29 @@ EmissionFunctionArray::EmissionFunctionArray(const ParameterReader& params, cons
           c.mass[d] = particles[at].mass; c.width[d] = particles[at].width;
         }
         decays_.push_back(c);
+        if (four_body) {
+          is3d_decay_channel4 w{};
+          w.parent = c.parent; w.n_body = c.n_body; w.branching = c.branching;
+          w.mass_parent = c.mass_parent; w.width_parent = c.width_parent;
+          for (int d = 0; d < 4; d++) w.daughter[d] = -1;
+          for (int d = 0; d < 3; d++) { w.daughter[d] = c.daughter[d]; w.mass[d] = c.mass[d]; w.width[d] = c.width[d]; }
+          if (c.n_body >= 4) {
+            const int at = find(r.daughter[3]);
+            check(at >= 0, "decay row of " + std::to_string(par.mcid) + ": daughter " + std::to_string(r.daughter[3]) + " is not in the PDG list");
+            w.daughter[3] = chosen_index(r.daughter[3]);
+            w.mass[3] = particles[at].mass; w.width[3] = particles[at].width;
+          }
+          decays4_.push_back(w);
+        }
       }
     }
   }
+}
+
+// the channel table of the run: four slots (is3d_set_decays4) under four_body_decays = 1, else three
+int EmissionFunctionArray::set_run_decays(is3d_engine* e) const {
+  if ((int)p_.get("four_body_decays", 0.0) == 1) return is3d_set_decays4(e, (int)decays4_.size(), decays4_.data());
+  return is3d_set_decays(e, (int)decays_.size(), decays_.data());
 }
 
 static void set_or_throw(is3d_engine* e, int rc) {
@@ -178,14 +200,14 @@ void EmissionFunctionArray::run_sharded(const RunOptions& opt, int operation) {
       dN_.assign(is3d_output_size(e), 0.0);
       set_or_throw(e, is3d_calculate_spectra(e, dN_.data()));
       if ((int)p_.get("do_resonance_decays", 0.0) == 1) {     // between the spectra and the writers
-        set_or_throw(e, is3d_set_decays(e, (int)decays_.size(), decays_.data()));
+        set_or_throw(e, set_run_decays(e));
         set_or_throw(e, is3d_decay_feeddown(e, dN_.data()));
         set_or_throw(e, is3d_get_decay_stats(e, &decay_stats_));
         if (!opt.quiet) {
           const is3d_decay_stats& d = decay_stats_;
-          std::printf("\nResonance decays: %ld channels, %ld kept (%ld opened by the mass adjustment), %ld with 4 or more "
+          std::printf("\nResonance decays: %ld channels, %ld kept (%ld opened by the mass adjustment), %ld with %d or more "
                       "bodies and %ld closed skipped (summed branching %g), %ld levels, %g ms\n",
-                      d.channels, d.kept, d.adjusted, d.skipped_many_body, d.skipped_closed, d.branching_skipped, d.levels,
+                      d.channels, d.kept, d.adjusted, d.skipped_many_body, (int)p_.get("four_body_decays", 0.0) == 1 ? 5 : 4, d.skipped_closed, d.branching_skipped, d.levels,
                       d.ms_total);
         }
       }
@@ -202,7 +224,7 @@ void EmissionFunctionArray::run_sharded(const RunOptions& opt, int operation) {
       // do_resonance_decays = 1: the sampled hadrons are decayed down their chains on the device, batch by batch
       // (is3d_sample_decayed, the sampler's seed), so the lists, the offsets and the binned files carry the final hadrons
       const bool decays = (int)p_.get("do_resonance_decays", 0.0) == 1;
-      if (decays) set_or_throw(e, is3d_set_decays(e, (int)decays_.size(), decays_.data()));
+      if (decays) set_or_throw(e, set_run_decays(e));
       if (operation == 4) {      // test_sampler = 1: binned only, no list (EmissionFunction.cpp:1279-1291)
         sbins_ = read_sample_bins(p_);
         set_or_throw(e, is3d_set_sample_bins(e, &sbins_));

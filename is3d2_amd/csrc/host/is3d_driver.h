@@ -110,6 +110,8 @@ class EmissionFunctionArray {
   std::vector<long> origins_;
   is3d_decay_list_stats decay_list_stats_{};
   std::vector<is3d_decay_channel> decays_;
+  std::vector<is3d_decay_channel4> decays4_;       // four_body_decays = 1: the same rows with four daughter slots
+  int set_run_decays(is3d_engine* e) const;
   is3d_decay_stats decay_stats_{};
   const ParameterReader& p_;
   const Table &pT_, &phi_, &y_, &eta_;

@@ -58,11 +58,13 @@ def _arr(a):
 
 
 def _decay_table(channels):
-    """(n, pointer, array) of a channel table given as a DECAY_DTYPE array or a list of dicts."""
-    if isinstance(channels, np.ndarray) and channels.dtype == _lib.DECAY_DTYPE:
+    """(n, pointer, array) of a channel table given as a DECAY_DTYPE or DECAY4_DTYPE array or a list of dicts; a
+    dict with four daughters makes it a DECAY4_DTYPE table (the array's dtype tells the caller which call to use)."""
+    if isinstance(channels, np.ndarray) and channels.dtype in (_lib.DECAY_DTYPE, _lib.DECAY4_DTYPE):
         a = np.ascontiguousarray(channels)
     else:
-        a = np.zeros(len(channels), dtype=_lib.DECAY_DTYPE)
+        four = any(len(c.get("daughter", ())) > 3 for c in channels)
+        a = np.zeros(len(channels), dtype=_lib.DECAY4_DTYPE if four else _lib.DECAY_DTYPE)
         a["daughter"] = -1
         for i, c in enumerate(channels):
             for k, v in c.items():
@@ -272,9 +274,11 @@ class Engine:
     def set_decays(self, channels):
         """The decay channel table over the chosen species (after set_species and set_momentum_grid, which clear it):
         a numpy array of _lib.DECAY_DTYPE (hrg.decay_channels builds it from PDG rows) or a list of dicts with its
-        field names."""
+        field names.  A _lib.DECAY4_DTYPE array (hrg.decay_channels(..., four_body=True)), or a list in which any dict
+        has four daughters, goes through is3d_set_decays4: open 4-body channels are then kept, not skipped."""
         n, ptr, keep = _decay_table(channels)      # keep: the array behind ptr, alive over the call
-        self._chk(self.lib.is3d_set_decays(self._e, n, ptr))
+        call = self.lib.is3d_set_decays4 if keep.dtype == _lib.DECAY4_DTYPE else self.lib.is3d_set_decays
+        self._chk(call(self._e, n, ptr))
         del keep
 
     def feeddown(self, dN):

@@ -146,12 +146,17 @@ def decay_rows_with_antibaryons(rows, particles):
     return new_rows, new_parts
 
 
-def decay_channels(rows, particles, mcids, antibaryons=True):
+def decay_channels(rows, particles, mcids, antibaryons=True, four_body=False):
     """The engine's channel table (_lib.DECAY_DTYPE, Engine.set_decays) for the chosen list `mcids` from PDG decay
     rows (the form above; antibaryons = True generates the antibaryon channels first).  A row whose parent is not
     chosen is dropped; a daughter that is not chosen gets index -1 (its mass and width still enter the kinematics);
-    rows with more than three bodies keep their first three daughters (the engine skips and counts them)."""
-    from ._lib import DECAY_DTYPE
+    rows with more than three bodies keep their first three daughters (the engine skips and counts them).
+    four_body = True: the table in _lib.DECAY4_DTYPE with the fourth daughter filled (Engine.set_decays then keeps
+    the open 4-body channels); rows with more than four bodies keep their first four."""
+    from ._lib import DECAY4_DTYPE, DECAY_DTYPE
+    if four_body:
+        DECAY_DTYPE = DECAY4_DTYPE
+    slots = 4 if four_body else 3
     if antibaryons:
         rows, particles = decay_rows_with_antibaryons(rows, particles)
     rec = {}
@@ -169,7 +174,7 @@ def decay_channels(rows, particles, mcids, antibaryons=True):
         c["parent"], c["n_body"], c["branching"] = index[m], nb, br
         c["mass_parent"], c["width_parent"] = rec[m]
         c["daughter"] = -1
-        for k in range(min(nb, 3)):
+        for k in range(min(nb, slots)):
             d = int(ds[k])
             if d not in rec:
                 raise ValueError("decay row of %d: daughter %d is not in the particle list" % (m, d))

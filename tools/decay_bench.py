@@ -16,7 +16,11 @@ is3d_launch_feeddown (decay_stats ms_total), and next to it the host clock aroun
   cpu_*                       the emulator on the first --cpu-channels channels with OMP_NUM_THREADS threads (default 16)
   build_id                    is3d_build_id() of the library measured
 
-    python tools/decay_bench.py [--repeats 5] [--warmup 1] [--cpu-channels 60] [--dims 3,2]
+--four-body: the UrQMD rows of tests/golden/decays_urqmd_subset.npz over the UrQMD chosen list, once through
+is3d_set_decays (the nine four-body rows skipped) and once through is3d_set_decays4: the second line's added_terms is
+the number of two-body terms the four-body slots add (12 each); no CPU run.
+
+    python tools/decay_bench.py [--repeats 5] [--warmup 1] [--cpu-channels 60] [--dims 3,2] [--four-body]
 """
 import argparse
 import json
@@ -35,9 +39,9 @@ os.environ.setdefault("OMP_NUM_THREADS", "16")
 def work(ch, stats):
     """(slots, terms) of a channel table none of whose channels is skipped as closed."""
     assert stats["skipped_closed"] == 0
-    sel = (ch["n_body"] == 2) | (ch["n_body"] == 3)
+    sel = (ch["n_body"] == 2) | (ch["n_body"] == 3) | ((ch["n_body"] == 4) & (stats["skipped_many_body"] == 0))
     per = np.array([(c["daughter"][:c["n_body"]] >= 0).sum() for c in ch[sel]])
-    return int(per.sum()), int((per * np.where(ch["n_body"][sel] == 3, 12, 1)).sum())
+    return int(per.sum()), int((per * np.where(ch["n_body"][sel] >= 3, 12, 1)).sum())
 
 
 def main():
@@ -46,17 +50,21 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--cpu-channels", type=int, default=60)
     ap.add_argument("--dims", default="3,2")
+    ap.add_argument("--four-body", action="store_true")
     a = ap.parse_args()
     import torch
     from is3d2_amd import Engine, _lib, hrg
     from is3d2_amd import data as D
-    d = dict(np.load(os.path.join(ROOT, "tests", "golden", "decays_smash.npz")))
-    parts = hrg.pdg_particles(2)
-    mcids = hrg.chosen_mcids("smash")
+    name, eos = ("urqmd_subset", 1) if a.four_body else ("smash", 2)
+    d = dict(np.load(os.path.join(ROOT, "tests", "golden", "decays_%s.npz" % name)))
+    parts = hrg.pdg_particles(eos)
+    mcids = hrg.chosen_mcids("urqmd" if a.four_body else "smash")
     sp = hrg.chosen_species(parts, mcids)
-    ch = hrg.decay_channels(d, d, mcids)
     (pT, _), (phi, _), (y21, _) = D.grid("pT48"), D.grid("phi32"), D.grid("y21")
-    for dim in [int(v) for v in a.dims.split(",")]:
+    runs = [(dim, four) for dim in [int(v) for v in a.dims.split(",")] for four in ((False, True) if a.four_body else (False,))]
+    base_terms = {}
+    for dim, four in runs:
+        ch = hrg.decay_channels(d, d, mcids, four_body=four)
         y = y21 if dim == 3 else np.zeros(1)
         S = np.exp(-np.sqrt(pT[None, :, None, None] ** 2 + sp["mass"][:, None, None, None] ** 2) / 0.15) * \
             (1 + 0.1 * np.cos(2 * phi))[None, None, :, None] * np.exp(-y ** 2 / 8)[None, None, None, :]
@@ -87,9 +95,12 @@ def main():
                    adjusted=st["adjusted"], levels=st["levels"], slots=slots, terms=terms, points=points,
                    ms=round(t * 1e3, 3), ms_all=[round(v, 3) for v in ms], wall_ms=round(float(np.median(wall)), 3),
                    node_evals_per_s=terms * points * 144 / t, build_id=_lib.build_id())
+        if a.four_body:
+            base_terms.setdefault(dim, terms)
+            out.update(four_body=four, skipped_many_body=st["skipped_many_body"], added_terms=terms - base_terms[dim])
         got = buf.cpu().numpy()
         e.close()
-        if a.cpu_channels > 0:
+        if a.cpu_channels > 0 and not a.four_body:
             import decay_ref as R
             sub = ch[:a.cpu_channels]
             R.emulator()        # built outside the timed window

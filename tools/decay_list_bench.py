@@ -18,7 +18,14 @@ then `repeats` timed ones.  One JSON line:
                               call (table build, trees, copy out); cpu_equal: its list has the GPU's species and origins
   build_id                    is3d_build_id() of the library measured
 
-    python tools/decay_list_bench.py [--repeats 5] [--warmup 1] [--primaries 1000000] [--cells 1000] [--no-cpu]
+--four-body: the UrQMD rows of tests/golden/decays_urqmd_subset.npz over the UrQMD chosen list through
+is3d_set_decays4 (nine four-body rows: f2(1270), f1(1285), f0(1370)), and in addition
+  four_body_decays, four_body_share   decays through a four-body channel (primaries of their parents x the channels'
+                              branching: nothing in the subset feeds those parents), and their share of all decays
+  four_body_tries             mean tries of the four-body rejection loop, 1 / acceptance of the engine's own draw
+                              (10^6 tries per parent mass on the host), weighted by those decays
+
+    python tools/decay_list_bench.py [--repeats 5] [--warmup 1] [--primaries 1000000] [--cells 1000] [--no-cpu] [--four-body]
 """
 import argparse
 import json
@@ -42,12 +49,17 @@ def main():
     ap.add_argument("--cells", type=int, default=1000)
     ap.add_argument("--seed", type=int, default=7)
     ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--four-body", action="store_true")
     a = ap.parse_args()
     from is3d2_amd import _lib, build_engine, hrg, make_spec, surface_averages, synth
-    d = dict(np.load(os.path.join(ROOT, "tests", "golden", "decays_smash.npz")))
-    spec = make_spec(hrg_eos=2, chosen="smash", df_mode=2, dimension=2)
+    if a.four_body:
+        d = dict(np.load(os.path.join(ROOT, "tests", "golden", "decays_urqmd_subset.npz")))
+        spec = make_spec(hrg_eos=1, chosen="urqmd", df_mode=2, dimension=2)
+    else:
+        d = dict(np.load(os.path.join(ROOT, "tests", "golden", "decays_smash.npz")))
+        spec = make_spec(hrg_eos=2, chosen="smash", df_mode=2, dimension=2)
     mcids = spec["species"]["mcid"]
-    ch = hrg.decay_channels(d, d, mcids)
+    ch = hrg.decay_channels(d, d, mcids, four_body=a.four_body)
     s = synth.as_read(synth.surface(a.cells, seed=a.seed))
     plasma = surface_averages(s, 0)
     e = build_engine(spec, s, T_avg=plasma[0])
@@ -75,11 +87,24 @@ def main():
                wall_ms=round(tw, 3), transfer_share=round((tw - t) / tw, 3), decays_per_s=st["decays"] / (t * 1e-3),
                decays_per_s_wall=st["decays"] / (tw * 1e-3), build_id=_lib.build_id())
     e.close()
+    if a.four_body:
+        import decay4_ref as D4
+        four = ch[ch["n_body"] == 4]
+        counts = np.bincount(prim["species"], minlength=len(mcids))
+        n4 = tries = 0.0
+        for p in sorted(set(four["parent"].tolist())):
+            rows = four[four["parent"] == p]
+            k = counts[p] * rows["branching"].sum()
+            n4 += k
+            tries += k / D4.envelope(rows["mass_parent"][0], rows["mass"][0], a.seed, 1_000_000)[1]
+        out.update(four_body_channels=len(four), four_body_decays=round(n4), four_body_share=n4 / max(st["decays"], 1),
+                   four_body_tries=tries / max(n4, 1.0))
     if not a.no_cpu:
         import decay_list_ref as L
-        L.emulator()        # built outside the timed window
+        emulator, emulate = (D4.emulator, D4.emulate_list) if a.four_body else (L.emulator, L.emulate)
+        emulator()          # built outside the timed window
         t0 = time.perf_counter()
-        ref, _, orig_r, cst, _ = L.emulate(spec["species"]["mass"], ch, prim, off0, a.seed)
+        ref, _, orig_r, cst, _ = emulate(spec["species"]["mass"], ch, prim, off0, a.seed)
         ct = time.perf_counter() - t0
         out.update(cpu_threads=int(os.environ["OMP_NUM_THREADS"]), cpu_ms=round(ct * 1e3, 3), cpu_decays_per_s=cst["decays"] / ct,
                    cpu_equal=bool(len(ref) == len(out_parts) and np.array_equal(ref["species"], out_parts["species"]) and

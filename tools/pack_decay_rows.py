@@ -4,6 +4,8 @@
   tests/golden/decays_smash.npz          every row of PDG/pdg_smash.dat (1- and 2-body)
   tests/golden/decays_urqmd_subset.npz   the rows of PDG/pdg-urqmd_v3.3+.dat whose parent is lighter than
                                          URQMD_MASS_CUT GeV (they include 3- and 4-body channels)
+  tests/golden/decays_urqmd_fourbody.npz every 4-body row of PDG/pdg-urqmd_v3.3+.dat with the particle records of
+                                         their parents and daughters only
 
 Format of a conventional PDG file (readindata.cpp:973-1007): per particle
   mcid name mass width gspin baryon strange charm bottom gisospin charge decays
@@ -50,6 +52,14 @@ def main(ref, out_dir):
     d = read(os.path.join(ref, "PDG", "pdg-urqmd_v3.3+.dat"), URQMD_MASS_CUT)
     np.savez_compressed(os.path.join(out_dir, "decays_urqmd_subset.npz"), **d)
     print("urqmd subset: %d rows, bodies %s" % (len(d["row_mcid"]), sorted(set(d["row_n_body"].tolist()))))
+    d = read(os.path.join(ref, "PDG", "pdg-urqmd_v3.3+.dat"))
+    rows = np.abs(d["row_n_body"]) == 4
+    used = set(d["row_mcid"][rows].tolist()) | set(d["row_daughters"][rows][:, :4].ravel().tolist())
+    parts = np.array([int(m) in used for m in d["p_mcid"]])
+    d = {k: v[rows] if k.startswith("row_") else v[parts] for k, v in d.items()}
+    np.savez_compressed(os.path.join(out_dir, "decays_urqmd_fourbody.npz"), **d)
+    print("urqmd four-body: %d rows, summed branching %.4g, %d particle records" %
+          (len(d["row_mcid"]), d["row_branching"].sum(), len(d["p_mcid"])))
 
 
 if __name__ == "__main__":
