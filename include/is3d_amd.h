@@ -165,10 +165,18 @@ int is3d_set_species(is3d_engine *e, int n, const double *mass, const double *si
  * equal to rounding (< 1e-9 relative, tests/test_gpu_classes.py) to integrating each species separately (on = 0):
  * the two launches group different lanes into their wavefronts and can pick other cell splits, and they are
  * bit-identical only when the per-wavefront Boltzmann-tail decisions coincide as well.
- * is3d_species_integrated returns the number of species the kernels integrate (SMASH 444 -> 193), or minus an
- * IS3D_ERR_* code when the tables cannot be finalised (is3d_last_error says why). */
+ * is3d_species_integrated counts the integrand classes under that documented key (SMASH 444 -> 193, UrQMD 305 -> 124;
+ * the species count with classes off), whatever the run's flags.
+ * The kernels integrate the *lane classes*, which is3d_lanes_integrated counts.  They are the integrand classes, or
+ * fewer when the run is baryon-blind: with include_baryon = 0 the baryon number of a species multiplies only per-cell
+ * quantities that are zero (alphaB, V^mu, and the delta-f coefficients c1 / G, which the engine checks to be zero on
+ * the table row such a run uses), so a baryon and its antibaryon of equal (mass, sign) are one integrand and share a
+ * lane (SMASH 193 -> 135, UrQMD 124 -> 75); the reduction writes every member with its own degeneracy.  With
+ * include_baryon = 1, a table that fails the check, or classes off, the two counts are equal.
+ * Both return minus an IS3D_ERR_* code when the tables cannot be finalised (is3d_last_error says why). */
 int is3d_set_species_classes(is3d_engine *e, int on);
 int is3d_species_integrated(is3d_engine *e);
+int is3d_lanes_integrated(is3d_engine *e);
 int is3d_set_pdg(is3d_engine *e, int n, const double *mass, const double *sign,
                  const double *degeneracy, const double *baryon);
 int is3d_set_momentum_grid(is3d_engine *e, int npT, const double *pT, int nphi, const double *phi,

@@ -18,7 +18,7 @@ IS3D_OK, IS3D_ERR_ARG, IS3D_ERR_STATE, IS3D_ERR_DEVICE, IS3D_ERR_DF_RANGE, IS3D_
 
 # every symbol include/is3d_amd.h declares
 EXPORTS = ["is3d_abi_version", "is3d_build_id", "is3d_create", "is3d_create_devices", "is3d_destroy", "is3d_last_error", "is3d_set_params", "is3d_set_tuning", "is3d_get_tuning",
-           "is3d_set_species", "is3d_set_species_classes", "is3d_species_integrated", "is3d_set_pdg", "is3d_set_momentum_grid", "is3d_set_gauss_laguerre",
+           "is3d_set_species", "is3d_set_species_classes", "is3d_species_integrated", "is3d_lanes_integrated", "is3d_set_pdg", "is3d_set_momentum_grid", "is3d_set_gauss_laguerre",
            "is3d_set_df_tables", "is3d_set_surface", "is3d_set_surface_device", "is3d_set_cell_window", "is3d_cell_costs", "is3d_calculate_spectra",
            "is3d_launch", "is3d_finish", "is3d_get_stats", "is3d_output_size", "is3d_evaluate_df_coefficients",
            "is3d_surface_averages", "is3d_get_jonah_table", "is3d_set_momentum_weights", "is3d_set_spacetime_bins",
@@ -165,6 +165,7 @@ def load():
     lib.is3d_set_species.argtypes = [C.c_void_p, C.c_int, pd, pd, pd, pd]
     lib.is3d_set_species_classes.argtypes = [C.c_void_p, C.c_int]
     lib.is3d_species_integrated.argtypes = [C.c_void_p]
+    lib.is3d_lanes_integrated.argtypes = [C.c_void_p]
     lib.is3d_set_pdg.argtypes = [C.c_void_p, C.c_int, pd, pd, pd, pd]
     lib.is3d_set_momentum_grid.argtypes = [C.c_void_p, C.c_int, pd, C.c_int, pd, C.c_int, pd, C.c_int, pd, pd]
     lib.is3d_set_gauss_laguerre.argtypes = [C.c_void_p, C.c_int, C.c_int, pd, pd]

@@ -133,8 +133,10 @@ struct is3d_engine {
     // integrand classes (is3d_set_species_classes, default on): the momentum integrals see a species only through
     // its (mass, sign, baryon) -- plus, in PTM, whether its degeneracy is zero (ptm_gkey) -- and the engine applies the degeneracy once, to the cell sum, in k_reduce (the reference
     // multiplies every cell's term by prefactor x degeneracy, MomentumSpectra.cpp:365: the same product up to
-    // rounding), so sorted species with identical keys have bit-identical cell sums: k_spectra / k_dndx integrate one lane species per class (SMASH 444 -> 193, UrQMD 305 -> 124) and the
-    // reduction writes every member.
+    // rounding), so sorted species with identical keys have bit-identical cell sums: the integrand classes (SMASH 444 -> 193, UrQMD 305 -> 124), which
+    // is3d_species_integrated counts.  k_spectra / k_dndx integrate one lane per *lane class* and the reduction writes
+    // every member: the lane classes are the integrand classes, or fewer when the run is baryon-blind
+    // (Tables::nlane: 135 / 75; is3d_lanes_integrated).
     bool classes = true;
   } in;
 
@@ -159,13 +161,25 @@ struct is3d_engine {
     int* d_sorig = nullptr;
     // PTM renormalisation classes: sorted species with identical (mass, sign, baryon) and a zero / nonzero degeneracy
     // share one n_linear / n_mod per cell (ptm_renorm depends on nothing else, ptm_gkey): d_rcls[s] = class of sorted species s,
-    // d_rrep[k] = a representative sorted species of class k (SMASH 444 -> nrcls classes)
+    // d_rrep[k] = a representative sorted species of class k (SMASH 444 -> nrcls classes).  A baryon-blind run keys
+    // them without the baryon number, as the lane classes.
     int* d_rcls = nullptr;
     int* d_rrep = nullptr;
     int nrcls = 0;
-    // integrand classes (Inputs::classes).  d_cmass/d_csign/d_cbaryon: class values, d_crcls: class -> renorm class,
-    // d_cmem[d_cmem_off[c] ..]: member sorted species of class c, d_scls: sorted species -> class.
-    int ncls = 0;
+    // Two levels of classes (Inputs::classes).
+    //  - ncls: the integrand classes under the documented key (mass, sign, baryon [, PTM: g == 0]); a count only, what
+    //    is3d_species_integrated reports.
+    //  - nlane: the lane classes, what the kernels integrate and every table below describes.  Their key is the class
+    //    key without the baryon number when the run is baryon-blind (finalize_tables baryon_blind: include_baryon = 0
+    //    and every delta-f table entry that multiplies the baryon number is zero), else the class key itself: SMASH 193
+    //    classes -> 135 lanes, UrQMD 124 -> 75.  The lane's baryon operand is its first member's; a blind run only
+    //    ever multiplies it by zeros.
+    // d_cmass/d_csign/d_cbaryon: lane values, d_crcls: lane -> renorm class, d_cmem[d_cmem_off[c] ..]: member sorted
+    // species of lane c (each written with its own degeneracy), d_scls: sorted species -> lane.
+    // nlane counts the lane slots of the tables, nlive the lane classes among them (is3d_lanes_integrated): the same,
+    // except where finalize_tables appends empty lanes to keep a table launch.
+    int ncls = 0, nlane = 0, nlive = 0;
+    bool blind = false;      // the run is baryon-blind and classes are on: lanes merge baryon / antibaryon pairs
     std::vector<int> scls;   // host copy of d_scls
     const double *d_cmass = nullptr, *d_csign = nullptr, *d_cbaryon = nullptr;
     int *d_crcls = nullptr, *d_cmem_off = nullptr, *d_cmem = nullptr, *d_scls = nullptr;

@@ -41,6 +41,7 @@
 #include <array>
 #include <cstdint>
 #include <map>
+#include <set>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -213,6 +214,13 @@ extern "C" int is3d_species_integrated(is3d_engine* e) {
   return rc ? -rc : e->tbl.ncls;       // an error as minus its IS3D_ERR_* code (a count is >= 1)
 }
 
+extern "C" int is3d_lanes_integrated(is3d_engine* e) {
+  if (e && e->grp) return is3d::group_lanes_integrated(e->grp);
+  if (!e) return -IS3D_ERR_ARG;
+  const int rc = finalize_tables(e);
+  return rc ? -rc : e->tbl.nlive;      // without the empty lanes that keep a table launch (finalize_tables)
+}
+
 extern "C" int is3d_set_pdg(is3d_engine* e, int n, const double* mass, const double* sign, const double* degeneracy,
                             const double* baryon) {
   if (e && e->grp) return is3d::group_set_pdg(e->grp, n, mass, sign, degeneracy, baryon);
@@ -336,7 +344,7 @@ static SpectraPlan spectra_plan(const is3d_engine* e, bool allow_ts = true) {
   SpectraPlan P{};
   P.npw = 1;
   const int mode = e->in.p.df_mode, dim = e->in.p.dimension;
-  const int np = e->tbl.ncls, nphi = (int)e->in.phi.size();     // lane species: the integrand classes
+  const int np = e->tbl.nlane, nphi = (int)e->in.phi.size();     // lane species: the lane classes
   const int npT = (int)e->in.pT.size();
   const int nk = (dim == 3) ? (int)e->in.y.size() : 1, nl = (dim == 3) ? 1 : (int)e->in.eta.size();
   P.nq = nk * nl;
@@ -388,7 +396,10 @@ static SpectraPlan spectra_plan(const is3d_engine* e, bool allow_ts = true) {
                              (mode == CE && !P.tb && !P.mp && qrows && P.KJ % 4 == 0 ? tb * 2 * tile * nphp + 1 : 0) +
                              (mode >= PTM && qrows ? tile * qrows * (P.KJ + 1) + 1 : 0));
   };
-  shape(spectra_kj_fill(nphi, (long)np * P.nq));
+  // the phi block's lane fill is judged by the integrand classes, not by the lanes a baryon-blind run merges them
+  // into (the same count otherwise): a merge then never moves a grid of one or two q rows off its one-block table
+  // launch (SMASH, 24 phi points, one rapidity: 193 tasks keep KJ = 24 and F_TS where 135 would take KJ = 8)
+  shape(spectra_kj_fill(nphi, (long)e->tbl.ncls * P.nq));
   P.ly = 0;
   P.shmem = lds_bytes(P.nqmax);
   // RTA-CE's table launch adds {TE, T2} to the {PD, T1} rows: where that costs the third workgroup per CU
@@ -471,6 +482,37 @@ static SpectraPlan spectra_plan(const is3d_engine* e, bool allow_ts = true) {
 // ~1e-16; rounds 3 / 4 keyed on g itself)
 static uint64_t ptm_gkey(double g) { return (uint64_t)(g == 0.0 ? 1 : 0); }
 
+// Baryon-blind runs: the lanes of a baryon and of its antibaryon of equal (mass, sign) integrate the same integrand, so
+// the lane classes drop the baryon number from their key (finalize_tables).  A lane's baryon number b enters only as a
+// factor of per-cell quantities:
+//   the separable lanes   b R_CHEM, mT b Y_S1, b R_SCB, b R_SSB, b R_L0B      (sep_skips, sep_setup)
+//   the modified lanes    b R_CHEMM                                            (mod_skips, mod_setup)
+//   ptm_renorm            b alphaB, b alphaB_mod, b N10 G
+// With include_baryon = 0 every prologue packs alphaB = 0, nB / (E + P) = 0 and V^mu = 0 whatever the surface holds
+// (prep_grad_ce, prep_feqmod, prep_famod_a), which zeroes R_CHEM and every V^mu product (Grad's c3 and c4, the betaV
+// terms).  What is left comes from the delta-f table, per mode:
+//   Grad (1)        c1, column 1: R_BULK1 = c1 Pi -> Y_S1, R_SCB, R_SSB
+//   RTA-CE (2)      G, column 6:  R_BULK1 = G Pi / betabulk -> R_L0B
+//   PTM (3)         G, column 6:  the same in its linearised fallback; alphaB_mod = alphaB + Pi G / betabulk -> R_CHEMM;
+//                   N10 G in ptm_renorm
+//   PTB (4)         none: R_CHEM = 0, lambda and z come from the Jonah table (and include_baryon = 1 is refused)
+//   PTMA (5)        none: R_CHEM = R_CHEMM = alphaB, no delta-f coefficient reaches the lanes
+// df_eval sets c1 = G = 0 without reading them when include_baryon = 0 -- but that is the assumption this function
+// exists to check: the column must be identically zero on the table row such a run uses (muB row 0, every T), or the
+// lanes keep the full key.  Tables from is3d_generate_df_tables reach the engine through is3d_set_df_tables like any
+// other, so the same check sees them.
+constexpr double kEmptyLaneMass = 1.0e6;   // GeV: the lanes finalize_tables adds to keep a table launch (no members)
+static bool baryon_blind(const is3d_engine* e) {
+  if (e->in.p.include_baryon) return false;
+  const int mode = e->in.p.df_mode;
+  const int col = mode == GRAD ? 1 : (mode == CE || mode == PTM) ? 6 : -1;
+  if (col < 0) return true;
+  const double* row = e->in.tab.data() + (size_t)col * e->in.nmuB * e->in.nT;   // muB row 0
+  for (int i = 0; i < e->in.nT; i++)
+    if (row[i] != 0.0) return false;     // NaN too
+  return true;
+}
+
 int finalize_tables(is3d_engine* e) {
   if (!e->in.have_params) return e->fail(IS3D_ERR_STATE, "is3d_set_params not called");
   if (!e->in.have_species) return e->fail(IS3D_ERR_STATE, "is3d_set_species not called");
@@ -548,13 +590,19 @@ int finalize_tables(is3d_engine* e) {
   std::vector<double> pTw(e->in.pT.size(), 0.0), phiw(e->in.phi.size(), 0.0);
   if (e->in.have_weights) { pTw = e->in.pT_w; phiw = e->in.phi_w; }
   const size_t opw = cput(pTw.data(), pTw.size()), ophw = cput(phiw.data(), phiw.size());
-  // integrand classes of the sorted species (first occurrence order, so the class list stays mass-sorted)
+  // The classes of the sorted species, on two levels (engine.h Tables).  The integrand classes keep the documented key
+  // and are only counted; the lane classes, which every table below describes, drop the baryon number from it when
+  // the run is baryon-blind.  First occurrence order, so the lane list stays mass-sorted.
+  const bool blind = e->in.classes && baryon_blind(e);
+  auto bkey = [&](int i) { return blind ? (uint64_t)0 : __builtin_bit_cast(uint64_t, sb[i]); };
   std::vector<int> scls(np), crep, cmem_off, cmem;
   {
     std::map<std::array<uint64_t, 4>, int> cls;
+    std::set<std::array<uint64_t, 4>> full;
     for (int i = 0; i < np; i++) {
-      const std::array<uint64_t, 4> key{__builtin_bit_cast(uint64_t, sm[i]), __builtin_bit_cast(uint64_t, ss[i]),
-                                        __builtin_bit_cast(uint64_t, sb[i]), mode == PTM ? ptm_gkey(sd[i]) : (uint64_t)0};
+      const uint64_t gk = mode == PTM ? ptm_gkey(sd[i]) : (uint64_t)0;
+      const std::array<uint64_t, 4> key{__builtin_bit_cast(uint64_t, sm[i]), __builtin_bit_cast(uint64_t, ss[i]), bkey(i), gk};
+      full.insert({key[0], key[1], __builtin_bit_cast(uint64_t, sb[i]), gk});
       int c = (int)crep.size();
       if (e->in.classes) {
         auto it = cls.find(key);
@@ -571,12 +619,26 @@ int finalize_tables(is3d_engine* e) {
     cmem.resize(np);
     std::vector<int> fill(cmem_off.begin(), cmem_off.end() - 1);
     for (int i = 0; i < np; i++) cmem[fill[scls[i]]++] = i;
-    e->tbl.ncls = nc;
+    e->tbl.nlive = e->tbl.nlane = nc;
+    e->tbl.ncls = e->in.classes ? (int)full.size() : np;
+    e->tbl.blind = blind;
     e->tbl.scls = scls;
+    // A merge must not cost the Grad / RTA-CE table launches (F_TB, F_TS): a workgroup's 256 tasks span at most
+    // kTbQ q rows only from kTbLanes lanes on (spectra_plan nqmax).  A list whose classes reach that count but whose
+    // merged lanes do not (UrQMD: 124 classes, 75 lanes) gets empty lanes up to it: no member, so nothing is written
+    // for them, and a mass no cell can reach, so every one is skipped at the lane's first test (sep_skips) like the
+    // heavy resonances of a cold cell.  86 lane slots still beat 124.
+    constexpr int kTbLanes = (kBlock - 1) / (kTbQ - 1) + 1;
+    static_assert((kBlock - 1) / kTbLanes + 2 <= kTbQ && (kBlock - 1) / (kTbLanes - 1) + 2 > kTbQ, "the smallest lane count of the table launches");
+    if (blind && mode <= CE && nc < kTbLanes && e->tbl.ncls >= kTbLanes) {
+      e->tbl.nlane = kTbLanes;
+      cmem_off.resize(kTbLanes + 1, cmem_off.back());
+    }
   }
-  std::vector<double> cm(e->tbl.ncls), csn(e->tbl.ncls), cby(e->tbl.ncls);
-  for (int c = 0; c < e->tbl.ncls; c++) { cm[c] = sm[crep[c]]; csn[c] = ss[crep[c]]; cby[c] = sb[crep[c]]; }
-  const size_t ocm = cput(cm.data(), e->tbl.ncls), ocs_ = cput(csn.data(), e->tbl.ncls), ocb = cput(cby.data(), e->tbl.ncls);
+  const int nlane = e->tbl.nlane, nlive = e->tbl.nlive;
+  std::vector<double> cm(nlane, kEmptyLaneMass), csn(nlane, 1.0), cby(nlane, 0.0);
+  for (int c = 0; c < nlive; c++) { cm[c] = sm[crep[c]]; csn[c] = ss[crep[c]]; cby[c] = sb[crep[c]]; }
+  const size_t ocm = cput(cm.data(), nlane), ocs_ = cput(csn.data(), nlane), ocb = cput(cby.data(), nlane);
   // {pT cos phi, pT sin phi} per (pT, padded phi slot) for k_spectra's scalar loads (same products as
   // its LDS copy s_cs); 16-byte aligned
   if (cb.size() & 1) cb.push_back(0.0);
@@ -623,16 +685,16 @@ int finalize_tables(is3d_engine* e) {
     std::map<std::array<uint64_t, 4>, int> cls;
     for (int i = 0; i < np; i++) {
       const std::array<uint64_t, 4> key{__builtin_bit_cast(uint64_t, sm[i]), __builtin_bit_cast(uint64_t, ss[i]),
-                                        ptm_gkey(sd[i]), __builtin_bit_cast(uint64_t, sb[i])};
+                                        ptm_gkey(sd[i]), bkey(i)};     // baryon-blind: as the lanes (baryon_blind)
       auto it = cls.find(key);
       if (it == cls.end()) { it = cls.emplace(key, (int)rrep.size()).first; rrep.push_back(i); }
       rcls[i] = it->second;
     }
   }
   e->tbl.nrcls = (int)rrep.size();
-  const int nc = e->tbl.ncls;
-  std::vector<int> crcls(nc);
-  for (int c = 0; c < nc; c++) crcls[c] = rcls[crep[c]];
+  const int nc = nlane;
+  std::vector<int> crcls(nc, 0);
+  for (int c = 0; c < nlive; c++) crcls[c] = rcls[crep[c]];
   // ints after the doubles: sorig[np] | rcls[np] | rrep[np] | crcls[nc] | cmem_off[nc + 1] | cmem[np] | scls[np]
   std::vector<int> ib;
   for (int i = 0; i < np; i++) ib.push_back(e->in.order[i]);
@@ -992,7 +1054,7 @@ static int integral_plan(is3d_engine* e, const SpectraPlan& P, long nw, Integral
   const int KJ = P.KJ, njb = P.njb;
   if (!spectra_kj_supported(KJ)) return e->fail(IS3D_ERR_ARG, "internal: no k_spectra instantiation for this phi block");
   if (P.shmem > 160 * 1024) return e->fail(IS3D_ERR_ARG, "momentum grid too large for the LDS tile (phi table)");
-  const int nc = e->tbl.ncls;      // lane species: one per integrand class (the reduction writes the members)
+  const int nc = e->tbl.nlane;     // lane species: one per lane class (the reduction writes the members)
   const long ntask = (long)nc * nk * nl * njb;
   const long bx = (ntask + kBlock - 1) / kBlock;            // lane groups per pT (F_MP: 1, ntask <= 128)
   if (!P.ly) {
@@ -1051,7 +1113,7 @@ static int enqueue_spectra(is3d_engine* e, const IntegralPlan& I, const double* 
   const int npT = (int)e->in.pT.size(), nphi = (int)e->in.phi.size();
   const int ny_out = (dim == 3) ? (int)e->in.y.size() : 1;
   const int nk = ny_out, nl = (dim == 3) ? 1 : (int)e->in.eta.size();
-  const int KJ = P.KJ, njb = P.njb, nc = e->tbl.ncls;
+  const int KJ = P.KJ, njb = P.njb, nc = e->tbl.nlane;
   const long nsplit = I.nsplit, cps = I.cps, wgs = I.wgs;
   if (mode >= PTM) {
     if (!e->ws.d_fb.reserve(nw + 1 + kFbBlocks)) return e->fail(IS3D_ERR_DEVICE, "hipMalloc(fallback list) failed");
@@ -1169,7 +1231,7 @@ static int enqueue_reduce(is3d_engine* e, const IntegralPlan& I, double* dev_out
   const int npT = (int)e->in.pT.size(), nphi = (int)e->in.phi.size();
   const int ny_out = (dim == 3) ? (int)e->in.y.size() : 1;
   const int nk = ny_out, nl = (dim == 3) ? 1 : (int)e->in.eta.size();
-  const int nc = e->tbl.ncls;
+  const int nc = e->tbl.nlane;
   ReduceArgs ra{};
   ra.slab = e->ws.d_slab.get(); ra.sstride = I.sstride; ra.nsplit = I.fold ? 1 : (int)(I.nsplit + I.nsplit_fb);
   ra.nbx = (int)I.bx; ra.npart = nc; ra.npT = npT; ra.nphi = nphi; ra.nk = nk; ra.nl = nl; ra.ny_out = ny_out; ra.kj = I.P.KJ;

@@ -44,7 +44,7 @@ static int dndx_finish(is3d_engine* e, long wlo, long n, const char* df_msg, dou
     const int KJ = spectra_kj(nphi);
     const int njb = (nphi + KJ - 1) / KJ;
     DndxArgs da{};
-    const int nc = e->tbl.ncls;    // lane species: the integrand classes (k_stbin scales and writes the members)
+    const int nc = e->tbl.nlane;   // lane species: the lane classes (k_stbin scales and writes the members)
     da.ntask = nk * njb * nl;
     da.Sl = std::min(nc, 64);
     da.Yl = 64 / da.Sl;
@@ -248,7 +248,7 @@ extern "C" int is3d_get_cell_yields(const is3d_engine* e, double* dN_dy_cell) {
   const long n = e->op0.ycell_n;
   const int np = (int)e->in.mass.size();
   if (n == 0) return IS3D_OK;
-  std::vector<double> y((size_t)e->tbl.ncls * n);
+  std::vector<double> y((size_t)e->tbl.nlane * n);
   if (hipSetDevice(e->device) != hipSuccess) return IS3D_ERR_DEVICE;
   if (hipMemcpy(y.data(), e->op0.d_ycell.get(), y.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return IS3D_ERR_DEVICE;
   const double pref = std::pow(2.0 * M_PI * kHbarC, -3);

@@ -28,6 +28,7 @@ long group_get_tuning(const Group* g, const char* key);   // shard 0's value; "p
 int group_set_species(Group* g, int n, const double* mass, const double* sign, const double* degen, const double* baryon);
 int group_set_species_classes(Group* g, int on);
 int group_species_integrated(Group* g);
+int group_lanes_integrated(Group* g);
 // record an error on the group (is3d_last_error of a device-list engine reads the group's message)
 int group_fail(Group* g, int code, const char* msg);
 int group_set_pdg(Group* g, int n, const double* mass, const double* sign, const double* degen, const double* baryon);

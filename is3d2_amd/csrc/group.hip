@@ -199,6 +199,10 @@ int group_species_integrated(Group* g) {
   const int n = is3d_species_integrated(g->sh[0]);
   return n < 0 ? -g->shard_fail(0, -n) : n;
 }
+int group_lanes_integrated(Group* g) {
+  const int n = is3d_lanes_integrated(g->sh[0]);
+  return n < 0 ? -g->shard_fail(0, -n) : n;
+}
 int group_fail(Group* g, int code, const char* msg) { return g->fail(code, msg); }
 int group_set_pdg(Group* g, int n, const double* m, const double* s, const double* d, const double* b) {
   return each(g, [&](is3d_engine* e) { return is3d_set_pdg(e, n, m, s, d, b); });

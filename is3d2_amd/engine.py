@@ -142,9 +142,18 @@ class Engine:
         self._chk(self.lib.is3d_set_species_classes(self._e, int(bool(on))))
 
     def species_integrated(self):
+        """The integrand classes under the documented key (include/is3d_amd.h); see lanes_integrated."""
         n = self.lib.is3d_species_integrated(self._e)
         if n < 0:
             self._chk(-n)     # an error comes back as minus its IS3D_ERR_* code
+        return n
+
+    def lanes_integrated(self):
+        """The lane classes the kernels integrate: the integrand classes, or fewer when the run is baryon-blind
+        (is3d_lanes_integrated: SMASH 193 -> 135 without baryon terms)."""
+        n = self.lib.is3d_lanes_integrated(self._e)
+        if n < 0:
+            self._chk(-n)
         return n
 
     def set_pdg(self, mass, sign, degen, baryon):
@@ -342,7 +351,10 @@ class Engine:
     def stats(self):
         s = _lib.Stats()
         self._chk(self.lib.is3d_get_stats(self._e, C.byref(s)))
-        return {k: getattr(s, k) for k, _ in s._fields_}
+        out = {k: getattr(s, k) for k, _ in s._fields_}
+        # the lane classes of the tables as they stand (is3d_stats itself is fixed by the ABI); 0 before a full setup
+        out["lanes_integrated"] = max(0, self.lib.is3d_lanes_integrated(self._e))
+        return out
 
     def evaluate_df_coefficients(self, T, muB, E, P, bulkPi):
         out = np.zeros(15)

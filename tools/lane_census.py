@@ -1,6 +1,7 @@
 """Per-pT census of the separable lanes of a Grad F_TB launch (skipped / Boltzmann-tail / other), from the
 host build of the device math (tests/native/cf_emulator.cpp) on a cell sample of BASELINE config 2.
-usage: python tools/lane_census.py [cells] | --waves (per-wavefront mix, wave_census)"""
+usage: python tools/lane_census.py [cells] | --waves [--lane-key] (per-wavefront mix, wave_census; --lane-key: the
+lane classes of a baryon-blind run, key (mass, sign), instead of the integrand classes, key (mass, sign, baryon))"""
 import ctypes as C
 import os
 import sys
@@ -28,7 +29,7 @@ def lane_census(n):
     print("all    %6.3f %6.3f %6.3f" % tuple(a))
 
 
-def wave_census(n=60, pTs=(0, 8, 16, 24, 32, 40, 47)):
+def wave_census(n=60, pTs=(0, 8, 16, 24, 32, 40, 47), lane_key=False):
     """Per-wavefront census of the Grad F_TB launch with integrand classes: for each (pT, cell, 64-lane wave of
     class lanes, task = class + nclass q) the mix of lane kinds among its live lanes.  A wave holding both
     Boltzmann-tail and other fast lanes runs both phi loops back to back."""
@@ -41,6 +42,8 @@ def wave_census(n=60, pTs=(0, 8, 16, 24, 32, 40, 47)):
     emulator().emu_set_census_lanes(None)
     buf = buf.reshape(npT, n, ns, nq)
     key = list(zip(sp["species"]["mass"], sp["species"]["sign"], sp["species"]["baryon"]))
+    if lane_key:     # config 2 carries no baryon terms: its lanes merge baryon / antibaryon pairs (engine.hip baryon_blind)
+        key = [k[:2] for k in key]
     rep, seen = [], set()
     for i, k in enumerate(key):
         if k not in seen:
@@ -61,11 +64,12 @@ def wave_census(n=60, pTs=(0, 8, 16, 24, 32, 40, 47)):
         tot["near"] += int((has_n & ~has_f).sum())
         tot["fast"] += int((~has_t & has_f).sum()); tot["skip"] += int((~has_t & ~has_f & ~has_n).sum())
     allw = sum(tot.values())
+    print("%d lanes, %d tasks, %d wavefronts per pT (%d live lanes in the last)" % (nc, ntask, nw, ntask - (nw - 1) * 64))
     print("waves: " + "  ".join("%s %.3f" % (k, v / allw) for k, v in tot.items()))
 
 
 if __name__ == "__main__":
     if "--waves" in sys.argv:
-        wave_census()
+        wave_census(lane_key="--lane-key" in sys.argv)
     else:
         lane_census(int(sys.argv[1]) if len(sys.argv) > 1 else 200)
